@@ -325,6 +325,54 @@ def time_dominant_kernel(B, device):
     return out
 
 
+DUMP_SAMPLE = 1 << 20             # --dump-outputs: positions kept of an output larger than this (float32: 4 MB)
+DUMP_PARAM_SAMPLE = 64            # positions kept of every parameter
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _seeded_positions(name, numel, k):
+    """k positions of a flattened tensor of numel elements, fixed by the name and the size alone (its own CPU generator)."""
+    import zlib
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+    return torch.randint(0, numel, (k,), generator=g)
+
+
+def dump_outputs(path, loss, out, model):
+    """--dump-outputs: what the last timed step computed, as <path>/<name>.npy --
+      loss                 the summed training loss the step back-propagated (float64, shape [1]);
+      <key>                every tensor of the forward's output dict (losses, logits, labels; float32); one with more than
+                           DUMP_SAMPLE elements is written as <key>_sample, its values at DUMP_SAMPLE seeded positions;
+      param_norms          L2 norm of every parameter after the optimizer step, in named_parameters() order (float64);
+      param_sample         DUMP_PARAM_SAMPLE seeded positions of every parameter after the step, concatenated (float32).
+    `out` is empty for a replayed hipGraph step (its activations live in the graph's private pool): loss and parameters only."""
+    import numpy as np
+    arrays = {"loss": loss.detach().double().reshape(1)}
+    for key in sorted(out):
+        t = out[key]
+        if not isinstance(t, torch.Tensor):
+            continue
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            t, key = t[_seeded_positions(key, t.numel(), DUMP_SAMPLE).to(t.device)], key + "_sample"
+        arrays[key] = t.float()
+    norms, sample = [], []
+    with torch.no_grad():
+        for name, p in model.named_parameters():
+            flat = p.detach().reshape(-1)
+            norms.append(flat.double().norm())
+            k = min(DUMP_PARAM_SAMPLE, flat.numel())
+            sample.append(flat[_seeded_positions(name, flat.numel(), k).to(flat.device)].float())
+    arrays["param_norms"] = torch.stack(norms)
+    arrays["param_sample"] = torch.cat(sample)
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return {"dir": path, "arrays": len(arrays), "bytes": total}
+
+
 def time_forward(model, batch, B, device):
     """fwd ms/img: the fused-backbone forward (`infer`, B image-text pairs, no dropout, no autograd graph) on the batch that
     was just trained on; HIP events around 5 passes after 2 warm-ups."""
@@ -368,7 +416,13 @@ def main():
                          "all-reduce one tensor, print {n_gpus, rccl_ranks} and exit -- no model, no timing (tests/test_dp_gloo.py)")
     ap.add_argument("--task", choices=sorted(TASKS), default="mlm_itm",
                     help="default = BASELINE.json's metric; the others are extra configurations of the same path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB; see dump_outputs): the loss, the forward's outputs (seeded samples of the large ones) and the updated "
+                         "parameters (norms + seeded samples).  Same arguments = same inputs, so two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.batch <= 0:
         args.batch = {"mlm_itm": 256, "mlm_itm_itc": 96, "vqa": 160}[args.task]
 
@@ -455,9 +509,13 @@ def main():
         batch["vqa_labels"] = [torch.randperm(cfg["vqav2_label_size"], generator=gq)[:k].tolist() for k in ks]
         batch["vqa_scores"] = [[(0.3, 0.6, 0.9, 1.0)[int(torch.randint(0, 4, (1,), generator=gq))] for _ in range(k)] for k in ks]
 
+    kept = {}                                                # --dump-outputs: the forward's outputs of the last timed step
+
     def eager_step():
         ops.set_rng_step(model.global_step)
         out = net(batch)
+        if kept.get("want"):
+            kept["out"] = out
         loss = sum(v for k, v in out.items() if "loss" in k)
         loss.backward()
         opt.step()
@@ -492,12 +550,19 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
+        kept["want"] = args.dump_outputs is not None and i == args.steps - 1
         loss = step()
         marks[i + 1].record()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt_local = dt = time.perf_counter() - t0
+    kept["want"] = False
+    if args.dump_outputs is not None and rank == 0:          # before the extras below, which train the same model on
+        dumped = dump_outputs(args.dump_outputs, loss, kept.pop("out", {}), model)
+        print(f"[bench] --dump-outputs: {dumped['arrays']} arrays, {dumped['bytes'] / 2**20:.1f} MB -> {dumped['dir']}",
+              file=sys.stderr, flush=True)
+    kept.clear()
     per_rank_ms = [dt_local / args.steps * 1e3]
     if world > 1:
         t = torch.tensor([dt], device=device, dtype=torch.float64)

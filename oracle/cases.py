@@ -110,6 +110,13 @@ def roberta_layer_inputs(name, B=2, S=40, hidden=768):
     return h, ext, img, g
 
 
+def f64(*ts):
+    """float64 copies (None passes through).  The block / patch-merging / patch-embedding / RoBERTa-layer fixtures are computed
+    in float64 and the oracle is checked against them in float64: their bias and norm gradients are sums over thousands of rows,
+    whose fp32 result depends on the summation order (the CPU's vector width and thread count) by more than the tolerance."""
+    return tuple(None if t is None else t.double() for t in ts)
+
+
 def summarize(t, cap=4096):
     """Compact fingerprint of a tensor: strided sample + l2 norm + sum (keeps fixtures small)."""
     t = t.detach().float().cpu().reshape(-1)

@@ -41,8 +41,8 @@ def gen_blocks(sw):
         sw.DIM_TEXT = c["dim_text"] or 768
         blk = sw.SwinTransformerBlock(c["dim"], c["res"], c["heads"], window_size=c["ws"], shift_size=c["shift"],
                                       dim_text=c["dim_text"]).eval()
-        detgen.fill_(blk)
-        x, y, ext, g = cases.block_inputs(name)
+        detgen.fill_(blk).double()
+        x, y, ext, g = cases.f64(*cases.block_inputs(name))
         x.requires_grad_(True)
         if y is not None:
             y.requires_grad_(True)
@@ -57,10 +57,10 @@ def gen_blocks(sw):
 def gen_merge(sw):
     for name, c in cases.MERGE_CASES.items():
         m = sw.PatchMerging(c["res"], c["dim"]).eval()
-        detgen.fill_(m)
+        detgen.fill_(m).double()
         L = c["res"][0] * c["res"][1]
-        x = cases.randn(name + ".x", (c["B"], L, c["dim"])).requires_grad_(True)
-        g = cases.randn(name + ".g", (c["B"], L // 4, 2 * c["dim"]))
+        x, g = cases.f64(cases.randn(name + ".x", (c["B"], L, c["dim"])), cases.randn(name + ".g", (c["B"], L // 4, 2 * c["dim"])))
+        x.requires_grad_(True)
         out = m(x)
         (out * g).sum().backward()
         d = {}
@@ -73,10 +73,10 @@ def gen_patch_embed():
     from timm.models.layers import PatchEmbed
     for name, c in cases.EMBED_CASES.items():
         m = PatchEmbed(img_size=c["img"], patch_size=4, in_chans=3, embed_dim=c["dim"], norm_layer=nn.LayerNorm).eval()
-        detgen.fill_(m)
-        img = cases.randn(name + ".img", (c["B"], 3, c["img"], c["img"]))
+        detgen.fill_(m).double()
+        img, = cases.f64(cases.randn(name + ".img", (c["B"], 3, c["img"], c["img"])))
         out = m(img)
-        g = cases.randn(name + ".g", tuple(out.shape))
+        g, = cases.f64(cases.randn(name + ".g", tuple(out.shape)))
         (out * g).sum().backward()
         d = {}
         cases.flatten_summary("out", out, d)
@@ -106,8 +106,8 @@ def gen_roberta(rb):
 
     for name, c in cases.ROBERTA_LAYER_CASES.items():
         lyr = rb.RobertaLayer(cfg, layer_index=c["layer_index"]).eval()
-        detgen.fill_(lyr)
-        h, ext, img, g = cases.roberta_layer_inputs(name)
+        detgen.fill_(lyr).double()
+        h, ext, img, g = cases.f64(*cases.roberta_layer_inputs(name))
         h.requires_grad_(True)
         if img is not None:
             img.requires_grad_(True)

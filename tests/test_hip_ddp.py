@@ -192,3 +192,28 @@ def test_bench_counts_the_launches_of_a_step_in_a_child_process():
     assert "error" not in d, d
     assert 1000 < d["kernels"] + d["copy_or_fill_commands"] <= 1700, d
     assert d["of_which_fiber_hip"] > 0.8 * d["kernels"], d
+
+
+def test_bench_dumps_the_outputs_of_its_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: after the timed steps the loss, the forward's outputs (a seeded sample of the MLM logits) and the
+    updated parameters of the LAST timed step as float arrays, at most 64 MB; the line reports the timed steps it was asked for."""
+    import json
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    res = run_bounded([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+                       "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "out")], 240, cwd=root, env=env)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    got = {n[:-4]: np.load(tmp_path / "out" / n) for n in os.listdir(tmp_path / "out")}
+    for k in ("loss", "mlm_loss", "itm_loss", "mlm_logits_sample", "itm_logits", "itm_labels", "param_norms", "param_sample"):
+        assert k in got, (k, sorted(got))
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values()), sorted(got)
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["itm_logits"].shape == (8 * 2,) and got["mlm_logits_sample"].shape == (1 << 20,)
+    assert abs(got["loss"][0] - d["loss"]) < 1e-3 and abs(got["loss"][0] - got["mlm_loss"][0] - got["itm_loss"][0]) < 1e-3

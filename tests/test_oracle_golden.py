@@ -1,5 +1,6 @@
 """CPU: pin oracle/fiber_ref.py (the restatement) to the golden vectors produced by the REFERENCE
-modules (oracle/gen_golden.py).  fp32, tolerance 1e-5 relative."""
+modules (oracle/gen_golden.py).  fp32, tolerance 1e-5 relative; the block, patch-merging, patch-embedding and
+RoBERTa-layer cases in float64 on both sides, so that the result does not depend on the host's fp32 summation order (cases.f64)."""
 import numpy as np
 import pytest
 import torch
@@ -25,8 +26,8 @@ def _check_grads(module, gold, prefix="grad/"):
 def test_swin_block(name, golden):
     c, gold = cases.BLOCK_CASES[name], golden(name)
     blk = R.SwinTransformerBlock(c["dim"], c["res"], c["heads"], c["ws"], c["shift"], dim_text=c["dim_text"]).eval()
-    detgen.fill_(blk)
-    x, y, ext, g = cases.block_inputs(name)
+    detgen.fill_(blk).double()                         # float64 against the float64 fixture (cases.f64)
+    x, y, ext, g = cases.f64(*cases.block_inputs(name))
     x.requires_grad_(True)
     if y is not None:
         y.requires_grad_(True)
@@ -42,10 +43,10 @@ def test_swin_block(name, golden):
 @pytest.mark.parametrize("name", list(cases.MERGE_CASES))
 def test_patch_merging(name, golden):
     c, gold = cases.MERGE_CASES[name], golden(name)
-    m = detgen.fill_(R.PatchMerging(c["res"], c["dim"]).eval())
+    m = detgen.fill_(R.PatchMerging(c["res"], c["dim"]).eval()).double()       # float64 against the float64 fixture (cases.f64)
     L = c["res"][0] * c["res"][1]
-    x = cases.randn(name + ".x", (c["B"], L, c["dim"])).requires_grad_(True)
-    g = cases.randn(name + ".g", (c["B"], L // 4, 2 * c["dim"]))
+    x, g = cases.f64(cases.randn(name + ".x", (c["B"], L, c["dim"])), cases.randn(name + ".g", (c["B"], L // 4, 2 * c["dim"])))
+    x.requires_grad_(True)
     out = m(x)
     (out * g).sum().backward()
     cases.check_summary("out", out, gold, RT, AT)
@@ -56,10 +57,10 @@ def test_patch_merging(name, golden):
 @pytest.mark.parametrize("name", list(cases.EMBED_CASES))
 def test_patch_embed(name, golden):
     c, gold = cases.EMBED_CASES[name], golden(name)
-    m = detgen.fill_(R.PatchEmbed(c["img"], 4, 3, c["dim"]).eval())
-    img = cases.randn(name + ".img", (c["B"], 3, c["img"], c["img"]))
+    m = detgen.fill_(R.PatchEmbed(c["img"], 4, 3, c["dim"]).eval()).double()    # float64 against the float64 fixture (cases.f64)
+    img, = cases.f64(cases.randn(name + ".img", (c["B"], 3, c["img"], c["img"])))
     out = m(img)
-    g = cases.randn(name + ".g", tuple(out.shape))
+    g, = cases.f64(cases.randn(name + ".g", tuple(out.shape)))
     (out * g).sum().backward()
     cases.check_summary("out", out, gold, RT, AT)
     assert _check_grads(m, gold) == 4
@@ -85,8 +86,8 @@ def test_roberta_embeddings(golden):
 def test_roberta_layer(name, golden):
     c, gold = cases.ROBERTA_LAYER_CASES[name], golden(name)
     lyr = R.RobertaLayer(768, 12, 3072, 1e-5, 0.1, c["layer_index"], 6, 1024).eval()
-    detgen.fill_(lyr)
-    h, ext, img, g = cases.roberta_layer_inputs(name)
+    detgen.fill_(lyr).double()                         # float64 against the float64 fixture (cases.f64)
+    h, ext, img, g = cases.f64(*cases.roberta_layer_inputs(name))
     h.requires_grad_(True)
     if img is not None:
         img.requires_grad_(True)
