@@ -40,7 +40,8 @@ def make_config(**over):
     return c
 
 
-# Named task configs of the path built here (reference config.py:95-110 pre-training with / without ITC, :134-150 VQAv2).
+# Named task configs of the path built here (reference config.py:95-110 pre-training with / without ITC, :134-150 VQAv2,
+# :235-250 COCO caption fine-tuning).
 NAMED = {
     "task_pretrain_mlm_itm": dict(
         exp_name="mlm_itm", loss_names={"itm": 1, "mlm": 1}, draw_false_image=1, batch_size=4096, max_steps=100000,
@@ -53,6 +54,10 @@ NAMED = {
         exp_name="finetune_vqa", loss_names={"vqa": 1}, batch_size=512, max_epoch=10, max_steps=None, warmup_steps=0.1,
         learning_rate=2e-5, lr_mult_cross_modal=5, lr_mult_head=50, max_text_len=50, image_size=576,
         pretrained_vit=False, draw_false_image=0),
+    "task_finetune_caption_mle_coco": dict(                               # reference config.py:235-250
+        exp_name="finetune_caption_mle_coco", datasets=["coco"], loss_names={"caption_mle": 1}, batch_size=512, max_epoch=10,
+        max_steps=None, warmup_steps=0.1, learning_rate=5e-5, lr_mult_cross_modal=5, lr_mult_head=5, max_text_len=50,
+        train_transform_keys=["albef_randaug"], val_transform_keys=["albef"], image_size=576, pretrained_vit=False),
 }
 
 

@@ -190,7 +190,10 @@ __device__ __forceinline__ void fill_rowmeta(const AttnP& p, const Lds& L, int g
 
 
 // ===================================================== forward =================================================
-template <int D, bool WINDOW, int NT = NKT>       // NT: key (query) tiles held per chunk -- 3 for the 40-token text side
+// CAUSAL (text decoder self-attention, Lq == Lk, PLAIN mode): key j > query i is masked.  Key tiles wholly above a query strip's diagonal get
+// no LDS reads and no MFMAs; the diagonal tile masks per element.  Scores are floored at a finite value first, so that a padding mask of
+// finfo(fp32).min (-inf once scaled by log2 e) cannot turn a row's running max into -inf.
+template <int D, bool WINDOW, int NT = NKT, bool CAUSAL = false>   // NT: key (query) tiles held per chunk -- 3 for the 40-token text side
 __global__ __launch_bounds__(768) void attn_fwd_kernel(AttnP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int KS = D / 32, DT = D / 16;
@@ -256,7 +259,7 @@ __global__ __launch_bounds__(768) void attn_fwd_kernel(AttnP p) {
 #pragma unroll
     for (int kt = 0; kt < NT; ++kt) {
       s[kt] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-      if (kt < tpc) {
+      if (kt < tpc && !(CAUSAL && kbase / 16 + kt > strip)) {
         f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -271,6 +274,7 @@ __global__ __launch_bounds__(768) void attn_fwd_kernel(AttnP p) {
             v += L.btab[ioff - L.woff[jl]];
             if (L.reg[jl] != qreg) v += -144.26950408889634f;   // -100 * log2(e)
           }
+          if (CAUSAL) v = kbase + jl > i ? -INFINITY : fmaxf(v, -1e30f);
           s[kt][r] = v;
           cmax = fmaxf(cmax, v);
         }
@@ -300,7 +304,7 @@ __global__ __launch_bounds__(768) void attn_fwd_kernel(AttnP p) {
       for (int r = 0; r < 4; ++r) oacc[dt][r] *= alpha;
 #pragma unroll
     for (int t2 = 0; t2 < NT / 2; ++t2) {
-      if (t2 * 2 < tpc) {
+      if (t2 * 2 < tpc && !(CAUSAL && kbase / 16 + 2 * t2 > strip)) {
         const bf16x8 pf = pack8(s[2 * t2], s[2 * t2 + 1]);
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
@@ -347,7 +351,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16* __restrict_
 }
 
 // ===================================================== backward, pass A: dQ (+ dbias) ==========================
-template <int D, bool WINDOW, int NT = NKT>       // NT: key (query) tiles held per chunk -- 3 for the 40-token text side
+template <int D, bool WINDOW, int NT = NKT, bool CAUSAL = false>   // NT: key (query) tiles held per chunk -- 3 for the 40-token text side; CAUSAL: as attn_fwd_kernel
 // (WINDOW mode keeps its bias-gradient slice in registers, the 10-slot form 40 score registers per array: at most 8 waves per workgroup so
 //  that the allocator has 256 registers -- the 168 of a 12-wave bound left 24-260 bytes of scratch per lane)
 __global__ __launch_bounds__((WINDOW || NT > 6) ? 512 : 768) void attn_bwd_dq_kernel(AttnP p) {
@@ -422,13 +426,13 @@ __global__ __launch_bounds__((WINDOW || NT > 6) ? 512 : 768) void attn_bwd_dq_ke
       }
 #pragma unroll
       for (int t2 = 0; t2 < NT / 2; ++t2) {
-        if (t2 * 2 < tpc) {
+        if (t2 * 2 < tpc && !(CAUSAL && kbase / 16 + 2 * t2 > strip)) {
           f32x4 ds[2];
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
             const int kt = 2 * t2 + u;
             ds[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (kt < tpc) {
+            if (kt < tpc && !(CAUSAL && kbase / 16 + kt > strip)) {
               f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
               for (int ks = 0; ks < KS; ++ks) {
@@ -445,6 +449,7 @@ __global__ __launch_bounds__((WINDOW || NT > 6) ? 512 : 768) void attn_bwd_dq_ke
                   sv += L.btab[ioff - L.woff[jl]];
                   if (L.reg[jl] != qreg) sv += -144.26950408889634f;
                 }
+                if (CAUSAL) sv = kbase + jl > i ? -INFINITY : fmaxf(sv, -1e30f);
                 const float pr = __builtin_amdgcn_exp2f(sv - lse);
                 float dpe = dp[r];
                 if (p.p_drop > 0.f) {
@@ -506,7 +511,7 @@ __global__ __launch_bounds__((WINDOW || NT > 6) ? 512 : 768) void attn_bwd_dq_ke
 }
 
 // ===================================================== backward, pass B: dK, dV ================================
-template <int D, bool WINDOW, int NT = NKT>       // NT: key (query) tiles held per chunk -- 3 for the 40-token text side
+template <int D, bool WINDOW, int NT = NKT, bool CAUSAL = false>   // NT: key (query) tiles held per chunk -- 3 for the 40-token text side; CAUSAL: as attn_fwd_kernel
 // (the 10-slot form at D = 64 carries 8 more registers for the next strip's K / V: bounded at 8 waves so that it does not spill)
 __global__ __launch_bounds__((!WINDOW && NT > 6 && D == 64) ? 512 : 768) void attn_bwd_dkv_kernel(AttnP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -590,14 +595,14 @@ __global__ __launch_bounds__((!WINDOW && NT > 6 && D == 64) ? 512 : 768) void at
       if (!once) stage_chunk(qbase);
   #pragma unroll
       for (int t2 = 0; t2 < NT / 2; ++t2) {
-        if (t2 * 2 < tpc) {
+        if (t2 * 2 < tpc && !(CAUSAL && qbase / 16 + 2 * t2 + 1 < strip)) {   // (causal: query tiles wholly before the key strip see none of its keys)
           f32x4 ds[2], pd[2];
   #pragma unroll
           for (int u = 0; u < 2; ++u) {
             const int qt = 2 * t2 + u;
             ds[u] = f32x4{0.f, 0.f, 0.f, 0.f};
             pd[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (qt < tpc) {
+            if (qt < tpc && !(CAUSAL && qbase / 16 + qt < strip)) {
               f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
   #pragma unroll
               for (int ks = 0; ks < KS; ++ks) {
@@ -615,6 +620,7 @@ __global__ __launch_bounds__((!WINDOW && NT > 6 && D == 64) ? 512 : 768) void at
                   sv += L.btab[L.woff[il] - joff];
                   if (L.reg[il] != kreg) sv += -144.26950408889634f;
                 }
+                if (CAUSAL) sv = j > qbase + il ? -INFINITY : fmaxf(sv, -1e30f);
                 float pr = kvalid ? __builtin_amdgcn_exp2f(sv - L.addmask[il]) : 0.f;
                 float dpe = dp[r], prd = pr;
                 if (p.p_drop > 0.f) {
@@ -714,13 +720,14 @@ bool small_chunk(const AttnP& p, int staged_len) {
 }
 
 template <int D>
-int launch_fwd(AttnP& p, hipStream_t st) {
+int launch_fwd(AttnP& p, hipStream_t st, bool causal = false) {
   const int nstrips = cdiv(p.Lq, 16), nw = pick_waves(nstrips, p.Lk);
   const int nb = p.window ? (2 * p.ws - 1) * (2 * p.ws - 1) : 0;
   launch_geometry(p, p.Lk, nw, false);
   const size_t sh = lds_bytes<D>(nb, 2, p.chrows);
   const int gx = strip_blocks(p, p.Lk, nstrips, nw, p.H * p.G, true);
   if (p.window) hipLaunchKernelGGL((attn_fwd_kernel<D, true>), dim3(gx, p.H, p.G), dim3(64 * nw), sh, st, p);
+  else if (causal) hipLaunchKernelGGL((attn_fwd_kernel<D, false, 4, true>), dim3(gx, p.H, p.G), dim3(64 * nw), sh, st, p);   // (L <= 64: one 4-tile chunk)
   else if (small_chunk(p, p.Lk)) hipLaunchKernelGGL((attn_fwd_kernel<D, false, 4>), dim3(gx, p.H, p.G), dim3(64 * nw), sh, st, p);
   else hipLaunchKernelGGL((attn_fwd_kernel<D, false>), dim3(gx, p.H, p.G), dim3(64 * nw), sh, st, p);
   FIBER_CHECK_LAUNCH();
@@ -728,7 +735,7 @@ int launch_fwd(AttnP& p, hipStream_t st) {
 }
 
 template <int D>
-int launch_bwd(AttnP& p, float* delta, float* dbias_table, float* dbias_ws, int nz, hipStream_t st) {
+int launch_bwd(AttnP& p, float* delta, float* dbias_table, float* dbias_ws, int nz, hipStream_t st, bool causal = false) {
   const int rows_q = p.G * p.Lq;
   {
     const size_t total = (size_t)rows_q * p.H * (D / 8);
@@ -757,6 +764,7 @@ int launch_bwd(AttnP& p, float* delta, float* dbias_table, float* dbias_ws, int 
     launch_geometry(p, p.Lk, nw, true);
     const size_t sh = lds_bytes<D>(nb, 2, p.chrows);
     if (p.window) hipLaunchKernelGGL((attn_bwd_dq_kernel<D, true>), dim3(cdiv(nstrips, nw), p.H, gz), dim3(64 * nw), sh, st, p);
+    else if (causal) hipLaunchKernelGGL((attn_bwd_dq_kernel<D, false, 4, true>), dim3(strip_blocks(p, p.Lk, nstrips, nw, p.H * gz, false), p.H, gz), dim3(64 * nw), sh, st, p);
     else if (small_chunk(p, p.Lk)) hipLaunchKernelGGL((attn_bwd_dq_kernel<D, false, 4>), dim3(strip_blocks(p, p.Lk, nstrips, nw, p.H * gz, false), p.H, gz), dim3(64 * nw), sh, st, p);
     else if (chunk_tiles(p, p.Lk) <= 6) hipLaunchKernelGGL((attn_bwd_dq_kernel<D, false, 6>), dim3(strip_blocks(p, p.Lk, nstrips, nw, p.H * gz, false), p.H, gz), dim3(64 * nw), sh, st, p);   // (t2i: 5-tile chunks; the 10-slot form spills)
     else hipLaunchKernelGGL((attn_bwd_dq_kernel<D, false>), dim3(strip_blocks(p, p.Lk, nstrips, nw, p.H * gz, false), p.H, gz), dim3(64 * nw), sh, st, p);
@@ -778,6 +786,7 @@ int launch_bwd(AttnP& p, float* delta, float* dbias_table, float* dbias_ws, int 
     static const int once_env = getenv("FIBER_ATTN_DKV_ONCE") ? atoi(getenv("FIBER_ATTN_DKV_ONCE")) : 1;   // 0: one strip per wave (A/B runs)
     const int gx = once_env ? strip_blocks(p, p.Lq, nstrips, nw, p.H * p.G, false) : cdiv(nstrips, nw);
     if (p.window) hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, true>), dim3(cdiv(nstrips, nw), p.H, p.G), dim3(64 * nw), sh, st, p);
+    else if (causal) hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, false, 4, true>), dim3(gx, p.H, p.G), dim3(64 * nw), sh, st, p);
     else if (small_chunk(p, p.Lq)) hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, false, 4>), dim3(gx, p.H, p.G), dim3(64 * nw), sh, st, p);
     else hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, false>), dim3(gx, p.H, p.G), dim3(64 * nw), sh, st, p);
     FIBER_CHECK_LAUNCH();
@@ -820,9 +829,11 @@ int fiber_i2t_bwd_launch(const void* q, const void* k, const void* v, const floa
 // the same for head_dim 64 and at most 48 queries (text -> image cross attention, text self attention), dropout included
 int fiber_t2i_bwd_launch(const void* q, const void* k, const void* v, const float* kmask, const void* o, const void* dout, const float* lse,
                          void* dq, void* dk, void* dv, int B, int heads, int Lq, int Lk, int ldq, int ldk, int ldv, int ldo, int lddo,
-                         int lddq, int lddk, int lddv, float scale, float p_drop, uint64_t seed, const uint64_t* seed_base, hipStream_t st);
+                         int lddq, int lddk, int lddv, float scale, float p_drop, uint64_t seed, const uint64_t* seed_base, bool causal,
+                         hipStream_t st);
 int fiber_t2i_fwd_launch(const void* q, const void* k, const void* v, const float* kmask, void* o, float* lse, int B, int heads, int Lq, int Lk,
-                         int ldq, int ldk, int ldv, int ldo, float scale, float p_drop, uint64_t seed, const uint64_t* seed_base, hipStream_t st);
+                         int ldq, int ldk, int ldv, int ldo, float scale, float p_drop, uint64_t seed, const uint64_t* seed_base, bool causal,
+                         hipStream_t st);
 int fiber_i2t_fwd_launch(const void* q, const void* k, const void* v, const float* kmask, void* o, float* lse, int B, int heads, int Lq, int Lk,
                          int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t st);
 
@@ -895,7 +906,7 @@ extern "C" int fiber_mha_fwd_bf16(const void* q, const void* k, const void* v, c
     if (rc != FIBER_EINVAL) return rc;
   }
   if (onepass_t && D == 64 && Lq <= 48) {
-    const int rc = fiber_t2i_fwd_launch(q, k, v, kmask, o, lse, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, scale, p_drop, seed, seed_base, stream);
+    const int rc = fiber_t2i_fwd_launch(q, k, v, kmask, o, lse, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, scale, p_drop, seed, seed_base, false, stream);
     if (rc != FIBER_EINVAL) return rc;
   }
   ensure_attrs();
@@ -926,7 +937,7 @@ extern "C" int fiber_mha_bwd_bf16(const void* q, const void* k, const void* v, c
   static const int onepass_t = getenv("FIBER_ATTN_T2I_ONEPASS") ? atoi(getenv("FIBER_ATTN_T2I_ONEPASS")) : 1;
   if (onepass_t && D == 64 && Lq <= 48) {
     const int rc = fiber_t2i_bwd_launch(q, k, v, kmask, o, dout, lse, dq, dk, dv, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv,
-                                        scale, p_drop, seed, seed_base, stream);
+                                        scale, p_drop, seed, seed_base, false, stream);
     if (rc != FIBER_EINVAL) return rc;
   }
   ensure_attrs();
@@ -936,4 +947,46 @@ extern "C" int fiber_mha_bwd_bf16(const void* q, const void* k, const void* v, c
   p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
   p.H = heads; p.Lq = Lq; p.Lk = Lk; p.G = B; p.scale = scale; p.kmask = kmask; p.p_drop = p_drop; p.seed = seed; p.seed_base = seed_base;
   return D == 32 ? launch_bwd<32>(p, delta_ws, nullptr, nullptr, 1, stream) : launch_bwd<64>(p, delta_ws, nullptr, nullptr, 1, stream);
+}
+
+// Causal self-attention (text decoder, roberta.py _prepare_decoder_attention_mask): softmax(q.k^T*scale + kmask[b, j] + (j > i ? -inf : 0)).v.
+// Arguments as fiber_mha_fwd_bf16 / fiber_mha_bwd_bf16 with Lq == Lk = L, 1 <= L <= 64; kmask may be NULL (decoding) and may pad with -10000
+// or finfo(fp32).min.  head_dim 64 and L <= 48: the one-pass kernels of attn_x.hip; otherwise the generic kernels above in one 4-tile chunk.
+// Both skip the key tiles above each query strip's diagonal.  Attention dropout hashes (row, key) exactly as the non-causal kernels do.
+extern "C" int fiber_mha_causal_fwd_bf16(const void* q, const void* k, const void* v, const float* kmask, void* o, float* lse,
+                                         int B, int heads, int Lq, int Lk, int D, int ldq, int ldk, int ldv, int ldo,
+                                         float scale, float p_drop, uint64_t seed, const uint64_t* seed_base, hipStream_t stream) {
+  if ((D != 32 && D != 64) || Lq != Lk || Lq <= 0 || Lq > 64 || B <= 0 || heads <= 0 || (ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 7) ||
+      p_drop < 0.f || p_drop >= 1.f)
+    return FIBER_EINVAL;
+  if (D == 64 && Lq <= 48) {
+    const int rc = fiber_t2i_fwd_launch(q, k, v, kmask, o, lse, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, scale, p_drop, seed, seed_base, true, stream);
+    if (rc != FIBER_EINVAL) return rc;
+  }
+  AttnP p{};
+  p.q = (const bf16*)q; p.k = (const bf16*)k; p.v = (const bf16*)v; p.o = (bf16*)o; p.lse = lse;
+  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
+  p.H = heads; p.Lq = Lq; p.Lk = Lk; p.G = B; p.scale = scale; p.kmask = kmask; p.p_drop = p_drop; p.seed = seed; p.seed_base = seed_base;
+  return D == 32 ? launch_fwd<32>(p, stream, true) : launch_fwd<64>(p, stream, true);
+}
+
+extern "C" int fiber_mha_causal_bwd_bf16(const void* q, const void* k, const void* v, const float* kmask, const void* o,
+                                         const void* dout, const float* lse, void* dq, void* dk, void* dv, float* delta_ws,
+                                         int B, int heads, int Lq, int Lk, int D, int ldq, int ldk, int ldv, int ldo, int lddo,
+                                         int lddq, int lddk, int lddv, float scale, float p_drop, uint64_t seed,
+                                         const uint64_t* seed_base, hipStream_t stream) {
+  if ((D != 32 && D != 64) || Lq != Lk || Lq <= 0 || Lq > 64 || B <= 0 || heads <= 0 || (ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 7) ||
+      (lddo & 7) || (lddq & 7) || (lddk & 7) || (lddv & 7) || p_drop < 0.f || p_drop >= 1.f)
+    return FIBER_EINVAL;
+  if (D == 64 && Lq <= 48) {
+    const int rc = fiber_t2i_bwd_launch(q, k, v, kmask, o, dout, lse, dq, dk, dv, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv,
+                                        scale, p_drop, seed, seed_base, true, stream);
+    if (rc != FIBER_EINVAL) return rc;
+  }
+  AttnP p{};
+  p.q = (const bf16*)q; p.k = (const bf16*)k; p.v = (const bf16*)v; p.o = (bf16*)o; p.lse = (float*)lse;
+  p.dout = (const bf16*)dout; p.dq = (bf16*)dq; p.dk = (bf16*)dk; p.dv = (bf16*)dv;
+  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
+  p.H = heads; p.Lq = Lq; p.Lk = Lk; p.G = B; p.scale = scale; p.kmask = kmask; p.p_drop = p_drop; p.seed = seed; p.seed_base = seed_base;
+  return D == 32 ? launch_bwd<32>(p, delta_ws, nullptr, nullptr, 1, stream, true) : launch_bwd<64>(p, delta_ws, nullptr, nullptr, 1, stream, true);
 }

@@ -292,7 +292,10 @@ __device__ __forceinline__ T* atx(T* base, unsigned elem_off) {        // wave-u
   return reinterpret_cast<T*>(reinterpret_cast<C*>(base) + elem_off * (unsigned)sizeof(T));
 }
 
-template <bool DROP>
+// CAUSAL (text decoder self-attention, Lq == Lk): key j > query i is masked.  A wave's key tile kt only meets query tiles qt >= kt: the tiles
+// above the diagonal get no MFMA and no softmax work, the diagonal tile masks per element.  The padding mask is clamped to a finite floor so
+// that a row whose keys of one tile are all padding (finfo.min * log2 e overflows to -inf) cannot produce exp2(-inf + inf).
+template <bool DROP, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 2) void t2i_bwd_kernel(TP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16* Qs = reinterpret_cast<bf16*>(smem);
@@ -308,7 +311,8 @@ __global__ __launch_bounds__(256, 2) void t2i_bwd_kernel(TP p) {
   bf16* slabS = slabP + 3 * 256;
   float* mkl = reinterpret_cast<float*>(smem + T_FIX);
   for (int j = tid; j < ((p.Lk + 15) & ~15); j += 256)   // additive key mask in the log2 domain, -inf past Lk
-    mkl[j] = j < p.Lk ? (p.kmask ? p.kmask[(size_t)b * p.Lk + j] * 1.4426950408889634f : 0.f) : -INFINITY;
+    mkl[j] = j < p.Lk ? (p.kmask ? (CAUSAL ? fmaxf(p.kmask[(size_t)b * p.Lk + j] * 1.4426950408889634f, -1e30f)
+                                          : p.kmask[(size_t)b * p.Lk + j] * 1.4426950408889634f) : 0.f) : -INFINITY;
   // ---- Q, dO images (rows >= Lq zero), delta = rowsum(dO . O), lse in the log2 domain (+inf past Lq: p = 0 there)
   for (int idx = tid; idx < 48 * 8; idx += 256) {
     const int r = idx >> 3, c = idx & 7;
@@ -392,6 +396,7 @@ __global__ __launch_bounds__(256, 2) void t2i_bwd_kernel(TP p) {
     f32x4 st[3], dp[3];
 #pragma unroll
     for (int qt = 0; qt < 3; ++qt) {
+      if (CAUSAL && qt < kt) continue;                   // query tile wholly above the diagonal: nothing to compute
       st[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[0], qf[qt][0], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
       st[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[1], qf[qt][1], st[qt], 0, 0, 0);
       dp[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[0], dof[qt][0], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
@@ -404,8 +409,14 @@ __global__ __launch_bounds__(256, 2) void t2i_bwd_kernel(TP p) {
     s16x4 dsb[3];
 #pragma unroll
     for (int qt = 0; qt < 3; ++qt) {
+      if (CAUSAL && qt < kt) continue;
       const float nl = -lse2[qt];
-      const f32x4 pr = exp2x4(__builtin_elementwise_fma(st[qt], f32x4{c2, c2, c2, c2}, mk + nl));
+      f32x4 arg = __builtin_elementwise_fma(st[qt], f32x4{c2, c2, c2, c2}, mk + nl);
+      if (CAUSAL && qt == kt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) arg[r] = gq * 4 + r > lq ? -INFINITY : arg[r];   // key > query on the diagonal tile
+      }
+      const f32x4 pr = exp2x4(arg);
       f32x4 prd = pr, dpe = dp[qt];
       if constexpr (DROP) {
 #pragma unroll
@@ -425,18 +436,25 @@ __global__ __launch_bounds__(256, 2) void t2i_bwd_kernel(TP p) {
     for (int dt = 0; dt < 4; ++dt) {
       const s16x4 ktT = tr16s(Kt, TRS, dt * 16, gq, lq);
 #pragma unroll
-      for (int qt = 0; qt < 3; ++qt) dqT[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ktT, dsb[qt], dqT[dt][qt], 0, 0, 0);
+      for (int qt = 0; qt < 3; ++qt) {
+        if (CAUSAL && qt < kt) continue;
+        dqT[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ktT, dsb[qt], dqT[dt][qt], 0, 0, 0);
+      }
     }
     // dK^T[d][key] = sum_q Q^T[d][q] dS[q][key];  dV^T[d][key] = sum_q dO^T[d][q] P_dropped[q][key]
     s16x4 pB[3], dB[3];
 #pragma unroll
-    for (int qt = 0; qt < 3; ++qt) { pB[qt] = tr16s(slabP + qt * 256, 16, 0, gq, lq); dB[qt] = tr16s(slabS + qt * 256, 16, 0, gq, lq); }
+    for (int qt = 0; qt < 3; ++qt) {
+      if (CAUSAL && qt < kt) continue;
+      pB[qt] = tr16s(slabP + qt * 256, 16, 0, gq, lq); dB[qt] = tr16s(slabS + qt * 256, 16, 0, gq, lq);
+    }
     f32x4 dkT[4], dvT[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
       dkT[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dvT[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int qt = 0; qt < 3; ++qt) {
+        if (CAUSAL && qt < kt) continue;
         dkT[dt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(tr16s(Qs + qt * 16 * TRS, TRS, dt * 16, gq, lq), dB[qt], dkT[dt], 0, 0, 0);
         dvT[dt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(tr16s(dOs + qt * 16 * TRS, TRS, dt * 16, gq, lq), pB[qt], dvT[dt], 0, 0, 0);
       }
@@ -496,7 +514,7 @@ struct FP {
   float scale, p_drop; uint64_t seed; const uint64_t* seed_base;
 };
 
-template <bool DROP>
+template <bool DROP, bool CAUSAL = false>                // CAUSAL: as t2i_bwd_kernel
 __global__ __launch_bounds__(256, 3) void t2i_fwd_kernel(FP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* mkl = reinterpret_cast<float*>(smem);
@@ -506,7 +524,8 @@ __global__ __launch_bounds__(256, 3) void t2i_fwd_kernel(FP p) {
   const int b = blockIdx.x, h = blockIdx.y;
   bf16* Vt = reinterpret_cast<bf16*>(smem + T_MAXK * 4 + wave * T_KT);
   for (int j = tid; j < ((p.Lk + 15) & ~15); j += 256)   // additive key mask in the log2 domain, -inf past Lk
-    mkl[j] = j < p.Lk ? (p.kmask ? p.kmask[(size_t)b * p.Lk + j] * 1.4426950408889634f : 0.f) : -INFINITY;
+    mkl[j] = j < p.Lk ? (p.kmask ? (CAUSAL ? fmaxf(p.kmask[(size_t)b * p.Lk + j] * 1.4426950408889634f, -1e30f)
+                                          : p.kmask[(size_t)b * p.Lk + j] * 1.4426950408889634f) : 0.f) : -INFINITY;
   bf16x8 qf[3][2];
 #pragma unroll
   for (int qt = 0; qt < 3; ++qt) {
@@ -548,6 +567,7 @@ __global__ __launch_bounds__(256, 3) void t2i_fwd_kernel(FP p) {
     f32x4 st[3];
 #pragma unroll
     for (int qt = 0; qt < 3; ++qt) {
+      if (CAUSAL && qt < kt) continue;                   // query tile wholly above the diagonal
       st[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[0], qf[qt][0], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
       st[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[1], qf[qt][1], st[qt], 0, 0, 0);
     }
@@ -560,7 +580,12 @@ __global__ __launch_bounds__(256, 3) void t2i_fwd_kernel(FP p) {
     float alpha[3];
 #pragma unroll
     for (int qt = 0; qt < 3; ++qt) {
-      const f32x4 sv = __builtin_elementwise_fma(st[qt], f32x4{c2, c2, c2, c2}, mk);
+      if (CAUSAL && qt < kt) { alpha[qt] = 1.f; continue; }
+      f32x4 sv = __builtin_elementwise_fma(st[qt], f32x4{c2, c2, c2, c2}, mk);
+      if (CAUSAL && qt == kt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sv[r] = gq * 4 + r > lq ? -INFINITY : sv[r];     // key > query on the diagonal tile
+      }
       const float tmax = rows4_max(fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3])));
       const float mnew = fmaxf(m[qt], tmax);
       alpha[qt] = __builtin_amdgcn_exp2f(m[qt] - mnew);  // (first tile: exp2(-inf) = 0)
@@ -588,7 +613,10 @@ __global__ __launch_bounds__(256, 3) void t2i_fwd_kernel(FP p) {
     for (int dt = 0; dt < 4; ++dt) {
       const s16x4 vT = tr16s(Vt, TRS, dt * 16, gq, lq);
 #pragma unroll
-      for (int qt = 0; qt < 3; ++qt) oT[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(vT, pb[qt], oT[dt][qt], 0, 0, 0);
+      for (int qt = 0; qt < 3; ++qt) {
+        if (CAUSAL && qt < kt) continue;
+        oT[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(vT, pb[qt], oT[dt][qt], 0, 0, 0);
+      }
     }
   }
 #pragma unroll
@@ -765,15 +793,19 @@ int fiber_i2t_bwd_launch(const void* q, const void* k, const void* v, const floa
 // included; FIBER_EINVAL when the shape is not served.
 int fiber_t2i_bwd_launch(const void* q, const void* k, const void* v, const float* kmask, const void* o, const void* dout, const float* lse,
                          void* dq, void* dk, void* dv, int B, int heads, int Lq, int Lk, int ldq, int ldk, int ldv, int ldo, int lddo,
-                         int lddq, int lddk, int lddv, float scale, float p_drop, uint64_t seed, const uint64_t* seed_base, hipStream_t st) {
-  if (Lq > 48 || Lq <= 0 || Lk <= 0 || Lk > T_MAXK || (size_t)Lk * (size_t)(ldk | ldv | lddk | lddv) >= (1u << 30) || ((ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 7) || scale <= 0.f || p_drop < 0.f || p_drop >= 1.f)
+                         int lddq, int lddk, int lddv, float scale, float p_drop, uint64_t seed, const uint64_t* seed_base, bool causal,
+                         hipStream_t st) {
+  if ((causal && Lq != Lk) || Lq > 48 || Lq <= 0 || Lk <= 0 || Lk > T_MAXK || (size_t)Lk * (size_t)(ldk | ldv | lddk | lddv) >= (1u << 30) || ((ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 7) || scale <= 0.f || p_drop < 0.f || p_drop >= 1.f)
     return FIBER_EINVAL;
   TP p;
   p.q = (const bf16*)q; p.k = (const bf16*)k; p.v = (const bf16*)v; p.o = (const bf16*)o; p.dout = (const bf16*)dout;
   p.dq = (bf16*)dq; p.dk = (bf16*)dk; p.dv = (bf16*)dv; p.lse = lse; p.kmask = kmask;
   p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
   p.H = heads; p.Lq = Lq; p.Lk = Lk; p.scale = scale; p.p_drop = p_drop; p.seed = seed; p.seed_base = seed_base;
-  if (p_drop > 0.f) hipLaunchKernelGGL(t2i_bwd_kernel<true>, dim3(B, heads), dim3(256), T_SMEM, st, p);
+  if (causal) {
+    if (p_drop > 0.f) hipLaunchKernelGGL((t2i_bwd_kernel<true, true>), dim3(B, heads), dim3(256), T_SMEM, st, p);
+    else hipLaunchKernelGGL((t2i_bwd_kernel<false, true>), dim3(B, heads), dim3(256), T_SMEM, st, p);
+  } else if (p_drop > 0.f) hipLaunchKernelGGL(t2i_bwd_kernel<true>, dim3(B, heads), dim3(256), T_SMEM, st, p);
   else hipLaunchKernelGGL(t2i_bwd_kernel<false>, dim3(B, heads), dim3(256), T_SMEM, st, p);
   FIBER_CHECK_LAUNCH();
   return FIBER_OK;
@@ -781,15 +813,19 @@ int fiber_t2i_bwd_launch(const void* q, const void* k, const void* v, const floa
 
 // Forward for head_dim 64 and at most 48 queries (text -> image cross attention, text self attention); FIBER_EINVAL: shape not served.
 int fiber_t2i_fwd_launch(const void* q, const void* k, const void* v, const float* kmask, void* o, float* lse, int B, int heads, int Lq, int Lk,
-                         int ldq, int ldk, int ldv, int ldo, float scale, float p_drop, uint64_t seed, const uint64_t* seed_base, hipStream_t st) {
-  if (Lq > 48 || Lq <= 0 || Lk <= 0 || Lk > T_MAXK || (size_t)Lk * (size_t)(ldk | ldv) >= (1u << 30) || ((ldq | ldk | ldv | ldo) & 7) ||
+                         int ldq, int ldk, int ldv, int ldo, float scale, float p_drop, uint64_t seed, const uint64_t* seed_base, bool causal,
+                         hipStream_t st) {
+  if ((causal && Lq != Lk) || Lq > 48 || Lq <= 0 || Lk <= 0 || Lk > T_MAXK || (size_t)Lk * (size_t)(ldk | ldv) >= (1u << 30) || ((ldq | ldk | ldv | ldo) & 7) ||
       scale <= 0.f || p_drop < 0.f || p_drop >= 1.f)
     return FIBER_EINVAL;
   FP p;
   p.q = (const bf16*)q; p.k = (const bf16*)k; p.v = (const bf16*)v; p.o = (bf16*)o; p.lse = lse; p.kmask = kmask;
   p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
   p.H = heads; p.Lq = Lq; p.Lk = Lk; p.scale = scale; p.p_drop = p_drop; p.seed = seed; p.seed_base = seed_base;
-  if (p_drop > 0.f) hipLaunchKernelGGL(t2i_fwd_kernel<true>, dim3(B, heads), dim3(256), F_SMEM, st, p);
+  if (causal) {
+    if (p_drop > 0.f) hipLaunchKernelGGL((t2i_fwd_kernel<true, true>), dim3(B, heads), dim3(256), F_SMEM, st, p);
+    else hipLaunchKernelGGL((t2i_fwd_kernel<false, true>), dim3(B, heads), dim3(256), F_SMEM, st, p);
+  } else if (p_drop > 0.f) hipLaunchKernelGGL(t2i_fwd_kernel<true>, dim3(B, heads), dim3(256), F_SMEM, st, p);
   else hipLaunchKernelGGL(t2i_fwd_kernel<false>, dim3(B, heads), dim3(256), F_SMEM, st, p);
   FIBER_CHECK_LAUNCH();
   return FIBER_OK;

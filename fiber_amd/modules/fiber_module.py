@@ -3,8 +3,8 @@
 Mirrors coarse_grained/fiber/modules/fiber_module.py: constructor wiring (:27-179), infer() (:224-367, fused branch
 :310-367, image-only :279-308, text-only :247-277), forward() (:431-471), training_step (:473-478),
 configure_optimizers (:522).  Parameter names / shapes equal the reference's so a `fiber_pretrain.ckpt` state dict loads
-(`load_path`, ITC queue keys dropped as at :141-146).  Captioning / ITC-queue / NLVR2 code is out of scope (SURVEY.md
-section 2) and raises if requested.
+(`load_path`, ITC queue keys dropped as at :141-146).  Captioning: caption_mle training and beam-search decoding (infer_caption
+:369-429, on the causal attention kernels); caption_gold / caption_cider (host-side CIDEr scoring) and NLVR2 raise if requested.
 """
 import os
 import types
@@ -38,7 +38,7 @@ class FIBERTransformerSS(LightningModule):
         self.save_hyperparameters()
         self.config = config
         ln = config["loss_names"]
-        for k in ("caption_mle", "caption_gold", "caption_cider", "nlvr2"):
+        for k in ("caption_gold", "caption_cider", "nlvr2"):
             if ln.get(k, 0) > 0:
                 raise NotImplementedError(f"loss '{k}' is outside the fused-backbone hot path built here")
 
@@ -105,7 +105,8 @@ class FIBERTransformerSS(LightningModule):
             self.cross_modal_image_pooler_itc.apply(objectives.init_weights)
             self.cross_modal_text_pooler_itc.apply(objectives.init_weights)
 
-        if ln.get("mlm", 0) > 0:
+        caption = ln.get("caption_mle", 0) > 0
+        if ln.get("mlm", 0) > 0 or caption:                               # fiber_module.py:100-106
             self.mlm_score = heads.MLMHead(bert_config)
             self.mlm_score.apply(objectives.init_weights)
         if ln.get("itm", 0) > 0:
@@ -114,6 +115,13 @@ class FIBERTransformerSS(LightningModule):
             self.rank_output = nn.Linear(hs, 1)
             self.rank_output.weight.data = self.itm_score.fc.weight.data[1:, :]
             self.rank_output.bias.data = self.itm_score.fc.bias.data[1:]
+
+        if caption:                                                      # fiber_module.py:116-128: one per text layer but the top two;
+            self.cross_modal_att_layers = nn.ModuleList()                # only those of the fusion layers below the top two (6..9) run
+            for _ in range(self.num_text_layer - 2):
+                lt = nn.Linear(config["input_image_embed_size"], int(config["input_image_embed_size"] / 2))
+                lt.apply(objectives.init_weights)
+                self.cross_modal_att_layers.append(lt)
 
         if config["load_path"] != "" and not config.get("test_only", False):   # pre-trained -> downstream (:138-147)
             state_dict = self._read_checkpoint(config["load_path"])
@@ -161,6 +169,8 @@ class FIBERTransformerSS(LightningModule):
     # with ITC the image-only / text-only passes also exercise vit_model.norm, the *_itc transforms / poolers and layer 11's
     # output LayerNorm
     def unused_parameter_names(self):
+        if self.config["loss_names"].get("caption_mle", 0) > 0:
+            return self._unused_caption()
         itc = self.config["loss_names"].get("itc", 0) > 0
         names = []
         for n, _ in self.named_parameters():
@@ -184,6 +194,57 @@ class FIBERTransformerSS(LightningModule):
             if not hasattr(lyr, "crossattention_t2i") or f"text_transformer.encoder.layer.{i}.alpha_t2i" in names:
                 names.append(f"text_transformer.encoder.layer.{i}.alpha_t2i")
         return sorted(set(names))
+
+    def _unused_caption(self):
+        """infer_caption: the image stack runs alone (no i2t branch, no final norm), every text layer runs (6..9 against the
+        cross_modal_att_layers projections, also on Swin-T), and only text_feats reach the loss: the image-side transforms, every
+        pooler, the ITC transforms, cross_modal_att_layers of the non-fusion layers and alpha_t2i of the layers without
+        cross-attention get no gradient, nor does the cross-attention output LayerNorm (in the state dict, never applied)."""
+        first_fuse = self.num_text_layer - self.num_fuse_block
+        names = []
+        for n, _ in self.named_parameters():
+            if (n.startswith("vit_model.norm.") or (n.startswith("vit_model.") and "i2t" in n)
+                    or n.startswith("cross_modal_image_") or "pooler" in n or n.startswith("cross_modal_text_transform_itc.")
+                    or "crossattention_t2i.output.LayerNorm" in n or n.startswith("rank_output.")
+                    or (n.startswith("cross_modal_att_layers.") and int(n.split(".")[1]) < first_fuse)):
+                names.append(n)
+        for i, lyr in enumerate(self.text_transformer.encoder.layer):
+            if not hasattr(lyr, "crossattention_t2i"):
+                names.append(f"text_transformer.encoder.layer.{i}.alpha_t2i")
+        return sorted(set(names))
+
+    def infer_caption(self, batch, mask_text=False, mask_image=False, image_token_type_idx=1, img=None, text_only=False,
+                      image_only=False, image_embeds=None):
+        """fiber_module.py:369-429.  Image side: the whole Swin stack without text (patch merging included, no final norm), computed
+        once and handed back as image_embeds for decoding.  Text side: a causal decoder (_prepare_decoder_attention_mask -> the causal
+        attention kernels); layers 0..num_fuse-1 plain, the fusion layers below the top two cross-attend to their
+        cross_modal_att_layers projection of the image tokens (DIM_IMG / 2 wide), the top two to the image tokens; every layer
+        ends in its output LayerNorm."""
+        vit, txt = self.vit_model, self.text_transformer
+        if image_embeds is None:
+            if img is None:
+                imgkey = f"image_{image_token_type_idx - 1}" if f"image_{image_token_type_idx - 1}" in batch else "image"
+                img = batch[imgkey][0]
+            image_embeds = vit.patch_embed(img)              # (absolute_pos_embed is None and pos_drop the identity in every FIBER config)
+            for layer in vit.layers:
+                image_embeds = layer(image_embeds)
+        do_mlm = "_mlm" if mask_text else ""
+        text_ids, text_labels, text_masks = batch[f"text_ids{do_mlm}"], batch[f"text_labels{do_mlm}"], batch["text_masks"]
+        text_embeds = txt.embeddings(input_ids=text_ids)
+        ext = roberta._prepare_decoder_attention_mask(text_masks, text_ids.size(), text_embeds, text_embeds.device)
+        first_fuse = self.num_text_layer - self.num_fuse_block
+        for i, layer in enumerate(txt.encoder.layer):
+            if i < first_fuse:
+                text_embeds = layer(text_embeds, ext)[0]
+            elif i < self.num_text_layer - 2:
+                lt = self.cross_modal_att_layers[i]
+                text_embeds = layer(text_embeds, ext, encoder_hidden_states=ops.linear(image_embeds, lt.weight, lt.bias))[0]
+            else:
+                text_embeds = layer(text_embeds, ext, encoder_hidden_states=image_embeds)[0]
+        text_embeds = ops.linear(text_embeds, self.cross_modal_text_transform.weight, self.cross_modal_text_transform.bias)
+        cls_feats = self.cross_modal_text_pooler(text_embeds)
+        return {"text_feats": text_embeds, "image_embeds": image_embeds, "cls_feats": cls_feats, "text_labels": text_labels,
+                "text_ids": text_ids, "text_masks": text_masks, "image": img}
 
     def infer(self, batch, mask_text=False, mask_image=False, image_token_type_idx=1, img=None, text_only=False,
               image_only=False):
@@ -348,6 +409,8 @@ class FIBERTransformerSS(LightningModule):
                 ret.update(objectives.compute_itm(self, batch, batch.get("itm_labels_override")))
         if "vqa" in self.current_tasks:
             ret.update(objectives.compute_vqa(self, batch))
+        if "caption_mle" in self.current_tasks:
+            ret.update(objectives.compute_caption_mle(self, batch))
         return ret
 
     def training_step(self, batch, batch_idx):
@@ -367,12 +430,14 @@ class FIBERTransformerSS(LightningModule):
         fiber_utils.epoch_wrapup(self)
 
     def test_step(self, batch, batch_idx):
-        """fiber_module.py:490-507: forward, then the per-task test record (VQA answers; captioning is out of scope)."""
+        """fiber_module.py:490-507: forward, then the per-task test record (VQA answers, beam-searched captions)."""
         fiber_utils.set_task(self)
         output = self(batch)
         ret = dict()
         if self.hparams.config["loss_names"].get("vqa", 0) > 0:
             ret.update(objectives.vqa_test_step(self, batch, output))
+        if self.hparams.config["loss_names"].get("caption_mle", 0) > 0:
+            ret.update(objectives.caption_test_step(self, batch, output))
         return ret
 
     def test_epoch_end(self, outs):
@@ -380,6 +445,8 @@ class FIBERTransformerSS(LightningModule):
         model_name = self.hparams.config["load_path"].split("/")[-1][:-5]
         if self.hparams.config["loss_names"].get("vqa", 0) > 0:
             objectives.vqa_test_wrapup(outs, model_name)
+        if self.hparams.config["loss_names"].get("caption_mle", 0) > 0:
+            objectives.caption_test_wrapup(outs, model_name)
         fiber_utils.epoch_wrapup(self)
 
     def configure_optimizers(self):

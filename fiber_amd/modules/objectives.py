@@ -1,5 +1,6 @@
 """Loss functions on the metric path: compute_mlm / compute_itm / compute_itm_hardneg / compute_itc / compute_vqa /
-init_weights (reference coarse_grained/fiber/modules/objectives.py:17-213, 502-510).  Same call signatures and return keys."""
+compute_caption_mle + caption_test_step / caption_test_wrapup / init_weights (reference coarse_grained/fiber/modules/objectives.py:17-213,
+502-510, 560-710).  Same call signatures and return keys."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -277,6 +278,121 @@ def vqa_test_wrapup(outs, model_name, out_dir="result"):
                 merged += json.load(fp)
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, f"vqa_submit_{model_name}.json"), "w") as fp:
+            json.dump(merged, fp, indent=4)
+    if multi:
+        dist.barrier()
+    os.remove(shard)
+
+
+def compute_caption_mle(pl_module, batch):
+    """objectives.py:682-710: the MLM head over EVERY text position of the causal decoder, labels = the ids shifted left by one and
+    padded with pad_token_id, pad -> -100 (ignored); cross entropy through _mlm_head / _mlm_ce like compute_mlm."""
+    tok = pl_module.trainer.datamodule.dms[0].tokenizer
+    infer = pl_module.infer_caption(batch, mask_text=False, mask_image=False)
+    ids = infer["text_ids"]
+    labels = torch.cat([ids[:, 1:], torch.full_like(ids[:, :1], tok.pad_token_id)], 1)
+    labels = labels.masked_fill(labels == tok.pad_token_id, -100)
+    loss, logits, labels = _mlm_head(pl_module, infer["text_feats"], labels)
+    ret = {"caption_mle_loss": loss, "caption_mle_logits": logits, "caption_mle_labels": labels, "caption_mle_ids": ids}
+    phase = "train" if pl_module.training else "val"
+    loss = getattr(pl_module, f"{phase}_caption_mle_loss")(ret["caption_mle_loss"])
+    acc = getattr(pl_module, f"{phase}_caption_mle_accuracy")(ret["caption_mle_logits"], ret["caption_mle_labels"])
+    pl_module.log(f"caption_mle/{phase}/loss", loss)
+    pl_module.log(f"caption_mle/{phase}/accuracy", acc)
+    return ret
+
+
+@torch.no_grad()
+def caption_test_step(pl_module, batch, output, beam_size=5):
+    """objectives.py:560-645: beam search over max_text_len - 1 steps.  The image tokens are computed once (the first infer_caption,
+    on the batch's own text) and repeated per beam; every step re-runs the whole causal text stack on the current ids
+    (text_masks None) and scores one position, the [MASK] logit forced to -10000; candidates are ranked by length-normalised
+    log-probability, and the search stops early once every beam has ended.  Returns the captions (tokenizer.decode of beam 0, sep /
+    cls -> pad, pad removed) and, not in the reference, the ids beam 0 generated (sep kept, padding after it) under `caption_ids`
+    ([B, max_text_len - 1])."""
+    captions = []
+    if pl_module.training:
+        return {"image_ids": batch["iid"], "captions": captions, "caption_ids": None}
+    tok = pl_module.trainer.datamodule.dms[0].tokenizer
+    max_len = pl_module.hparams.config["max_text_len"]
+    batch = dict(batch)                                   # (the reference overwrites text_ids / text_masks in the caller's batch)
+    bs, dev = batch["text_ids"].size(0), batch["text_ids"].device
+    text_ids = torch.full((bs, max_len), tok.pad_token_id, device=dev, dtype=batch["text_ids"].dtype)
+    text_ids[:, 0] = tok.cls_token_id
+    search = bs * beam_size
+    end_seq = torch.zeros(bs, dtype=torch.bool, device=dev)
+    first = pl_module.infer_caption(batch, mask_text=False, mask_image=False)
+    image_embeds = first["image_embeds"]
+    batch["text_masks"] = None
+    for i in range(max_len - 1):
+        batch["text_ids"] = text_ids
+        infer = first if i == 0 else pl_module.infer_caption(batch, mask_text=False, mask_image=False, image_embeds=image_embeds)
+        logits = pl_module.mlm_score(infer["text_feats"][:, i:i + 1]).float()
+        logits[:, 0, tok.mask_token_id] = -10000
+        logp = torch.log_softmax(logits, dim=-1)                                  # [N, 1, V]
+        if i == 0:
+            top = logp.argsort(descending=True, dim=-1)[:, :, :beam_size]         # [bs, 1, beam]
+            head_logp = logp.gather(-1, top).view(search, 1)
+            tgt = top.permute(0, 2, 1).reshape(search, 1)
+            head_lengths = torch.ones_like(head_logp)
+            text_ids = text_ids.view(bs, 1, -1).repeat(1, beam_size, 1).view(search, -1)
+            padded = torch.full((search, 1), tok.pad_token_id, dtype=torch.long, device=dev)
+            hs = image_embeds.size(-1)
+            image_embeds = image_embeds.view(bs, 1, -1, hs).repeat(1, beam_size, 1, 1).view(search, -1, hs)
+        else:
+            lengths = 1.0 - end_seq.to(logp.dtype)                                # ended beams add nothing
+            logp = (logp * lengths[:, :, None] + head_logp[:, :, None]).view(bs, beam_size, 1, -1).permute(0, 2, 1, 3)
+            V = logp.size(3)
+            lengths = (lengths + head_lengths).view(bs, beam_size, 1).permute(0, 2, 1)
+            normed = (logp / (lengths[:, :, :, None] + 1e-9)).contiguous().view(bs, 1, -1)
+            top_idx = normed.argsort(descending=True, dim=-1)[:, :, :beam_size]
+            top_logp = logp.contiguous().view(bs, 1, -1).gather(-1, top_idx)
+            top_tokens = (top_idx % V).permute(0, 2, 1).contiguous().view(search, 1)
+            top_prev = top_idx // V + torch.arange(bs, dtype=torch.long, device=dev)[:, None, None] * beam_size
+            top_prev = top_prev.permute(0, 2, 1).contiguous().view(search, 1)
+            head_logp = top_logp.permute(0, 2, 1).contiguous().view(search, 1)
+            head_lengths = lengths.permute(0, 2, 1).contiguous().view(search, 1)  # (per beam slot, not gathered: as the reference)
+            prev_ended = end_seq.gather(0, top_prev).to(torch.long)
+            tgt = (1 - prev_ended) * top_tokens + prev_ended * padded
+            text_ids = text_ids.gather(0, top_prev.repeat(1, text_ids.size(1)))
+        text_ids[:, i + 1] = tgt.view(-1)
+        end_seq = (tgt == tok.sep_token_id) | (tgt == tok.pad_token_id)
+        if i > 0 and bool(end_seq.all()):
+            break
+    gen = text_ids.view(bs, beam_size, -1)[:, 0, 1:].contiguous()
+    ids = gen.clone()
+    ids[ids == tok.sep_token_id] = tok.pad_token_id
+    ids[ids == tok.cls_token_id] = tok.pad_token_id
+    for t in ids:
+        captions.append(tok.decode(t.tolist()).replace(tok.pad_token, ""))
+    return {"image_ids": batch["iid"], "captions": captions, "caption_ids": gen}
+
+
+def caption_test_wrapup(outs, model_name, out_dir="result"):
+    """objectives.py:647-680: every rank writes its (image_id, caption) shard, rank 0 merges the shards (first caption per image id)
+    into result/caption.json."""
+    import glob
+    import json
+    import os
+    import torch.distributed as dist
+    multi = dist.is_available() and dist.is_initialized()
+    rank = dist.get_rank() if multi else 0
+    records = [{"image_id": iid, "caption": c} for out in outs for iid, c in zip(out["image_ids"], out["captions"])]
+    shard = f"caption_{rank}.json"
+    with open(shard, "w") as fp:
+        json.dump(records, fp, indent=4)
+    if multi:
+        dist.barrier()
+    if rank == 0:
+        merged, seen = [], set()
+        for path in glob.glob("caption_*.json"):
+            with open(path) as fp:
+                for x in json.load(fp):
+                    if x["image_id"] not in seen:
+                        merged.append(x)
+                        seen.add(x["image_id"])
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "caption.json"), "w") as fp:
             json.dump(merged, fp, indent=4)
     if multi:
         dist.barrier()

@@ -26,6 +26,28 @@ def roberta_base_config(**over):
     return types.SimpleNamespace(**cfg)
 
 
+class DecoderMask:
+    """What _prepare_decoder_attention_mask hands the text layers: the additive [B, L] padding mask (finfo(fp32).min on padding,
+    or None) plus causal=True.  RobertaSelfAttention routes it to the causal attention kernels, which add the (j > i ? -inf : 0)
+    term themselves -- the [B, 1, L, L] tensor of roberta.py:891-938 is never built."""
+
+    causal = True
+
+    def __init__(self, kmask):
+        self.kmask = kmask
+
+
+def _prepare_decoder_attention_mask(attention_mask, input_shape, inputs_embeds, device, past_key_values_length=0):
+    """roberta.py:920-938: causal mask, plus the padding of `attention_mask` ([B, L] of 0 / 1) as finfo.min, or causal only when
+    attention_mask is None."""
+    if past_key_values_length:
+        raise NotImplementedError("cached decoding (past_key_values_length > 0) is not built")
+    if attention_mask is None:
+        return DecoderMask(None)
+    m = attention_mask.to(device)
+    return DecoderMask(torch.zeros(m.shape, dtype=torch.float32, device=device).masked_fill(m == 0, torch.finfo(torch.float32).min))
+
+
 class RobertaEmbeddings(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -66,10 +88,12 @@ class RobertaSelfAttention(nn.Module):
         p = self.dropout.p if self.training else 0.0
         seed = ops.next_seed() if p > 0 else 0
         if encoder_hidden_states is None:
+            causal = isinstance(attention_mask, DecoderMask)
+            kmask = attention_mask.kmask if causal else attention_mask
             # q, k, v of one input as ONE GEMM (three nn.Linear modules in the state dict, roberta.py:231-241)
             qkv = ops.linear_packed(hidden_states, [(self.query.weight, self.query.bias), (self.key.weight, self.key.bias),
                                                     (self.value.weight, self.value.bias)])
-            o = ops.mha_qkv_packed(qkv.view(B * S, 3 * C), attention_mask, B, self.num_attention_heads, scale, p, seed)
+            o = ops.mha_qkv_packed(qkv.view(B * S, 3 * C), kmask, B, self.num_attention_heads, scale, p, seed, causal=causal)
         else:
             # t2i: keys / values from the image tokens as one GEMM; roberta.py:276: the cross-attention mask is None
             q = ops.linear(hidden_states, self.query.weight, self.query.bias).view(B * S, C)

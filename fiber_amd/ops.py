@@ -1397,7 +1397,7 @@ class _MHAPacked(torch.autograd.Function):
     backward is one dgrad + one wgrad and autograd never assembles slices."""
 
     @staticmethod
-    def forward(ctx, a, b, kmask, mode, B, heads, scale, p_drop, seed):
+    def forward(ctx, a, b, kmask, mode, B, heads, scale, p_drop, seed, causal=False):
         a = _c(a)
         b = _c(b) if b is not None else None
         if mode == 0:
@@ -1411,16 +1411,16 @@ class _MHAPacked(torch.autograd.Function):
         o = torch.empty((q.shape[0], C), dtype=BF16, device=a.device)
         lse = torch.empty((q.shape[0], heads), dtype=torch.float32, device=a.device)
         base = seed_base_ptr()
-        lib.call("fiber_mha_fwd_bf16", lib.ptr(q), lib.ptr(k), lib.ptr(v), lib.ptr(kmask), lib.ptr(o), lib.ptr(lse), B, heads, Lq, Lk, D,
-                 _ld(q), _ld(k), _ld(v), _ld(o), scale, p_drop, seed, base)
+        lib.call("fiber_mha_causal_fwd_bf16" if causal else "fiber_mha_fwd_bf16", lib.ptr(q), lib.ptr(k), lib.ptr(v), lib.ptr(kmask),
+                 lib.ptr(o), lib.ptr(lse), B, heads, Lq, Lk, D, _ld(q), _ld(k), _ld(v), _ld(o), scale, p_drop, seed, base)
         ctx.save_for_backward(a, b, kmask, o, lse)
-        ctx.cfg = (mode, B, heads, Lq, Lk, D, C, scale, p_drop, seed, base)
+        ctx.cfg = (mode, B, heads, Lq, Lk, D, C, scale, p_drop, seed, base, causal)
         return o
 
     @staticmethod
     def backward(ctx, do):
         a, b, kmask, o, lse = ctx.saved_tensors
-        mode, B, heads, Lq, Lk, D, C, scale, p_drop, seed, base = ctx.cfg
+        mode, B, heads, Lq, Lk, D, C, scale, p_drop, seed, base, causal = ctx.cfg
         do = _c(do)
         da = torch.empty_like(a)
         db = torch.empty_like(b) if b is not None else None
@@ -1431,17 +1431,20 @@ class _MHAPacked(torch.autograd.Function):
             q, k, v = a, b[:, :C], b[:, C:]
             dq, dk, dv = da, db[:, :C], db[:, C:]
         delta = torch.empty((q.shape[0], heads), dtype=torch.float32, device=a.device)
-        lib.call("fiber_mha_bwd_bf16", lib.ptr(q), lib.ptr(k), lib.ptr(v), lib.ptr(kmask), lib.ptr(o), lib.ptr(do), lib.ptr(lse),
-                 lib.ptr(dq), lib.ptr(dk), lib.ptr(dv), lib.ptr(delta), B, heads, Lq, Lk, D, _ld(q), _ld(k), _ld(v), _ld(o), _ld(do),
-                 _ld(dq), _ld(dk), _ld(dv), scale, p_drop, seed, base)
-        return da, db, None, None, None, None, None, None, None
+        lib.call("fiber_mha_causal_bwd_bf16" if causal else "fiber_mha_bwd_bf16", lib.ptr(q), lib.ptr(k), lib.ptr(v), lib.ptr(kmask),
+                 lib.ptr(o), lib.ptr(do), lib.ptr(lse), lib.ptr(dq), lib.ptr(dk), lib.ptr(dv), lib.ptr(delta), B, heads, Lq, Lk, D,
+                 _ld(q), _ld(k), _ld(v), _ld(o), _ld(do), _ld(dq), _ld(dk), _ld(dv), scale, p_drop, seed, base)
+        return da, db, None, None, None, None, None, None, None, None
 
 
-def mha_qkv_packed(qkv, kmask, B, heads, scale, p_drop=0.0, seed=0):
-    """Self-attention on a packed projection qkv [B*L, 3*heads*D] = [q | k | v] (linear_packed)."""
+def mha_qkv_packed(qkv, kmask, B, heads, scale, p_drop=0.0, seed=0, causal=False):
+    """Self-attention on a packed projection qkv [B*L, 3*heads*D] = [q | k | v] (linear_packed).  causal=True: key j > query i is
+    masked as well (text decoder; L <= 64, kmask [B, L] additive or None)."""
+    if kmask is not None and kmask.numel() != qkv.shape[0]:     # e.g. a dense [B, 1, L, L] mask, which view(B, -1) would misread
+        raise ValueError(f"mha_qkv_packed: kmask must be an additive [B, L] key mask, got shape {tuple(kmask.shape)}")
     if kmask is not None:
         kmask = _c(kmask.view(B, -1).float())
-    return _MHAPacked.apply(qkv, None, kmask, 0, B, heads, float(scale), float(p_drop), int(seed))
+    return _MHAPacked.apply(qkv, None, kmask, 0, B, heads, float(scale), float(p_drop), int(seed), bool(causal))
 
 
 def mha_kv_packed(q, kv, kmask, B, heads, scale, p_drop=0.0, seed=0):

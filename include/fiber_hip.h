@@ -138,6 +138,16 @@ int fiber_mha_bwd_bf16(const void* q, const void* k, const void* v, const float*
                        const float* lse, void* dq, void* dk, void* dv, float* delta_ws, int B, int heads, int Lq, int Lk, int D,
                        int ldq, int ldk, int ldv, int ldo, int lddo, int lddq, int lddk, int lddv, float scale, float p_drop,
                        uint64_t seed, const uint64_t* seed_base, fiber_stream_t stream);
+/* Causal self-attention (text decoder): softmax(q.k^T*scale + kmask[b, j] + (j > i ? -inf : 0)).v.  Arguments as the two above
+ * with Lq == Lk = L, 1 <= L <= 64, D in {32,64}; kmask [B, L] additive (-10000 or finfo(fp32).min padding) or NULL.  Key tiles
+ * above a query strip's diagonal are skipped.  Dropout keys (row, key) exactly as the non-causal entry points. */
+int fiber_mha_causal_fwd_bf16(const void* q, const void* k, const void* v, const float* kmask, void* o, float* lse, int B,
+                              int heads, int Lq, int Lk, int D, int ldq, int ldk, int ldv, int ldo, float scale, float p_drop,
+                              uint64_t seed, const uint64_t* seed_base, fiber_stream_t stream);
+int fiber_mha_causal_bwd_bf16(const void* q, const void* k, const void* v, const float* kmask, const void* o, const void* dout,
+                              const float* lse, void* dq, void* dk, void* dv, float* delta_ws, int B, int heads, int Lq, int Lk,
+                              int D, int ldq, int ldk, int ldv, int ldo, int lddo, int lddq, int lddk, int lddv, float scale,
+                              float p_drop, uint64_t seed, const uint64_t* seed_base, fiber_stream_t stream);
 
 /* RobertaEmbeddings.forward (roberta.py:169-199, 877-888) and its backward (scatter-add into fp32 gradient tables) */
 int fiber_roberta_embed_fwd(const int64_t* ids, const float* word, const float* pos_tab, const float* type_tab,
