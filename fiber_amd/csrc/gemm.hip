@@ -1160,16 +1160,46 @@ extern "C" void fiber_p2_probe(GemmArgs a, hipStream_t st) {
 }
 #else
 // C ABI ---------------------------------------------------------------------------------------------------------
-// Row-tile height the dispatcher will use for an [M,N,K] problem (rows of `colpart` = ceil(M / tile)).
-extern "C" int fiber_gemm_row_tile(int M, int N, int K) {
-  const long big = (long)cdiv(M, 128) * cdiv(N, 128), huge = (long)cdiv(M, 256) * cdiv(N, 128);
+// Shape decision of the dispatcher, shared with fiber_gemm_row_tile (which sizes the caller's `colpart`: the two must not disagree).
+//   shape: 0 wide (256x256), 1 256x128, 2 128x128, 3 64x64, 4/5 register-staged 128x128 / 64x64;  -1: rejected
+// Tile choice.  256x256 (K step 32, two wave groups half a tile apart) whenever N is a multiple of 256 and there are
+// enough tiles; otherwise 256x128 / 128x128 / 64x64 on the 64-deep ring.  FIBER_GEMM_TILE / FIBER_GEMM_NOWIDE force a
+// choice for A/B runs (tools/gemm_ab.py).
+struct GemmPlan { int shape; bool persist; int persist_env, q8_env; };
+static GemmPlan gemm_plan(int M, int N, int K, int ldy, int ldr, bool has_r, bool has_rs, bool colpart, int act) {
   static const int force = getenv("FIBER_GEMM_TILE") ? atoi(getenv("FIBER_GEMM_TILE")) : 0;
   static const int nowide = getenv("FIBER_GEMM_NOWIDE") ? atoi(getenv("FIBER_GEMM_NOWIDE")) : 0;
+  static const int persist_env = getenv("FIBER_GEMM_PERSIST") ? atoi(getenv("FIBER_GEMM_PERSIST")) : 1;
+  static const int persist_min = getenv("FIBER_GEMM_PERSIST_MIN") ? atoi(getenv("FIBER_GEMM_PERSIST_MIN")) : 200;
+  static const int q8_env = getenv("FIBER_GEMM_Q8") ? atoi(getenv("FIBER_GEMM_Q8")) : 1;   // 0: the v4 K loop (A/B runs)
+  const long big = (long)cdiv(M, 128) * cdiv(N, 128);
+  const long huge = (long)cdiv(M, 256) * cdiv(N, 128);
   const long wide = (long)cdiv(M, 256) * cdiv(N, 256);
-  if (!nowide && force == 0 && wide >= 200 && N % 256 == 0 && K >= 128 && K % 64 == 0) return 256;
-  if ((huge >= 400 && K >= 256 && force == 0) || force == 256) return 256;
-  if (big >= 192 || force == 128) return 128;
-  return 64;
+  const int mode = act & 0xff;
+  const bool v2 = (K % 64 == 0) && (N % 8 == 0) && (ldy % 8 == 0) && (!has_r || ldr % 8 == 0) && !getenv("FIBER_GEMM_V1");
+  // will FIBER_LAUNCH_EPI pick gemm_nt_q8_kernel for this call?  (run-time mirror of kV4Ok and of the colpart exclusion)
+  const bool v4ok = (act & 0x800) ? has_rs : mode == 0 ? (!has_r || has_rs) : mode == 1 ? !has_r : mode == 2;
+  const bool q8_serves = persist_env == 1 && q8_env && wide >= persist_min && v4ok && !(mode == 2 && colpart) && !(act & 0x1600);
+  // (q8 wins from one tile per CU on: 240 tiles 31.5 -> 28.1 us, 97.5 -> 85.1 us at K = 3072)
+  GemmPlan p{-1, persist_env != 0 && wide >= persist_min, persist_env, q8_env};
+  if (act & 0x100) {                                      // fp32 output: the register-staged kernels only
+    if (mode != 0 || has_r || colpart) return p;
+    p.shape = big >= 192 ? 4 : 5;
+  } else if (v2 && !nowide && force == 0 && wide >= 200 && K >= 128 && !(mode == 2 && !q8_serves) &&
+             (N % 256 == 0 || (N % 64 == 0 && N > 256 && q8_serves))) p.shape = 0;   // (only the q8 kernel masks a partial tile column; gelu' * aux
+                                                                                        //  with column sums / without q8: the 256x128 ring kernel)
+  else if (v2 && ((huge >= 400 && K >= 256 && force == 0) || force == 256)) p.shape = 1;
+  else if (big >= 192 || force == 128) p.shape = v2 ? 2 : 4;
+  else p.shape = v2 ? 3 : 5;
+  return p;
+}
+
+// Row-tile height of the fused gelu' * aux column-sum call (act 2 with `colpart`, ldy = N) for an [M,N,K] problem: the rows of
+// `colpart` = ceil(M / tile).  0: the dispatcher rejects that call.
+extern "C" int fiber_gemm_row_tile(int M, int N, int K) {
+  static const int rows[6] = {256, 256, 128, 64, 128, 64};
+  const GemmPlan p = gemm_plan(M, N, K, N, 0, false, false, true, 2);
+  return p.shape < 0 ? 0 : rows[p.shape];
 }
 
 // Y = rowscale * act(X.W^T + bias) + residual.  bias: fp32[N] or NULL; residual: bf16[M,ldr] or NULL; act: 0 none, 1 exact GELU;
@@ -1201,31 +1231,12 @@ extern "C" int fiber_gemm_nt_bf16(const void* X, const void* W, const float* bia
   if (mode == 2 && residual) return FIBER_EINVAL;
   if ((act & 0x800) && (mode != 0 || !residual || !Ypre || colpart || (act & 0x100))) return FIBER_EINVAL;
   if (colpart && mode != 2 && !(act & 0x1600)) return FIBER_EINVAL;
-  const bool v2 = (K % 64 == 0) && (N % 8 == 0) && (ldy % 8 == 0) && (!residual || ldr % 8 == 0) && !getenv("FIBER_GEMM_V1");
-  // Tile choice.  256x256 (K step 32, two wave groups half a tile apart) whenever N is a multiple of 256 and there are
-  // enough tiles; otherwise 256x128 / 128x128 / 64x64 on the 64-deep ring.  FIBER_GEMM_TILE / FIBER_GEMM_NOWIDE force a
-  // choice for A/B runs (tools/gemm_ab.py).
-  static const int force = getenv("FIBER_GEMM_TILE") ? atoi(getenv("FIBER_GEMM_TILE")) : 0;
-  static const int nowide = getenv("FIBER_GEMM_NOWIDE") ? atoi(getenv("FIBER_GEMM_NOWIDE")) : 0;
-  static const int persist_env = getenv("FIBER_GEMM_PERSIST") ? atoi(getenv("FIBER_GEMM_PERSIST")) : 1;
-  static const int persist_min = getenv("FIBER_GEMM_PERSIST_MIN") ? atoi(getenv("FIBER_GEMM_PERSIST_MIN")) : 200;
-  static const int q8_env = getenv("FIBER_GEMM_Q8") ? atoi(getenv("FIBER_GEMM_Q8")) : 1;   // 0: the v4 K loop (A/B runs)
-  // will FIBER_LAUNCH_EPI below pick gemm_nt_q8_kernel for this call?  (run-time mirror of kV4Ok and of the colpart exclusion)
-  const bool has_r = residual != nullptr, has_rs = rowscale != nullptr;
-  const bool v4ok = (act & 0x800) ? has_rs : mode == 0 ? (!has_r || has_rs) : mode == 1 ? !has_r : mode == 2;
-  const bool q8_serves = persist_env == 1 && q8_env && wide >= persist_min && v4ok && !(mode == 2 && colpart) && !(act & 0x1600);
-  int shape;                                             // 0 wide, 1 256x128, 2 128x128, 3 64x64, 4/5 register-staged
-  if (act & 0x100) {                                      // fp32 output: the register-staged kernels only
-    if (mode != 0 || residual || colpart) return FIBER_EINVAL;
-    shape = big >= 192 ? 4 : 5;
-  } else if (v2 && !nowide && force == 0 && wide >= 200 && K >= 128 && !(mode == 2 && !q8_serves) &&
-             (N % 256 == 0 || (N % 64 == 0 && N > 256 && q8_serves))) shape = 0;   // (only the q8 kernel masks a partial tile column; gelu' * aux
-                                                                                    //  with column sums / without q8: the 256x128 ring kernel)
-  else if (v2 && ((huge >= 400 && K >= 256 && force == 0) || force == 256)) shape = 1;
-  else if (big >= 192 || force == 128) shape = v2 ? 2 : 4;
-  else shape = v2 ? 3 : 5;
+  const GemmPlan plan = gemm_plan(M, N, K, ldy, ldr, residual != nullptr, rowscale != nullptr, colpart != nullptr, act);
+  if (plan.shape < 0) return FIBER_EINVAL;
+  const int shape = plan.shape;                          // 0 wide, 1 256x128, 2 128x128, 3 64x64, 4/5 register-staged
+  const bool persist = plan.persist;
+  const int persist_env = plan.persist_env, q8_env = plan.q8_env;
   const long small = (long)cdiv(M, 64) * cdiv(N, 64);
-  const bool persist = persist_env && wide >= persist_min;   // (q8 wins from one tile per CU on: 240 tiles 31.5 -> 28.1 us, 97.5 -> 85.1 us at K = 3072)
 #define FIBER_LAUNCH_EPI(EPI, R, RS)                                                                                          \
   do {                                                                                                                        \
     if (shape == 0 && EPI == 2 && !(persist && q8_env && !a.colpart)) return FIBER_EINVAL;   /* (the pre-q8 kernels are not built for gelu' * aux: 104-168 B of scratch) */ \

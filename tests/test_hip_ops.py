@@ -386,6 +386,25 @@ def test_wgrad_tn_identity_layout(ops):
     dw = ops.wgrad(bf(dy), bf(x))
     ref = dy.t() @ x
     assert torch.equal(dw.cpu(), ref), (dw.cpu() - ref).abs().max()
+    # the DropPath row mask (sample 2 of 8 dropped, scale 2: exact) and the output row map, with one split and with S > 1
+    perm = torch.randperm(N, generator=torch.Generator().manual_seed(1)).to(torch.int32)
+    for m_rows in (M, 8192):
+        hot = torch.arange(m_rows) % N
+        dy = torch.zeros(m_rows, N)
+        dy[torch.arange(m_rows), hot] = 1.0
+        x = (torch.arange(m_rows)[:, None] % 7 + torch.arange(K)[None, :] % 5).float()
+        mask = torch.ones(8)
+        mask[2] = 0.0
+        keep = mask[torch.arange(m_rows) // (m_rows // 8)][:, None]
+        ref = 2.0 * (dy * keep).t() @ x
+        dw, db = ops.wgrad(bf(dy), bf(x), want_bias=True, row_mask=mask.to(DEV), scale=2.0)
+        assert torch.equal(dw.cpu(), ref) and torch.equal(db.cpu(), 2.0 * (dy * keep).sum(0)), m_rows
+        dw, db = ops.wgrad(bf(dy), bf(x), want_bias=True, row_map=perm.to(DEV))
+        pref = torch.empty_like(ref)
+        pref[perm.long()] = dy.t() @ x
+        pb = torch.empty(N)
+        pb[perm.long()] = dy.sum(0)
+        assert torch.equal(dw.cpu(), pref) and torch.equal(db.cpu(), pb), m_rows
 
 
 def test_own_dgrad_nt(ops):
