@@ -179,7 +179,7 @@ __device__ __forceinline__ void fill_rowmeta(const AttnP& p, const Lds& L, int g
     float am = 0.f;
     if (j < len) {
       if (p.window) window_tok(p, g, j, tok, reg);
-      else { tok = g * len + j; if (keys && p.kmask) am = p.kmask[(size_t)g * len + j] * 1.4426950408889634f; }   // log2 domain
+      else { tok = g * len + j; if (keys && p.kmask) am = kmask_log2(p.kmask[(size_t)g * len + j]); }   // log2 domain (common.h)
     } else {
       am = -INFINITY;
     }
@@ -191,8 +191,8 @@ __device__ __forceinline__ void fill_rowmeta(const AttnP& p, const Lds& L, int g
 
 // ===================================================== forward =================================================
 // CAUSAL (text decoder self-attention, Lq == Lk, PLAIN mode): key j > query i is masked.  Key tiles wholly above a query strip's diagonal get
-// no LDS reads and no MFMAs; the diagonal tile masks per element.  Scores are floored at a finite value first, so that a padding mask of
-// finfo(fp32).min (-inf once scaled by log2 e) cannot turn a row's running max into -inf.
+// no LDS reads and no MFMAs; the diagonal tile masks per element.  A finfo(fp32).min key mask gives the finite KMASK_SCORE (common.h) in every
+// mode, so a row's running max never becomes -inf.
 template <int D, bool WINDOW, int NT = NKT, bool CAUSAL = false>   // NT: key (query) tiles held per chunk -- 3 for the 40-token text side
 __global__ __launch_bounds__(768) void attn_fwd_kernel(AttnP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -274,7 +274,8 @@ __global__ __launch_bounds__(768) void attn_fwd_kernel(AttnP p) {
             v += L.btab[ioff - L.woff[jl]];
             if (L.reg[jl] != qreg) v += -144.26950408889634f;   // -100 * log2(e)
           }
-          if (CAUSAL) v = kbase + jl > i ? -INFINITY : fmaxf(v, -1e30f);
+          if (!WINDOW) v = kmask_fix(v, KMASK_SCORE);
+          if (CAUSAL) v = kbase + jl > i ? -INFINITY : v;
           s[kt][r] = v;
           cmax = fmaxf(cmax, v);
         }
@@ -449,7 +450,8 @@ __global__ __launch_bounds__((WINDOW || NT > 6) ? 512 : 768) void attn_bwd_dq_ke
                   sv += L.btab[ioff - L.woff[jl]];
                   if (L.reg[jl] != qreg) sv += -144.26950408889634f;
                 }
-                if (CAUSAL) sv = kbase + jl > i ? -INFINITY : fmaxf(sv, -1e30f);
+                if (!WINDOW) sv = kmask_fix(sv, KMASK_SCORE);
+                if (CAUSAL) sv = kbase + jl > i ? -INFINITY : sv;
                 const float pr = __builtin_amdgcn_exp2f(sv - lse);
                 float dpe = dp[r];
                 if (p.p_drop > 0.f) {
@@ -572,7 +574,7 @@ __global__ __launch_bounds__((!WINDOW && NT > 6 && D == 64) ? 512 : 768) void at
     {
       const int jc = kvalid ? j : p.Lk - 1;
       if (WINDOW) window_tok(p, g, jc, ktok, kreg);
-      else { ktok = g * p.Lk + jc; if (p.kmask) kadd = p.kmask[(size_t)g * p.Lk + jc] * 1.4426950408889634f; }
+      else { ktok = g * p.Lk + jc; if (p.kmask) kadd = kmask_log2(p.kmask[(size_t)g * p.Lk + jc]); }
     }
     bf16x8 kf[KS], vf[KS];
     if (once) {
@@ -620,7 +622,8 @@ __global__ __launch_bounds__((!WINDOW && NT > 6 && D == 64) ? 512 : 768) void at
                   sv += L.btab[L.woff[il] - joff];
                   if (L.reg[il] != kreg) sv += -144.26950408889634f;
                 }
-                if (CAUSAL) sv = j > qbase + il ? -INFINITY : fmaxf(sv, -1e30f);
+                if (!WINDOW) sv = kmask_fix(sv, KMASK_SCORE);
+                if (CAUSAL) sv = j > qbase + il ? -INFINITY : sv;
                 float pr = kvalid ? __builtin_amdgcn_exp2f(sv - L.addmask[il]) : 0.f;
                 float dpe = dp[r], prd = pr;
                 if (p.p_drop > 0.f) {

@@ -100,7 +100,7 @@ __global__ __launch_bounds__(512) void i2t_bwd_kernel(XP p) {
   // additive key mask of the sample in the log2 domain, -inf past Lk: ONE load per thread into an LDS table (as per-lane loads behind
   // `key < Lk` branches hipcc gave every one of the 15 its own vmcnt(0): fifteen DRAM latencies in a row at the head of every workgroup)
   float* mkl = reinterpret_cast<float*>(smem + X_SMEM - 64 * 4);
-  if (tid < 64) mkl[tid] = tid < p.Lk ? (p.kmask ? p.kmask[(size_t)b * p.Lk + tid] * 1.4426950408889634f : 0.f) : -INFINITY;
+  if (tid < 64) mkl[tid] = tid < p.Lk ? (p.kmask ? kmask_log2(p.kmask[(size_t)b * p.Lk + tid]) : 0.f) : -INFINITY;
   // ---- K, V of the four heads: row-major images, rows >= Lk zero
   for (int idx = tid; idx < 4 * 64 * 4; idx += 512) {
     const int hh = idx >> 8, r = (idx >> 2) & 63, c = idx & 3;
@@ -186,7 +186,8 @@ __global__ __launch_bounds__(512) void i2t_bwd_kernel(XP p) {
     for (int kt = 0; kt < 3; ++kt) {
       const f32x4 st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr[kt], qf, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
       const f32x4 dpt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfr[kt], dof, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-      const f32x4 pr = exp2x4(__builtin_elementwise_fma(st, f32x4{c2, c2, c2, c2}, mkT[kt] - lse2));
+      const float rl = KMASK_SCORE - lse2;
+      const f32x4 pr = exp2x4(kmask_fix4(__builtin_elementwise_fma(st, f32x4{c2, c2, c2, c2}, mkT[kt] - lse2), f32x4{rl, rl, rl, rl}));
       dsT[kt] = pr * (dpt - dlt);
     }
     {
@@ -201,6 +202,7 @@ __global__ __launch_bounds__(512) void i2t_bwd_kernel(XP p) {
     }
     // ---- lane = key: S[query][key], dS, P -> dK^T, dV^T (contraction over the strip's 16 queries)
     const f32x4 seedL = *reinterpret_cast<const f32x4*>(stat + gq * 4), seedD = *reinterpret_cast<const f32x4*>(stat + 16 + gq * 4);
+    const f32x4 rsc = __builtin_elementwise_fma(seedL, f32x4{c2, c2, c2, c2}, f32x4{KMASK_SCORE, KMASK_SCORE, KMASK_SCORE, KMASK_SCORE});   // KMASK_SCORE - lse2
     s16x4 qt[2], dot[2];
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt) { qt[dt] = tr16(Qst, dt * 16, gq, lq); dot[dt] = tr16(dOst, dt * 16, gq, lq); }
@@ -209,7 +211,7 @@ __global__ __launch_bounds__(512) void i2t_bwd_kernel(XP p) {
       const f32x4 sv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, kfr[kt], seedL, 0, 0, 0);       // q.k - lse / (scale log2e)
       const f32x4 dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dof, vfr[kt], seedD, 0, 0, 0);      // dP - delta
       const float mk = mkS[kt];
-      const f32x4 pr = exp2x4(__builtin_elementwise_fma(sv, f32x4{c2, c2, c2, c2}, f32x4{mk, mk, mk, mk}));
+      const f32x4 pr = exp2x4(kmask_fix4(__builtin_elementwise_fma(sv, f32x4{c2, c2, c2, c2}, f32x4{mk, mk, mk, mk}), rsc));
       const s16x4 dsb = pack4(pr * dp), pb = pack4(pr);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
@@ -311,8 +313,7 @@ __global__ __launch_bounds__(256, 2) void t2i_bwd_kernel(TP p) {
   bf16* slabS = slabP + 3 * 256;
   float* mkl = reinterpret_cast<float*>(smem + T_FIX);
   for (int j = tid; j < ((p.Lk + 15) & ~15); j += 256)   // additive key mask in the log2 domain, -inf past Lk
-    mkl[j] = j < p.Lk ? (p.kmask ? (CAUSAL ? fmaxf(p.kmask[(size_t)b * p.Lk + j] * 1.4426950408889634f, -1e30f)
-                                          : p.kmask[(size_t)b * p.Lk + j] * 1.4426950408889634f) : 0.f) : -INFINITY;
+    mkl[j] = j < p.Lk ? (p.kmask ? kmask_log2(p.kmask[(size_t)b * p.Lk + j]) : 0.f) : -INFINITY;
   // ---- Q, dO images (rows >= Lq zero), delta = rowsum(dO . O), lse in the log2 domain (+inf past Lq: p = 0 there)
   for (int idx = tid; idx < 48 * 8; idx += 256) {
     const int r = idx >> 3, c = idx & 7;
@@ -411,7 +412,8 @@ __global__ __launch_bounds__(256, 2) void t2i_bwd_kernel(TP p) {
     for (int qt = 0; qt < 3; ++qt) {
       if (CAUSAL && qt < kt) continue;
       const float nl = -lse2[qt];
-      f32x4 arg = __builtin_elementwise_fma(st[qt], f32x4{c2, c2, c2, c2}, mk + nl);
+      const float rl = KMASK_SCORE + nl;
+      f32x4 arg = kmask_fix4(__builtin_elementwise_fma(st[qt], f32x4{c2, c2, c2, c2}, mk + nl), f32x4{rl, rl, rl, rl});
       if (CAUSAL && qt == kt) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) arg[r] = gq * 4 + r > lq ? -INFINITY : arg[r];   // key > query on the diagonal tile
@@ -524,8 +526,7 @@ __global__ __launch_bounds__(256, 3) void t2i_fwd_kernel(FP p) {
   const int b = blockIdx.x, h = blockIdx.y;
   bf16* Vt = reinterpret_cast<bf16*>(smem + T_MAXK * 4 + wave * T_KT);
   for (int j = tid; j < ((p.Lk + 15) & ~15); j += 256)   // additive key mask in the log2 domain, -inf past Lk
-    mkl[j] = j < p.Lk ? (p.kmask ? (CAUSAL ? fmaxf(p.kmask[(size_t)b * p.Lk + j] * 1.4426950408889634f, -1e30f)
-                                          : p.kmask[(size_t)b * p.Lk + j] * 1.4426950408889634f) : 0.f) : -INFINITY;
+    mkl[j] = j < p.Lk ? (p.kmask ? kmask_log2(p.kmask[(size_t)b * p.Lk + j]) : 0.f) : -INFINITY;
   bf16x8 qf[3][2];
 #pragma unroll
   for (int qt = 0; qt < 3; ++qt) {
@@ -581,7 +582,7 @@ __global__ __launch_bounds__(256, 3) void t2i_fwd_kernel(FP p) {
 #pragma unroll
     for (int qt = 0; qt < 3; ++qt) {
       if (CAUSAL && qt < kt) { alpha[qt] = 1.f; continue; }
-      f32x4 sv = __builtin_elementwise_fma(st[qt], f32x4{c2, c2, c2, c2}, mk);
+      f32x4 sv = kmask_fix4(__builtin_elementwise_fma(st[qt], f32x4{c2, c2, c2, c2}, mk), f32x4{KMASK_SCORE, KMASK_SCORE, KMASK_SCORE, KMASK_SCORE});
       if (CAUSAL && qt == kt) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) sv[r] = gq * 4 + r > lq ? -INFINITY : sv[r];     // key > query on the diagonal tile
@@ -694,7 +695,7 @@ __global__ __launch_bounds__(512, 3) void i2t_fwd_kernel(XF p) {
   const int hl = wave & 3, half = wave >> 2;
   const int b = blockIdx.x, h0 = blockIdx.y * 4, h = h0 + hl;
   float* mkl = reinterpret_cast<float*>(smem + 2 * X_KV);     // key mask of the sample (log2 domain, -inf past Lk): one load per thread
-  if (tid < 64) mkl[tid] = tid < p.Lk ? (p.kmask ? p.kmask[(size_t)b * p.Lk + tid] * 1.4426950408889634f : 0.f) : -INFINITY;
+  if (tid < 64) mkl[tid] = tid < p.Lk ? (p.kmask ? kmask_log2(p.kmask[(size_t)b * p.Lk + tid]) : 0.f) : -INFINITY;
   for (int idx = tid; idx < 4 * 64 * 4; idx += 512) {    // K, V of the four heads: row-major images, rows >= Lk zero
     const int hh = idx >> 8, r = (idx >> 2) & 63, c = idx & 3;
     bf16x8 kv, vv;
@@ -739,7 +740,7 @@ __global__ __launch_bounds__(512, 3) void i2t_fwd_kernel(XF p) {
     float mx = -INFINITY;
 #pragma unroll
     for (int kt = 0; kt < 3; ++kt) {
-      sv[kt] = __builtin_elementwise_fma(st[kt], f32x4{c2, c2, c2, c2}, mkT[kt]);
+      sv[kt] = kmask_fix4(__builtin_elementwise_fma(st[kt], f32x4{c2, c2, c2, c2}, mkT[kt]), f32x4{KMASK_SCORE, KMASK_SCORE, KMASK_SCORE, KMASK_SCORE});
       mx = fmaxf(mx, fmaxf(fmaxf(sv[kt][0], sv[kt][1]), fmaxf(sv[kt][2], sv[kt][3])));
     }
     mx = rows4_max(mx);

@@ -199,3 +199,17 @@ __device__ __forceinline__ void lds_dma16_v(const void* lane_src, void* lds_wave
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// Additive key masks of the mha kernels (attn.hip, attn_x.hip), log2 domain.  A mask of finfo(fp32).min (-inf once scaled by log2 e)
+// or anything at or below KMASK_FLOOR enters the key table as KMASK_FLOOR, which absorbs the scaled q.k exactly; such a score is then
+// REPLACED by KMASK_SCORE (kmask_fix, on the score or on score - lse2 with KMASK_SCORE - lse2).  All finfo.min keys of a row thus score
+// alike: a row whose every key is masked is the uniform average the reference's fp32 softmax gives (finfo.min absorbs its scores), with
+// the finite lse KMASK_SCORE ln 2 + log n from which the backward recomputes P = 1/n.  KMASK_SCORE lies far below any score of a row with
+// a live key, a -10000 padding (-14427) included, so exp2 flushes those keys to 0 there.  Padding past Lk stays -inf.
+constexpr float KMASK_FLOOR = -1e30f;
+constexpr float KMASK_SCORE = -16000.f;
+__device__ __forceinline__ float kmask_log2(float m) { return fmaxf(m * 1.4426950408889634f, KMASK_FLOOR); }
+__device__ __forceinline__ float kmask_fix(float x, float r) { return x == KMASK_FLOOR ? r : x; }
+__device__ __forceinline__ f32x4 kmask_fix4(f32x4 x, f32x4 r) {
+  return f32x4{kmask_fix(x[0], r[0]), kmask_fix(x[1], r[1]), kmask_fix(x[2], r[2]), kmask_fix(x[3], r[3])};
+}

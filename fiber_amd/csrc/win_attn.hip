@@ -93,11 +93,12 @@ __device__ __forceinline__ f32x4 fma4(f32x4 a, float b, float c) { return __buil
 __device__ __forceinline__ f32x4 exp2x4(f32x4 a) {
   return f32x4{__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1]), __builtin_amdgcn_exp2f(a[2]), __builtin_amdgcn_exp2f(a[3])};
 }
-// shift-mask term: -100 (natural-log logits) on keys of another shift region, as arithmetic on float region labels:
-// pen * (region_a - region_b)^2 is 0 when equal and <= pen otherwise (masked probabilities underflow to 0 either way)
+// shift-mask term: -100 (natural-log logits) on keys of another shift region, as arithmetic on the integer-valued float region labels:
+// pen * min((region_a - region_b)^2, 1) is 0 when equal and exactly pen otherwise.  (Swin's mask is additive -100, not -inf: where the
+// scores span more than 100 the masked keys keep weight, and (region_a - region_b)^2 alone -- up to 64 -- gave them too little.)
 __device__ __forceinline__ f32x4 region_mask(f32x4 sv, f32x4 ra, float rb, float pen) {
   const f32x4 d = ra - rb;
-  return __builtin_elementwise_fma(d * d, f32x4{pen, pen, pen, pen}, sv);
+  return __builtin_elementwise_fma(__builtin_elementwise_min(d * d, f32x4{1.f, 1.f, 1.f, 1.f}), f32x4{pen, pen, pen, pen}, sv);
 }
 __device__ __forceinline__ bf16x8 zero8() {
   bf16x8 z;
