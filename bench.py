@@ -6,12 +6,18 @@
 A "step" = one optimizer step on a synthetic per-GPU batch: two fused-backbone passes (MLM on masked text, ITM on
 true/false image pairs), losses, backward, gradient all-reduce (DDP over RCCL, N>1), AdamW + poly LR schedule.
 Prints ONE JSON line on rank 0 (metric = whole-job images/s).  Data is synthetic and already resident in HBM.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  `--full` adds everything else
+after the timed steps: the forward-only timing, the dominant kernel's roofline, the per-GPU batch sweep, the launch count,
+the CPU baseline (1 GPU) and the exposed all-reduce time (N > 1); --no-extras / --no-cpu-baseline trim a --full run.
 """
 import argparse
 import json
 import os
 import sys
 import time
+
+T_START = time.perf_counter()     # set-up time in the [bench] stderr summary counts from here
 
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC only on this driver (RCCL across processes)
 
@@ -159,7 +165,7 @@ def launches_per_step(batch, budget_s=150.0):
 def cpu_baseline(budget_s=280.0, batch=2):
     """The oracle (CPU restatement of the reference path, fp32 PyTorch) timed on this host's cores, the legs BASELINE.md section 4b
     names (2 warm-ups, median of 5 each), every child process under a hard wall-clock budget (killed by PID at the deadline) so that
-    the default bench finishes in minutes:
+    a --full run finishes in minutes:
       8 threads (the survey's container reference point): FIBER-Base 384^2 S=40 B=2 MLM+ITM forward + backward (images/s) and the
         fused-backbone forward alone (ms / image); Swin-T 224^2 + RoBERTa-base B=4 (BASELINE.json configs[0]) forward + backward;
       every physical core, run FIRST with a budget of its own (200 s): the FIBER-Base train leg at B=8, 1 warm-up + 2 timed steps.  On the
@@ -405,8 +411,12 @@ def main():
                          "short kernels on the GPU, not by the host, and graph mode's persistent gradients add ~300 accumulate "
                          "kernels), but eager with the text stack on its second stream -- the default, not capturable -- is 36.3 ms; "
                          "N > 1 always runs eager (the DDP reducer is host code)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the forward-only and dominant-kernel timings (clean rocprof runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: forward-only ms per image, the "
+                         "dominant kernel against both rooflines, per-GPU batches 8 / 16 / 32, launches per step, the CPU baseline "
+                         "(1 GPU) and the exposed all-reduce time (N > 1).  Off: the line carries the headline fields only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip everything else --full adds")
     ap.add_argument("--mlm-head", choices=("full", "labelled"), default="full",
                     help="full (default) = the reference's MLM head over every text position; labelled = config mlm_compact_rows: the head "
                          "only on the rows that carry a label (same loss and gradients; -2.8 ms per step at B=256; the head's FLOPs are then "
@@ -425,6 +435,8 @@ def main():
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.batch <= 0:
         args.batch = {"mlm_itm": 256, "mlm_itm_itc": 96, "vqa": 160}[args.task]
+    extras = args.full and not args.no_extras
+    cpu_baseline_leg = args.full and not args.no_cpu_baseline
 
     # `--gpus N` is the contract: one rank per GPU.  Under a launcher (torchrun sets WORLD_SIZE) the two must agree; without one,
     # N > 1 re-executes this very command line under torch.distributed.run on a free local port (reference: Lightning spawns one
@@ -540,6 +552,7 @@ def main():
             batch["itm_labels_override"].copy_(base_lab[torch.randperm(args.batch, device=device)])
             return gstep()
 
+    t_warm = time.perf_counter()
     for _ in range(args.warmup):
         step()
     # per-step HIP events (recorded on the compute stream, read after the timed region: no extra synchronisation inside it)
@@ -574,7 +587,7 @@ def main():
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     pct = lambda q: step_ms[min(len(step_ms) - 1, int(round(q * (len(step_ms) - 1))))]
     exposed_allreduce_ms = None
-    if world > 1 and not args.no_extras:
+    if world > 1 and extras:
         # the same step without the gradient all-reduce (DDP no_sync): the difference is the communication time that backward
         # did NOT hide.  Outside the timed region; gradients of these steps are rank-local and are thrown away with the run.
         n_ns = max(3, min(10, args.steps))
@@ -590,8 +603,8 @@ def main():
         exposed_allreduce_ms = round(ms - ms_ns.item(), 3)
     if rank == 0:
         print(f"[bench] {ms:.2f} ms/step, {args.batch * world * args.steps / dt:.1f} images/s, peak HBM "
-              f"{torch.cuda.max_memory_allocated() / 2**30:.1f} GiB allocated / {torch.cuda.max_memory_reserved() / 2**30:.1f} GiB reserved",
-              file=sys.stderr, flush=True)
+              f"{torch.cuda.max_memory_allocated() / 2**30:.1f} GiB allocated / {torch.cuda.max_memory_reserved() / 2**30:.1f} GiB reserved; "
+              f"set-up {t_warm - T_START:.1f} s, warm-up {t0 - t_warm:.1f} s", file=sys.stderr, flush=True)
     ips = args.batch * world * args.steps / dt
     lossv = loss.item()
     if rank == 0 and hasattr(opt, "rebuilds"):
@@ -629,12 +642,12 @@ def main():
                          "basis": f"{flop_img / 1e9:.1f} GFLOP algorithmic per image per step (BASELINE.md section 3 / SURVEY.md "
                                   f"section 8d: {task['flop'] / 1e9:.1f} with the MLM head on every row) / measured step time, per GPU"},
         }
-        if not args.no_extras:
+        if extras:
             res["fwd_ms_per_image"] = round(time_forward(model, batch, args.batch, device), 4)   # BASELINE.json metric, second half
-        if args.task == "mlm_itm" and not args.no_extras:
+        if args.task == "mlm_itm" and extras:
             res["roofline"]["dominant_kernel"] = time_dominant_kernel(args.batch, device)
             res["roofline"]["traffic"] = res["roofline"]["dominant_kernel"]["traffic"]
-        if world == 1 and args.task == "mlm_itm" and not args.no_extras and not use_graph:
+        if world == 1 and args.task == "mlm_itm" and extras and not use_graph:
             # SURVEY.md section 8d names per-GPU batches 8 (the reference README's example), 16 and 32: the same model and optimizer,
             # 8 warm-up + 10 timed eager steps each, after (and outside) the headline's timed region
             sweep = {}
@@ -666,7 +679,7 @@ def main():
             res["extra"] = {"batch_sweep": sweep, "batch_sweep_note": "per-GPU batches of SURVEY.md 8d (8 = coarse_grained/README.md:35), "
                             "same process after torch.cuda.empty_cache(), 8 warm-up + 10 timed eager steps each, wall clock around a device synchronise"}
             res["extra"]["launches_per_step"] = launches_per_step(32)
-        if world == 1 and not args.no_cpu_baseline and args.task == "mlm_itm":
+        if world == 1 and cpu_baseline_leg and args.task == "mlm_itm":
             res["cpu_baseline"] = cpu_baseline()
         print(json.dumps(res), flush=True)
     if world > 1:

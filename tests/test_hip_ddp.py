@@ -140,14 +140,15 @@ def test_no_sync_gradient_accumulation_real_module(tmp_path):
 def test_bench_contract_two_ranks_one_gpu():
     """bench.py exactly as the driver launches it at N > 1 (torch.distributed.run, one process per rank), with the backend
     switched to gloo so that two ranks can share the one visible GPU: rank 0 must print ONE JSON line with the contract keys,
-    n_gpus = 2 and a whole-job value."""
+    n_gpus = 2 and a whole-job value; with --full also the exposed all-reduce time, the forward-only and dominant-kernel timings."""
     import json
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     port = free_port()
     env = dict(os.environ, FIBER_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8",
+           "--full"]
     res = run_bounded(cmd, 240, cwd=root, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -161,6 +162,8 @@ def test_bench_contract_two_ranks_one_gpu():
     assert abs(d["value"] - 16 / (d["ms_per_step"] * 1e-3)) < 0.05 * d["value"]
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
         assert k in d["roofline"], k
+    assert d["step_ms"]["allreduce_exposed"] is not None and d["fwd_ms_per_image"] > 0, d
+    assert d["roofline"]["dominant_kernel"]["us"] > 0, d["roofline"]
 
 
 def test_bench_self_spawns_two_ranks_one_gpu():
@@ -182,7 +185,7 @@ def test_bench_self_spawns_two_ranks_one_gpu():
 
 
 def test_bench_counts_the_launches_of_a_step_in_a_child_process():
-    """`extra.launches_per_step` of the bench line: tools/probes/launch_count.py (torch.profiler, device activity) in a child under a deadline.
+    """`extra.launches_per_step` of the --full bench line: tools/probes/launch_count.py (torch.profiler, device activity) in a child under a deadline.
     Round 6 counts 1493 kernels + 12 copy commands per steady-state step, 1292 of the kernels from libfiber_hip.so (the review's bar: <= 1700)."""
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -196,7 +199,8 @@ def test_bench_counts_the_launches_of_a_step_in_a_child_process():
 
 def test_bench_dumps_the_outputs_of_its_last_timed_step(tmp_path):
     """`bench.py --dump-outputs DIR`: after the timed steps the loss, the forward's outputs (a seeded sample of the MLM logits) and the
-    updated parameters of the LAST timed step as float arrays, at most 64 MB; the line reports the timed steps it was asked for."""
+    updated parameters of the LAST timed step as float arrays, at most 64 MB; the line reports the timed steps it was asked for.
+    Without --full the run measures nothing beyond the headline: no forward-only, dominant-kernel, batch-sweep or CPU timings."""
     import json
     import sys
 
@@ -204,12 +208,13 @@ def test_bench_dumps_the_outputs_of_its_last_timed_step(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     res = run_bounded([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
-                       "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "out")], 240, cwd=root, env=env)
+                       "--dump-outputs", str(tmp_path / "out")], 240, cwd=root, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert not {"fwd_ms_per_image", "extra", "cpu_baseline"} & set(d) and "dominant_kernel" not in d["roofline"], sorted(d)
     got = {n[:-4]: np.load(tmp_path / "out" / n) for n in os.listdir(tmp_path / "out")}
     for k in ("loss", "mlm_loss", "itm_loss", "mlm_logits_sample", "itm_logits", "itm_labels", "param_norms", "param_sample"):
         assert k in got, (k, sorted(got))

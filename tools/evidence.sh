@@ -4,6 +4,7 @@
 TAG=${1:-r06}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
+OUT=$_                                    # the directory just made: every log below goes there
 python tools/stage_breakdown.py 256 5 > gpurun_out/${TAG}_stage_breakdown.md 2> gpurun_out/${TAG}_stage_breakdown.err
 cp gpurun_out/stage_breakdown.json gpurun_out/${TAG}_stage_breakdown.json
 python tools/shape_breakdown.py 256 3 > gpurun_out/${TAG}_shape_breakdown.log 2>&1
@@ -46,8 +47,8 @@ out = {"dominant": {"kernel": name, "selected": info["kernel"], "kind": info["ki
 json.dump(out, open(f"gpurun_out/{TAG}_pmc_kernels.json", "w"), indent=1)
 print(json.dumps(out, indent=1))
 PY
-# the bench line itself (50 steps, CPU baseline included), the same step with the round-3 tile boundary, and the small-batch sweep
-python bench.py --steps 50 --warmup 10 > gpurun_out/${TAG}_bench_b256.log 2>&1
+# the --full bench line (50 steps, CPU baseline included), the same step with the round-3 tile boundary, and the small-batch sweep
+python bench.py --full --steps 50 --warmup 10 > "$OUT/${TAG}_bench_b256.log" 2>&1
 FIBER_GEMM_STAGGER=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > gpurun_out/${TAG}_bench_b256_stagger_kept.log 2>&1
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > gpurun_out/${TAG}_bench_b256_again.log 2>&1
 for b in 8 16 32 64; do

@@ -1,5 +1,5 @@
 """Device launches of ONE steady-state training step, counted with torch.profiler (device activity only): kernels (ours + ATen + library)
-and copy / fill commands.  bench.py runs this as a child process with a deadline and puts the JSON line into `extra.launches_per_step`.
+and copy / fill commands.  bench.py --full runs this as a child process with a deadline and puts the JSON line into `extra.launches_per_step`.
     python tools/probes/launch_count.py [batch]"""
 import json
 import os
