@@ -7,7 +7,8 @@
 //
 // HBM-bound: one wave per row, 16-byte loads (8 bf16 per lane), the whole row held in registers between the
 // statistics and normalisation passes (one read, one write per element).  Backward keeps per-lane fp32 partial
-// sums of dgamma/dbeta across the rows a wave visits (grid-stride), writes one partial row per wave; a second tiny kernel folds the partials.
+// sums of dgamma/dbeta across the rows a wave visits (grid-stride), writes one partial row per workgroup; a second tiny kernel folds the
+// partials in a fixed order (no atomics: dgamma / dbeta are the same bits run to run).
 #include "common.h"
 
 namespace {
@@ -146,12 +147,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16* __restrict__ dy
                                                      const float* __restrict__ rstd, const bf16* __restrict__ dres,
                                                      bf16* __restrict__ dx,
                                                      float* __restrict__ part /*[grid][2][C]*/, int rows, int C,
-                                                     MergeMap mm, float* __restrict__ zero_g, float* __restrict__ zero_b) {
+                                                     MergeMap mm) {
   constexpr int RPW = 64 / LPR;
-  // the fold kernel that follows accumulates into dgamma / dbeta with atomics: they are zeroed here (the fold runs after this
-  // kernel in stream order) instead of by two memset launches per LayerNorm backward (164 launches per step)
-  if (blockIdx.x == 0)
-    for (int c = threadIdx.x; c < C; c += 256) { zero_g[c] = 0.f; zero_b[c] = 0.f; }
   const bf16* x = reinterpret_cast<const bf16*>(xv);
   const float* xf = reinterpret_cast<const float*>(xv);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -272,24 +269,26 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16* __restrict__ dy
   for (int c = threadIdx.x; c < C; c += 256) { my[c] = red[c]; my[C + c] = red[CP + c]; }
 }
 
-// fold the per-wave partial rows: block = 64 columns x 4 row lanes (coalesced along columns); the row range is split
-// over blockIdx.y and combined with one fp32 atomic per column (outputs pre-zeroed by the launcher)
-__global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(const float* __restrict__ part, float* __restrict__ dgamma,
-                                                            float* __restrict__ dbeta, int nrows, int C) {
-  __shared__ float red[4][64];
-  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
-  const int col = blockIdx.x * 64 + cl;            // column in the [2][C] partial row
-  const int per = (nrows + gridDim.y - 1) / gridDim.y;
-  const int r0 = blockIdx.y * per, r1 = min(nrows, r0 + per);
+// fold the per-workgroup partial rows in a fixed order: block = 16 columns x 64 row lanes; lane rl adds rows rl, rl + 64, ... in turn,
+// then a fixed pairwise tree over the 64 lanes in LDS, and the block writes dgamma / dbeta.  No atomics and no split across blocks:
+// the result does not depend on which block finishes when.  (The previous fold split the rows 16 ways over blockIdx.y and combined
+// the splits with fp32 atomics into pre-zeroed outputs: not reproducible run to run.)
+__global__ __launch_bounds__(1024) void ln_bwd_reduce_kernel(const float* __restrict__ part, float* __restrict__ dgamma,
+                                                             float* __restrict__ dbeta, int nrows, int C) {
+  __shared__ float red[64][17];
+  const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
+  const int col = blockIdx.x * 16 + cl;            // column in the [2][C] partial row
   float s = 0.f;
   if (col < 2 * C)
-    for (int r = r0 + rl; r < r1; r += 4) s += part[(size_t)r * 2 * C + col];
+    for (int r = rl; r < nrows; r += 64) s += part[(size_t)r * 2 * C + col];
   red[rl][cl] = s;
   __syncthreads();
-  if (rl == 0 && col < 2 * C) {
-    s = red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl];
-    atomicAdd(col < C ? dgamma + col : dbeta + (col - C), s);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    if (rl < o) red[rl][cl] += red[rl + o][cl];
+    __syncthreads();
   }
+  if (rl == 0 && col < 2 * C) (col < C ? dgamma[col] : dbeta[col - C]) = red[0][cl];
 }
 
 // row groups in flight per wave, forward / backward (A/B builds: -DLN_UF=1 -DLN_UB=1 is the one-row-at-a-time form).  tools/ln_bench.py,
@@ -346,11 +345,11 @@ template <bool MERGE, bool X32>
 int launch_bwd(const bf16* dy, const void* x, const float* g, const float* mean, const float* rstd, const bf16* dres,
                bf16* dx, float* dgamma, float* dbeta, float* ws, int grid, int rows, int C, MergeMap mm, hipStream_t st) {
 #define BWD(LPR, NV, UU, ...) hipLaunchKernelGGL((ln_bwd_kernel<LPR, NV, MERGE, X32, UU>), dim3(grid), dim3(256), 0, st, __VA_ARGS__)
-  LN_DISPATCH(BWD, LN_UB, 1, dy, x, g, mean, rstd, dres, dx, ws, rows, C, mm, dgamma, dbeta);
+  LN_DISPATCH(BWD, LN_UB, 1, dy, x, g, mean, rstd, dres, dx, ws, rows, C, mm);
 #undef BWD
   FIBER_CHECK_LAUNCH();
-  const int nrows = grid, ysplit = nrows >= 64 ? 16 : 1;          // one partial row per workgroup
-  hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3(cdiv(2 * C, 64), ysplit), dim3(256), 0, st, ws, dgamma, dbeta, nrows, C);
+  // one partial row per workgroup in ws [grid][2C]
+  hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3(cdiv(2 * C, 16)), dim3(1024), 0, st, ws, dgamma, dbeta, grid, C);
   FIBER_CHECK_LAUNCH();
   return FIBER_OK;
 }
@@ -408,6 +407,7 @@ extern "C" int fiber_layernorm_bwd_stream(const void* dy, const void* x, const f
 extern "C" int fiber_patch_merge_ln_fwd_bf16(const void* x, const float* gamma, const float* beta, void* y, float* mean,
                                              float* rstd, int B, int H, int W, int C, float eps, hipStream_t stream) {
   if ((C & 7) || (H & 1) || (W & 1)) return FIBER_EINVAL;
+  if (B <= 0) return FIBER_OK;                            // (nothing to normalise: no zero-sized launch)
   return launch_fwd<true, false>(x, gamma, beta, (bf16*)y, nullptr, mean, rstd, B * (H / 2) * (W / 2), 4 * C, eps,
                                  MergeMap{H, W, C}, stream);
 }
@@ -416,6 +416,7 @@ extern "C" int fiber_patch_merge_ln_fwd_bf16(const void* x, const float* gamma, 
 extern "C" int fiber_patch_merge_ln_fwd_stream(const void* x, const float* gamma, const float* beta, void* y, float* mean,
                                                float* rstd, int B, int H, int W, int C, float eps, int flags, hipStream_t stream) {
   if ((C & 7) || (H & 1) || (W & 1)) return FIBER_EINVAL;
+  if (B <= 0) return FIBER_OK;                            // (nothing to normalise: no zero-sized launch)
   const int rows = B * (H / 2) * (W / 2);
   if (flags & 1) return launch_fwd<true, true>(x, gamma, beta, (bf16*)y, nullptr, mean, rstd, rows, 4 * C, eps, MergeMap{H, W, C}, stream);
   return launch_fwd<true, false>(x, gamma, beta, (bf16*)y, nullptr, mean, rstd, rows, 4 * C, eps, MergeMap{H, W, C}, stream);
@@ -426,6 +427,7 @@ extern "C" int fiber_patch_merge_ln_bwd_bf16(const void* dy, const void* x, cons
                                              const float* rstd, void* dx, float* dgamma, float* dbeta, float* workspace,
                                              int B, int H, int W, int C, hipStream_t stream) {
   if ((C & 7) || (H & 1) || (W & 1)) return FIBER_EINVAL;
+  if (B <= 0) return FIBER_OK;
   const int rows = B * (H / 2) * (W / 2);
   return launch_bwd<true, false>((const bf16*)dy, x, gamma, mean, rstd, nullptr, (bf16*)dx, dgamma, dbeta, workspace,
                                  fiber_layernorm_bwd_grid(rows), rows, 4 * C, MergeMap{H, W, C}, stream);
@@ -435,6 +437,7 @@ extern "C" int fiber_patch_merge_ln_bwd_stream(const void* dy, const void* x, co
                                                const float* rstd, void* dx, float* dgamma, float* dbeta, float* workspace,
                                                int B, int H, int W, int C, int flags, hipStream_t stream) {
   if ((C & 7) || (H & 1) || (W & 1)) return FIBER_EINVAL;
+  if (B <= 0) return FIBER_OK;
   const int rows = B * (H / 2) * (W / 2);
   if (flags & 1)
     return launch_bwd<true, true>((const bf16*)dy, x, gamma, mean, rstd, nullptr, (bf16*)dx, dgamma, dbeta, workspace,
