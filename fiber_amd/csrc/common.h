@@ -14,6 +14,9 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 #define FIBER_EINVAL 1
 #define FIBER_ELAUNCH 2
 
+// Workspace floats of fiber_dot_bf16 and of fiber_stream_add_bwd's d alpha: one partial per workgroup, at most this many workgroups
+#define FIBER_DOT_PARTS 512
+
 #define FIBER_CHECK_LAUNCH()                          \
   do {                                                \
     hipError_t e__ = hipGetLastError();               \
@@ -199,6 +202,10 @@ __device__ __forceinline__ void lds_dma16_v(const void* lane_src, void* lds_wave
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// Host check of the vectorised entry points: true if any base pointer is not a multiple of `align` bytes (NULL passes).  The kernels use
+// 16-byte (or 8-byte) accesses on these bases, so a view at an odd element offset is refused here instead of being launched.
+template <class... T>
+static inline bool fiber_misaligned(size_t align, const T*... p) { return ((((uintptr_t)(const void*)p) & (align - 1)) | ... | 0) != 0; }
 
 // Additive key masks of the mha kernels (attn.hip, attn_x.hip), log2 domain.  A mask of finfo(fp32).min (-inf once scaled by log2 e)
 // or anything at or below KMASK_FLOOR enters the key table as KMASK_FLOOR, which absorbs the scaled q.k exactly; such a score is then

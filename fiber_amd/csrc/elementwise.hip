@@ -3,7 +3,7 @@
 //
 //   gelu_bwd          dH = dG * gelu'(H)                    (timm Mlp / RobertaIntermediate exact-erf GELU backward)
 //   scale_add         out = a + alpha * b                   (x + alpha_i2t*y swin_transformer.py:259; alpha_t2i roberta.py:483)
-//   dot_scaled        *out += sum(a*b)                      (d alpha = <dOut, branch>)
+//   dot               *out = sum(a*b)                       (d alpha = <dOut, branch>; fixed-order fold)
 //   colsum            db[n] = sum_m dY[m,n]                 (bias gradients of every nn.Linear)
 //   dropout           y = keep ? x/(1-p) : 0                (RoBERTa hidden dropout, roberta.py:198,339,420)
 //   rowscale_add      out = r + s[row/rows_per_sample] * x  (timm DropPath on the residual branch, swin_transformer.py:390-391)
@@ -38,6 +38,7 @@ __global__ __launch_bounds__(256) void scale_add_kernel(const bf16* __restrict__
   }
 }
 
+// out[blockIdx.x] = this workgroup's part of sum(a*b); with more than one workgroup colsum_fold_kernel adds the parts in a fixed order
 __global__ __launch_bounds__(256) void dot_kernel(const bf16* __restrict__ a, const bf16* __restrict__ b,
                                                   float* __restrict__ out, size_t nvec) {
   __shared__ float red[4];
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(256) void dot_kernel(const bf16* __restrict__ a, co
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out, red[0] + red[1] + red[2] + red[3]);
+  if (threadIdx.x == 0) out[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // column sums of a [M, N] bf16 matrix -> fp32.  block = 32 column-vectors x 8 row lanes covering 256 columns and one
@@ -216,7 +217,9 @@ __global__ __launch_bounds__(256) void droppath_scale_kernel(float* __restrict__
   if (seed_base) seed += *seed_base;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) {
-    const float u = (float)hash_u32(seed, (uint64_t)i) * (1.0f / 4294967296.0f);
+    // U from the top 23 bits: u <= 1 - 2^-23, so keep + u stays below 2 after rounding even at keep = 1 (the full 32 bits rounded
+    // to u = 1.0f for h >= 2^32 - 128, which gave a factor of 2)
+    const float u = (float)(hash_u32(seed, (uint64_t)i) >> 9) * (1.0f / 8388608.0f);
     out[i] = floorf(keep + u) / keep;
   }
 }
@@ -311,10 +314,11 @@ __global__ __launch_bounds__(256) void stream_add_kernel(StreamAddArgs p) {
 }
 
 // Backward of stream_add with respect to the branches: da = rowscale * mask_a * dy, db = rowscale * alpha * mask_b * dy,
-// dalpha += sum(rowscale * dy * drop_b(b)) (one fp32 atomic per workgroup; the caller zeroes it).  The residual gradient is dy.
+// dalpha = sum(rowscale * dy * drop_b(b)) (one partial per workgroup into dpart[blockIdx.x], folded in a fixed order by
+// colsum_fold_kernel when there is more than one workgroup).  The residual gradient is dy.
 struct StreamAddBwdArgs {
   const bf16* dy; const bf16* b; const float* alpha; const float* rowscale;
-  bf16* da; bf16* db; float* dalpha;
+  bf16* da; bf16* db; float* dpart;
   size_t nvec, vec_per_sample;
   uint64_t seed_a, seed_b; const uint64_t* seed_base;
   uint32_t thresh_a, thresh_b; float inv_keep_a, inv_keep_b;
@@ -327,7 +331,7 @@ __global__ __launch_bounds__(256) void stream_add_bwd_kernel(StreamAddBwdArgs p)
   if (p.seed_base) { sa += *p.seed_base; sb += *p.seed_base; }
   float acc = 0.f;
   // Four vectors per thread and iteration, every load issued before the first use: with the grid capped at 512 workgroups for the gate's one
-  // atomic per workgroup, one 16-byte load per thread in flight left the kernel at 4.1 TB/s of its bytes (LayerNorm: 5.4).
+  // partial per workgroup, one 16-byte load per thread in flight left the kernel at 4.1 TB/s of its bytes (LayerNorm: 5.4).
   constexpr int U = 4;
   const size_t stride = (size_t)gridDim.x * 256;
   for (size_t i0 = blockIdx.x * (size_t)256 + threadIdx.x; i0 < p.nvec; i0 += stride * U) {
@@ -338,7 +342,7 @@ __global__ __launch_bounds__(256) void stream_add_bwd_kernel(StreamAddBwdArgs p)
       const size_t i = i0 + u * stride;
       if (i < p.nvec) {
         dvs[u] = reinterpret_cast<const bf16x8*>(p.dy)[i];
-        if (p.db && p.dalpha) bvs[u] = reinterpret_cast<const bf16x8*>(p.b)[i];
+        if (p.db && p.dpart) bvs[u] = reinterpret_cast<const bf16x8*>(p.b)[i];
         rss[u] = p.rowscale ? p.rowscale[i / p.vec_per_sample] : 1.f;
       }
     }
@@ -366,17 +370,17 @@ __global__ __launch_bounds__(256) void stream_add_bwd_kernel(StreamAddBwdArgs p)
         for (int e = 0; e < 8; ++e) {
           const float m = p.thresh_b ? (drop_keep_e(hb, e, p.thresh_b) ? p.inv_keep_b : 0.f) : 1.f;
           o[e] = f2bf(al * m * g[e]);
-          if (p.dalpha) acc += g[e] * m * bf2f(bv[e]);
+          if (p.dpart) acc += g[e] * m * bf2f(bv[e]);
         }
         reinterpret_cast<bf16x8*>(p.db)[i] = o;
       }
     }
   }
-  if (p.dalpha) {
+  if (p.dpart) {
     acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(p.dalpha, red[0] + red[1] + red[2] + red[3]);
+    if (threadIdx.x == 0) p.dpart[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
   }
 }
 
@@ -397,7 +401,7 @@ inline int ew_grid(size_t nvec) {
 
 extern "C" int fiber_gelu_bwd_bf16(const void* dgelu, const void* h_pre, void* dh, long n, hipStream_t stream) {
   if (n <= 0) return FIBER_OK;
-  if (n & 7) return FIBER_EINVAL;
+  if ((n & 7) || fiber_misaligned(16, dgelu, h_pre, dh)) return FIBER_EINVAL;
   hipLaunchKernelGGL(gelu_bwd_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, stream, (const bf16*)dgelu, (const bf16*)h_pre, (bf16*)dh, (size_t)n / 8);
   FIBER_CHECK_LAUNCH();
   return FIBER_OK;
@@ -407,21 +411,31 @@ extern "C" int fiber_gelu_bwd_bf16(const void* dgelu, const void* h_pre, void* d
 extern "C" int fiber_scale_add_bf16(const void* a, const void* b, const float* alpha, float mult, void* out, long n,
                                     hipStream_t stream) {
   if (n <= 0) return FIBER_OK;
-  if (n & 7) return FIBER_EINVAL;
+  if ((n & 7) || !b || !out || fiber_misaligned(16, a, b, out)) return FIBER_EINVAL;
   hipLaunchKernelGGL(scale_add_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, stream, (const bf16*)a, (const bf16*)b, alpha, mult, (bf16*)out, (size_t)n / 8);
   FIBER_CHECK_LAUNCH();
   return FIBER_OK;
 }
 
-// out[0] += sum(a*b)   (out must be zero-initialised by the caller for a plain dot product)
-extern "C" int fiber_dot_bf16(const void* a, const void* b, float* out, long n, hipStream_t stream) {
+// Workgroups of the dot product / d alpha reduction: one fp32 partial each, folded in a fixed order (no atomics: the same bits every run)
+static inline int dot_grid(size_t nvec) {
+  const size_t g = (nvec + 255) / 256;
+  return (int)(g > FIBER_DOT_PARTS ? FIBER_DOT_PARTS : g);
+}
+
+// out[0] = sum(a*b) (overwritten).  workspace: fp32[FIBER_DOT_PARTS] for the per-workgroup partials (may be NULL when n <= 2048).
+extern "C" int fiber_dot_bf16(const void* a, const void* b, float* out, float* workspace, long n, hipStream_t stream) {
   if (n <= 0) return FIBER_OK;
-  if (n & 7) return FIBER_EINVAL;
-  size_t nvec = n / 8;
-  int grid = (int)((nvec + 255) / 256);
-  grid = grid > 512 ? 512 : grid;
-  hipLaunchKernelGGL(dot_kernel, dim3(grid), dim3(256), 0, stream, (const bf16*)a, (const bf16*)b, out, nvec);
+  if ((n & 7) || !out || fiber_misaligned(16, a, b)) return FIBER_EINVAL;
+  const size_t nvec = n / 8;
+  const int grid = dot_grid(nvec);
+  if (grid > 1 && !workspace) return FIBER_EINVAL;
+  hipLaunchKernelGGL(dot_kernel, dim3(grid), dim3(256), 0, stream, (const bf16*)a, (const bf16*)b, grid > 1 ? workspace : out, nvec);
   FIBER_CHECK_LAUNCH();
+  if (grid > 1) {
+    hipLaunchKernelGGL(colsum_fold_kernel, dim3(1), dim3(256), 0, stream, workspace, out, grid, 1);
+    FIBER_CHECK_LAUNCH();
+  }
   return FIBER_OK;
 }
 
@@ -438,7 +452,7 @@ extern "C" int fiber_colsum_slabs(int M, int N) {
 // out[n] = sum_m x[m,n]   (out fp32[N], overwritten); N % 8 == 0; workspace fp32[slabs*N] (may be NULL when slabs == 1)
 extern "C" int fiber_colsum_bf16(const void* x, float* out, float* workspace, int M, int N, int ld, hipStream_t stream) {
   if (M <= 0 || N <= 0) return FIBER_OK;
-  if ((N & 7) || (ld & 7)) return FIBER_EINVAL;
+  if ((N & 7) || (ld & 7) || fiber_misaligned(16, x)) return FIBER_EINVAL;
   const int gx = cdiv(N, 256);
   const int gy0 = fiber_colsum_slabs(M, N);
   const int rpb = cdiv(M, gy0), gy = cdiv(M, rpb);
@@ -457,7 +471,7 @@ extern "C" int fiber_colsum_bf16(const void* x, float* out, float* workspace, in
 extern "C" int fiber_gelu_bwd_colsum_bf16(const void* dgelu, const void* h_pre, void* dh, float* db, float* workspace, int M,
                                           int N, hipStream_t stream) {
   if (M <= 0 || N <= 0) return FIBER_OK;
-  if (N & 7) return FIBER_EINVAL;
+  if ((N & 7) || fiber_misaligned(16, dgelu, h_pre, dh)) return FIBER_EINVAL;
   const int gx = cdiv(N, 256);
   const int gy0 = fiber_colsum_slabs(M, N);
   const int rpb = cdiv(M, gy0), gy = cdiv(M, rpb);
@@ -477,7 +491,7 @@ extern "C" int fiber_gelu_bwd_colsum_bf16(const void* dgelu, const void* h_pre, 
 extern "C" int fiber_rowscale_colsum_bf16(const void* x, const float* scale, void* y, float* db, float* workspace, int M, int N,
                                           int rows_per_sample, hipStream_t stream) {
   if (M <= 0 || N <= 0) return FIBER_OK;
-  if ((N & 7) || rows_per_sample <= 0) return FIBER_EINVAL;
+  if ((N & 7) || rows_per_sample <= 0 || fiber_misaligned(16, x, y)) return FIBER_EINVAL;
   const int gx = cdiv(N, 256);
   const int gy0 = fiber_colsum_slabs(M, N);
   const int rpb = cdiv(M, gy0), gy = cdiv(M, rpb);
@@ -505,7 +519,7 @@ extern "C" int fiber_fold_rows_f32(const float* part, float* out, int rows, int 
 extern "C" int fiber_dropout_bf16(const void* x, void* y, long n, float p, uint64_t seed, const uint64_t* seed_base,
                                   hipStream_t stream) {
   if (n <= 0) return FIBER_OK;
-  if ((n & 7) || p < 0.f || p >= 1.f) return FIBER_EINVAL;
+  if ((n & 7) || p < 0.f || p >= 1.f || fiber_misaligned(16, x, y)) return FIBER_EINVAL;
   const uint32_t thresh = (uint32_t)((double)p * 4294967296.0);
   hipLaunchKernelGGL(dropout_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, stream, (const bf16*)x, (bf16*)y, (size_t)n / 8, seed, seed_base, thresh, 1.f / (1.f - p));
   FIBER_CHECK_LAUNCH();
@@ -526,7 +540,7 @@ extern "C" int fiber_droppath_scale_f32(float* out, int n, float keep, uint64_t 
 extern "C" int fiber_rowscale_add_bf16(const void* r, const void* x, const float* scale, void* out, long n,
                                        long per_sample, hipStream_t stream) {
   if (n <= 0) return FIBER_OK;
-  if ((n & 7) || (per_sample & 7)) return FIBER_EINVAL;
+  if ((n & 7) || per_sample <= 0 || (per_sample & 7) || fiber_misaligned(16, r, x, out)) return FIBER_EINVAL;
   hipLaunchKernelGGL(rowscale_add_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, stream, (const bf16*)r, (const bf16*)x, scale, (bf16*)out, (size_t)n / 8, (size_t)per_sample / 8);
   FIBER_CHECK_LAUNCH();
   return FIBER_OK;
@@ -540,6 +554,7 @@ extern "C" int fiber_stream_add(const void* res, int res_kind, const void* a, co
                                 const uint64_t* seed_base, float* out32, void* out16, long n, hipStream_t stream) {
   if (n <= 0) return FIBER_OK;
   if ((n & 7) || !a || (!out32 && !out16) || (res_kind && !res) || res_kind < 0 || res_kind > 2) return FIBER_EINVAL;
+  if (fiber_misaligned(16, res, a, b, out32, out16)) return FIBER_EINVAL;
   if (rowscale && (per_sample <= 0 || (per_sample & 7))) return FIBER_EINVAL;
   if (p_a < 0.f || p_a >= 1.f || p_b < 0.f || p_b >= 1.f || (p_b > 0.f && !b)) return FIBER_EINVAL;
   StreamAddArgs p{res, (const bf16*)a, (const bf16*)b, alpha, rowscale, out32, (bf16*)out16, (size_t)n / 8,
@@ -554,28 +569,37 @@ extern "C" int fiber_stream_add(const void* res, int res_kind, const void* a, co
 }
 
 // Branch gradients of fiber_stream_add: da (optional), db (optional; needs b when dalpha is wanted), dalpha (optional fp32
-// scalar, accumulated: zero it first).  dy bf16 [n].
+// scalar, overwritten; its per-workgroup partials go to workspace fp32[FIBER_DOT_PARTS], which may be NULL when n <= 2048).  dy bf16 [n].
 extern "C" int fiber_stream_add_bwd(const void* dy, const void* b, const float* alpha, const float* rowscale, long per_sample,
                                     float p_a, uint64_t seed_a, float p_b, uint64_t seed_b, const uint64_t* seed_base, void* da,
-                                    void* db, float* dalpha, long n, hipStream_t stream) {
+                                    void* db, float* dalpha, float* workspace, long n, hipStream_t stream) {
   if (n <= 0) return FIBER_OK;
   if ((n & 7) || !dy || (dalpha && (!b || !db))) return FIBER_EINVAL;
+  if (fiber_misaligned(16, dy, b, da, db)) return FIBER_EINVAL;
   if (rowscale && (per_sample <= 0 || (per_sample & 7))) return FIBER_EINVAL;
   if (p_a < 0.f || p_a >= 1.f || p_b < 0.f || p_b >= 1.f) return FIBER_EINVAL;
-  StreamAddBwdArgs p{(const bf16*)dy, (const bf16*)b, alpha, rowscale, (bf16*)da, (bf16*)db, dalpha, (size_t)n / 8,
+  StreamAddBwdArgs p{(const bf16*)dy, (const bf16*)b, alpha, rowscale, (bf16*)da, (bf16*)db, nullptr, (size_t)n / 8,
                      rowscale ? (size_t)per_sample / 8 : (size_t)1, seed_a, seed_b, seed_base,
                      (uint32_t)((double)p_a * 4294967296.0), (uint32_t)((double)p_b * 4294967296.0), 1.f / (1.f - p_a), 1.f / (1.f - p_b)};
   int grid = ew_grid(p.nvec);
-  if (dalpha && grid > 512) grid = 512;                  // one atomic per workgroup
+  if (dalpha) {                                          // one partial per workgroup
+    grid = dot_grid(p.nvec);
+    if (grid > 1 && !workspace) return FIBER_EINVAL;
+    p.dpart = grid > 1 ? workspace : dalpha;
+  }
   hipLaunchKernelGGL(stream_add_bwd_kernel, dim3(grid), dim3(256), 0, stream, p);
   FIBER_CHECK_LAUNCH();
+  if (dalpha && grid > 1) {
+    hipLaunchKernelGGL(colsum_fold_kernel, dim3(1), dim3(256), 0, stream, workspace, dalpha, grid, 1);
+    FIBER_CHECK_LAUNCH();
+  }
   return FIBER_OK;
 }
 
 // y (bf16) = x (fp32), n % 8 == 0: the bf16 shadow of an fp32 stream tensor where a GEMM consumes it and no producer wrote one
 extern "C" int fiber_cast_f32_bf16(const float* x, void* y, long n, hipStream_t stream) {
   if (n <= 0) return FIBER_OK;
-  if (n & 7) return FIBER_EINVAL;
+  if ((n & 7) || fiber_misaligned(16, x, y)) return FIBER_EINVAL;
   hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, stream, x, (bf16*)y, (size_t)n / 8);
   FIBER_CHECK_LAUNCH();
   return FIBER_OK;

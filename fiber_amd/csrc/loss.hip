@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void colsum_labelled_kernel(const bf16* __rest
 extern "C" int fiber_ce_fwd_bf16(const void* logits, const long long* labels, float* loss, float* lse, int* pred, int rows, int V,
                                  long long ignore_index, hipStream_t stream) {
   if (rows <= 0) return FIBER_OK;
-  if (V <= 16) return FIBER_EINVAL;
+  if (V <= 16 || fiber_misaligned(16, logits)) return FIBER_EINVAL;   // (each row's unaligned head is worked out from row * V)
   hipLaunchKernelGGL(ce_fwd_kernel, dim3(rows), dim3(256), 0, stream, (const bf16*)logits, labels, loss, lse, pred, V, ignore_index);
   FIBER_CHECK_LAUNCH();
   return FIBER_OK;
@@ -165,7 +165,7 @@ extern "C" int fiber_ce_fwd_bf16(const void* logits, const long long* labels, fl
 extern "C" int fiber_ce_bwd_bf16(const void* logits, const long long* labels, const float* lse, const float* scale, void* dlogits,
                                  int rows, int V, long long ignore_index, hipStream_t stream) {
   if (rows <= 0) return FIBER_OK;
-  if (V <= 16) return FIBER_EINVAL;
+  if (V <= 16 || fiber_misaligned(16, logits, dlogits)) return FIBER_EINVAL;
   hipLaunchKernelGGL(ce_bwd_kernel, dim3(rows), dim3(256), 0, stream, (const bf16*)logits, labels, lse, scale, (bf16*)dlogits, V,
                      ignore_index);
   FIBER_CHECK_LAUNCH();
@@ -179,7 +179,7 @@ extern "C" int fiber_fold_rows_f32(const float* part, float* out, int rows, int 
 extern "C" int fiber_colsum_labelled_slabs(int rows) { return rows >= 4096 ? 8 : rows >= 512 ? 4 : 1; }
 extern "C" int fiber_colsum_labelled_bf16(const void* x, const long long* labels, float* out, float* workspace, int rows, int V,
                                           long long ignore_index, hipStream_t stream) {
-  if (rows <= 0 || V <= 0) return FIBER_EINVAL;
+  if (rows <= 0 || V <= 0) return FIBER_OK;
   const int slabs = fiber_colsum_labelled_slabs(rows), rps = cdiv(rows, slabs);
   if ((size_t)rps * sizeof(int) > 60 * 1024) return FIBER_EINVAL;
   float* part = slabs > 1 ? workspace : out;

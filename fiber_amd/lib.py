@@ -29,7 +29,7 @@ SIGNATURES = {
     "fiber_patch_merge_ln_fwd_stream": [P, P, P, P, P, P, I, I, I, I, F, I],
     "fiber_patch_merge_ln_bwd_stream": [P, P, P, P, P, P, P, P, P, I, I, I, I, I],
     "fiber_stream_add": [P, I, P, P, P, P, L, F, U64, F, U64, P, P, P, L],
-    "fiber_stream_add_bwd": [P, P, P, P, L, F, U64, F, U64, P, P, P, P, L],
+    "fiber_stream_add_bwd": [P, P, P, P, L, F, U64, F, U64, P, P, P, P, P, L],
     "fiber_cast_f32_bf16": [P, P, L],
     "fiber_patch_merge_ln_fwd_bf16": [P, P, P, P, P, P, I, I, I, I, F],
     "fiber_patch_merge_ln_bwd_bf16": [P, P, P, P, P, P, P, P, P, I, I, I, I],
@@ -40,13 +40,13 @@ SIGNATURES = {
     "fiber_mha_bwd_bf16": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, F, F, U64, P],
     "fiber_mha_causal_bwd_bf16": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, F, F, U64, P],
     "fiber_roberta_embed_fwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, F, U64, P],
-    "fiber_roberta_embed_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, U64, P],
+    "fiber_roberta_embed_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, U64, P],
     "fiber_im2col_patch4": [P, P, I, I, I],
     "fiber_im2col_patch4_pair": [P, P, P, P, I, I, I],
     "fiber_gelu_bwd_bf16": [P, P, P, L],
     "fiber_gelu_bwd_colsum_bf16": [P, P, P, P, P, I, I],
     "fiber_scale_add_bf16": [P, P, P, F, P, L],
-    "fiber_dot_bf16": [P, P, P, L],
+    "fiber_dot_bf16": [P, P, P, P, L],
     "fiber_colsum_bf16": [P, P, P, I, I, I],
     "fiber_fold_rows_f32": [P, P, I, I],
     "fiber_dropout_bf16": [P, P, L, F, U64, P],
@@ -67,9 +67,10 @@ SIGNATURES = {
 }
 # host-side helpers without a stream argument
 PLAIN = {"fiber_layernorm_bwd_grid": [I], "fiber_window_attn_bwd_slices": [I, I], "fiber_window_attn_colsum_rows": [I, I, I], "fiber_colsum_slabs": [I, I], "fiber_tn_fold_blocks": [I, I, I, I], "fiber_colsum_labelled_slabs": [I], "fiber_gemm_row_tile": [I, I, I], "fiber_gemm_tn_splits": [I, I, I],
-         "fiber_adamw_chunk": [], "fiber_resample_ksize": [I, I], "fiber_dcn_dx_workspace": [I, I, I, I, I, I, I]}
+         "fiber_adamw_chunk": [], "fiber_resample_ksize": [I, I], "fiber_dcn_dx_workspace": [I, I, I, I, I, I, I],
+         "fiber_roberta_embed_bwd_workspace": [I, I, I]}
 
-PLAIN_LONG = {"fiber_dcn_dx_workspace"}          # helpers returning a 64-bit count
+PLAIN_LONG = {"fiber_dcn_dx_workspace", "fiber_roberta_embed_bwd_workspace"}          # helpers returning a 64-bit count
 _lib = None
 
 

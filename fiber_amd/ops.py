@@ -214,7 +214,11 @@ def _rows(x):
 
 
 def _c(t):
-    return t if t.is_contiguous() else t.contiguous()
+    """t as contiguous memory whose base the kernels' 16-byte vector accesses accept: a contiguous view at an offset that is not a
+    multiple of 16 bytes is copied (the entry points refuse such a base with FIBER_EINVAL)."""
+    if t.is_contiguous() and t.data_ptr() % 16 == 0:
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
 
 
 # ---- fp32 residual stream ---------------------------------------------------------------------------------------------------
@@ -314,6 +318,8 @@ def rowscale_colsum(dy2, rowscale):
 
 
 def colsum(x2):
+    if x2.data_ptr() % 16 or x2.stride(1) != 1 or x2.stride(0) % 8:
+        x2 = _c(x2)
     M, N = x2.shape
     out = torch.empty(N, dtype=torch.float32, device=x2.device)
     slabs = lib.plain("fiber_colsum_slabs", M, N)
@@ -418,7 +424,7 @@ class _CrossEntropy(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, ignore_index):
         rows, V = logits.shape
-        x = logits if logits.is_contiguous() else logits.contiguous()
+        x = _c(logits)
         lab = labels.contiguous()
         loss = torch.empty(rows, dtype=torch.float32, device=x.device)
         lse = torch.empty_like(loss)
@@ -1454,6 +1460,9 @@ def mha_kv_packed(q, kv, kmask, B, heads, scale, p_drop=0.0, seed=0):
     return _MHAPacked.apply(q, kv, kmask, 1, B, heads, float(scale), float(p_drop), int(seed))
 
 
+_DOT_PARTS = 512      # workspace floats of fiber_dot_bf16 / the d alpha of fiber_stream_add_bwd (FIBER_DOT_PARTS, csrc/common.h)
+
+
 class _ScaleAdd(torch.autograd.Function):
     """out = a + alpha * b with a learnable scalar alpha (alpha_i2t / alpha_t2i)."""
 
@@ -1471,8 +1480,9 @@ class _ScaleAdd(torch.autograd.Function):
         dout = _c(dout)
         db = torch.empty_like(b)
         lib.call("fiber_scale_add_bf16", None, lib.ptr(dout), lib.ptr(alpha), 1.0, lib.ptr(db), dout.numel())
-        dalpha = torch.zeros(1, dtype=torch.float32, device=dout.device)
-        lib.call("fiber_dot_bf16", lib.ptr(dout), lib.ptr(b), lib.ptr(dalpha), dout.numel())
+        dalpha = torch.empty(1, dtype=torch.float32, device=dout.device)
+        ws = torch.empty(_DOT_PARTS, dtype=torch.float32, device=dout.device)
+        lib.call("fiber_dot_bf16", lib.ptr(dout), lib.ptr(b), lib.ptr(dalpha), lib.ptr(ws), dout.numel())
         return dout, db, dalpha
 
 
@@ -1530,10 +1540,11 @@ class _StreamAdd(torch.autograd.Function):
         plain_a = rowscale is None and p_a == 0.0                       # d a = dy itself
         da = dy if plain_a else torch.empty_like(dy)
         db = torch.empty_like(dy) if has_b else None
-        dalpha = torch.zeros(1, dtype=torch.float32, device=dy.device) if (alpha is not None and has_b and ctx.needs_input_grad[3]) else None
+        dalpha = torch.empty(1, dtype=torch.float32, device=dy.device) if (alpha is not None and has_b and ctx.needs_input_grad[3]) else None
+        ws = torch.empty(_DOT_PARTS, dtype=torch.float32, device=dy.device) if dalpha is not None else None
         if not plain_a or has_b:
             lib.call("fiber_stream_add_bwd", lib.ptr(dy), lib.ptr(b), lib.ptr(alpha), lib.ptr(rowscale), per, p_a, seed_a, p_b, seed_b, base,
-                     None if plain_a else lib.ptr(da), lib.ptr(db), lib.ptr(dalpha), dy.numel())
+                     None if plain_a else lib.ptr(da), lib.ptr(db), lib.ptr(dalpha), lib.ptr(ws), dy.numel())
         return (dy if has_res else None), da, db, dalpha, None, None, None, None, None, None, None
 
 
@@ -1712,6 +1723,7 @@ class _RobertaEmbed(torch.autograd.Function):
         B, S = ids.shape
         C = word.shape[1]
         ids = _c(ids)
+        word, pos_tab, type_tab, gamma, beta = (_c(t) for t in (word, pos_tab, type_tab, gamma, beta))
         y = torch.empty((B, S, C), dtype=BF16, device=ids.device)
         pos = torch.empty((B, S), dtype=torch.int32, device=ids.device)
         mean = torch.empty(B * S, dtype=torch.float32, device=ids.device)
@@ -1727,12 +1739,14 @@ class _RobertaEmbed(torch.autograd.Function):
         ids, pos, word, pos_tab, type_tab, gamma, mean, rstd = ctx.saved_tensors
         B, S, C, pad, p_drop, seed, base = ctx.cfg
         dy = _c(dy)
+        # untouched table rows stay zero; the rows present, dtype row 0, dgamma and dbeta are overwritten (fixed-order sums)
         dword, dpos, dtype = torch.zeros_like(word), torch.zeros_like(pos_tab), torch.zeros_like(type_tab)
-        dg = torch.zeros(C, dtype=torch.float32, device=dy.device)
-        db = torch.zeros_like(dg)
+        dg = torch.empty(C, dtype=torch.float32, device=dy.device)
+        db = torch.empty_like(dg)
+        ws = torch.empty(lib.plain("fiber_roberta_embed_bwd_workspace", B, S, C), dtype=torch.float32, device=dy.device)
         lib.call("fiber_roberta_embed_bwd", lib.ptr(dy), lib.ptr(ids), lib.ptr(pos), lib.ptr(word), lib.ptr(pos_tab), lib.ptr(type_tab),
                  lib.ptr(gamma), lib.ptr(mean), lib.ptr(rstd), lib.ptr(dword), lib.ptr(dpos), lib.ptr(dtype), lib.ptr(dg), lib.ptr(db),
-                 B, S, C, pad, p_drop, seed, base)
+                 lib.ptr(ws), B, S, C, pad, p_drop, seed, base)
         return None, dword, dpos, dtype, dg, db, None, None, None, None
 
 

@@ -149,14 +149,17 @@ int fiber_mha_causal_bwd_bf16(const void* q, const void* k, const void* v, const
                               int D, int ldq, int ldk, int ldv, int ldo, int lddo, int lddq, int lddk, int lddv, float scale,
                               float p_drop, uint64_t seed, const uint64_t* seed_base, fiber_stream_t stream);
 
-/* RobertaEmbeddings.forward (roberta.py:169-199, 877-888) and its backward (scatter-add into fp32 gradient tables) */
+/* RobertaEmbeddings.forward (roberta.py:169-199, 877-888) and its backward: dword / dpos rows of the ids / positions present and dtype row 0,
+ * dgamma, dbeta are overwritten (the caller zeroes the other table rows), every sum in a fixed order; workspace: the floats
+ * fiber_roberta_embed_bwd_workspace returns */
 int fiber_roberta_embed_fwd(const int64_t* ids, const float* word, const float* pos_tab, const float* type_tab,
                             const float* gamma, const float* beta, void* y, int* pos_out, float* mean, float* rstd, int B, int S,
                             int C, int pad, float eps, float p_drop, uint64_t seed, const uint64_t* seed_base, fiber_stream_t stream);
 int fiber_roberta_embed_bwd(const void* dy, const int64_t* ids, const int* pos, const float* word, const float* pos_tab,
                             const float* type_tab, const float* gamma, const float* mean, const float* rstd, float* dword,
-                            float* dpos, float* dtype, float* dgamma, float* dbeta, int B, int S, int C, int pad, float p_drop,
-                            uint64_t seed, const uint64_t* seed_base, fiber_stream_t stream);
+                            float* dpos, float* dtype, float* dgamma, float* dbeta, float* workspace, int B, int S, int C, int pad,
+                            float p_drop, uint64_t seed, const uint64_t* seed_base, fiber_stream_t stream);
+long fiber_roberta_embed_bwd_workspace(int B, int S, int C);
 
 /* timm PatchEmbed Conv2d(3->C,k=4,s=4) as im2col (K=48 ordered [c][kh][kw], zero padded to 64) feeding fiber_gemm_nt_bf16 */
 int fiber_im2col_patch4(const float* img, void* cols, int B, int H, int W, fiber_stream_t stream);
@@ -165,12 +168,14 @@ int fiber_im2col_patch4(const float* img, void* cols, int B, int H, int W, fiber
 int fiber_im2col_patch4_pair(const float* img, const float* alt, const unsigned char* sel, void* cols, int B, int H, int W,
                              fiber_stream_t stream);
 
-/* element-wise / reduction helpers (n % 8 == 0) */
+/* element-wise / reduction helpers (n % 8 == 0).  These, the cross-entropy, RoBERTa embedding and im2col entry points refuse (FIBER_EINVAL)
+ * a base pointer that their vector accesses would use unaligned: 16 bytes, 8 for the bf16x4 outputs of the embedding and im2col. */
 int fiber_gelu_bwd_bf16(const void* dgelu, const void* h_pre, void* dh, long n, fiber_stream_t stream);
 int fiber_gelu_bwd_colsum_bf16(const void* dgelu, const void* h_pre, void* dh, float* db, float* workspace, int M, int N,
                                fiber_stream_t stream);
 int fiber_scale_add_bf16(const void* a, const void* b, const float* alpha, float mult, void* out, long n, fiber_stream_t stream);
-int fiber_dot_bf16(const void* a, const void* b, float* out, long n, fiber_stream_t stream);
+/* out[0] = sum(a*b), overwritten; workspace fp32[512] (NULL allowed when n <= 2048): per-workgroup partials, folded in a fixed order */
+int fiber_dot_bf16(const void* a, const void* b, float* out, float* workspace, long n, fiber_stream_t stream);
 int fiber_colsum_slabs(int M, int N); /* workspace = slabs*N floats when slabs > 1 */
 int fiber_colsum_bf16(const void* x, float* out, float* workspace, int M, int N, int ld, fiber_stream_t stream);
 int fiber_fold_rows_f32(const float* part, float* out, int rows, int N, fiber_stream_t stream);
@@ -188,10 +193,11 @@ int fiber_rowscale_add_bf16(const void* r, const void* x, const float* scale, vo
 int fiber_stream_add(const void* res, int res_kind, const void* a, const void* b, const float* alpha, const float* rowscale,
                      long per_sample, float p_a, uint64_t seed_a, float p_b, uint64_t seed_b, const uint64_t* seed_base,
                      float* out32, void* out16, long n, fiber_stream_t stream);
-/* branch gradients of the above: da, db (nullable), dalpha (nullable fp32 scalar, accumulated: zero it first; needs b) */
+/* branch gradients of the above: da, db (nullable), dalpha (nullable fp32 scalar, overwritten; needs b and db) with its per-workgroup
+ * partials in workspace fp32[512] (NULL allowed when n <= 2048), folded in a fixed order */
 int fiber_stream_add_bwd(const void* dy, const void* b, const float* alpha, const float* rowscale, long per_sample, float p_a,
                          uint64_t seed_a, float p_b, uint64_t seed_b, const uint64_t* seed_base, void* da, void* db, float* dalpha,
-                         long n, fiber_stream_t stream);
+                         float* workspace, long n, fiber_stream_t stream);
 /* y (bf16) = x (fp32): the bf16 copy of an fp32 stream tensor for a GEMM that consumes it */
 int fiber_cast_f32_bf16(const float* x, void* y, long n, fiber_stream_t stream);
 /* y = scale[row / rows_per_sample] * x (DropPath backward, swin_transformer.py:390-391) and db = column sums of y (bias
