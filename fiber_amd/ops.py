@@ -1920,3 +1920,119 @@ def deform_conv(x, offset, mask, weight, bias=None, stride=1, pad=1, out_fp32=Fa
     is stored in fp32 (the offset / mask predictor: the reference runs the whole operator in fp32, deform_conv.py:335, and sampling
     positions rounded to bf16 move every bilinear weight by up to 2^-9 of the offset)."""
     return _DeformConv.apply(x, offset, mask, weight, bias, stride, pad, out_fp32)
+
+
+# ---- grounding head: region-word alignment + binary token focal loss (csrc/ground.hip) ---------------------------------------------
+def _ground_inputs(x, p, tbias, log_scale):
+    B, A, C = x.shape
+    T = p.shape[1]
+    if p.shape != (B, T, C) or tbias.shape != (B, T) or log_scale.numel() != 1:
+        raise ValueError(f"ground: x {tuple(x.shape)}, p {tuple(p.shape)}, tbias {tuple(tbias.shape)}, log_scale {tuple(log_scale.shape)}")
+    return (_c(x.detach().to(BF16)), _c(p.detach().to(BF16)), _c(tbias.detach().float()), _c(log_scale.detach().float().reshape(1)),
+            B, A, T, C)
+
+
+def _ground_workspace(B, A, T, device):
+    return torch.empty(max(1, lib.plain("fiber_ground_workspace", B, A, T)), dtype=torch.float32, device=device)
+
+
+def _ground_operand_grads(ctx, ds, x16, p16):
+    """dX = ds . P (NT kernel) and dP = ds^T . X (TN kernel), image by image: P differs per image."""
+    B, A, T = ds.shape
+    dx = dp = None
+    if ctx.needs_input_grad[0]:
+        pt = p16.transpose(1, 2).contiguous()                      # [B, C, T]: the W operand of Y = X . W^T
+        dx = torch.empty((B, A, pt.shape[1]), dtype=BF16, device=ds.device)
+        for b in range(B):                                         # written in place: no second [B, A, C] copy at the full geometry
+            lib.call("fiber_gemm_nt_bf16", lib.ptr(ds[b]), lib.ptr(pt[b]), None, None, lib.ptr(dx[b]), None, None, 0, None, 0, None,
+                     A, pt.shape[1], T, T, T, pt.shape[1], 0, 0)
+    if ctx.needs_input_grad[1]:
+        # dP is an ACTIVATION gradient (it flows on into the text projection), so it stays on the current stream and is folded at once:
+        # wgrad()'s side stream and deferred fold are for parameter gradients that nothing reads before the backward pass ends
+        C = x16.shape[2]
+        dp = torch.empty((B, T, C), dtype=torch.float32, device=ds.device)
+        S = lib.plain("fiber_gemm_tn_splits", A, T, C)
+        ws = torch.empty(S * (T * C + T), dtype=torch.float32, device=ds.device) if S > 1 else None
+        for b in range(B):
+            lib.call("fiber_gemm_tn_bf16", lib.ptr(ds[b]), lib.ptr(x16[b]), lib.ptr(dp[b]), None, lib.ptr(ws), A, T, C, T, C, None, 0, 1.0)
+    return dx, dp
+
+
+class _GroundLogits(torch.autograd.Function):
+    """The plain path: s materialised in fp32.  Backward: ds = dlogits where the clamp is inactive, as bf16, through the same two
+    GEMMs as the fused path."""
+
+    @staticmethod
+    def forward(ctx, x, p, tbias, log_scale):
+        x16, p16, tb, ls, B, A, T, C = _ground_inputs(x, p, tbias, log_scale)
+        out = torch.empty((B, A, T), dtype=torch.float32, device=x.device)
+        lib.call("fiber_ground_fwd_bf16", lib.ptr(x16), lib.ptr(p16), lib.ptr(tb), lib.ptr(ls), None, None, lib.ptr(out), None, None,
+                 B, A, T, C, -1.0, 0.0)
+        ctx.save_for_backward(x16, p16, tb, ls, out)
+        ctx.dtypes = (x.dtype, p.dtype, tbias.dtype, log_scale.dtype, log_scale.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x16, p16, tb, ls, out = ctx.saved_tensors
+        inv = torch.exp(-ls)
+        dsf = torch.where(out.abs() < 50000.0, dout.float(), torch.zeros((), device=out.device))     # clamp inactive
+        dtb = dsf.sum(1) if ctx.needs_input_grad[2] else None
+        dls = -(dsf * (out - tb[:, None, :])).sum().reshape(ctx.dtypes[4]) if ctx.needs_input_grad[3] else None
+        dx, dp = _ground_operand_grads(ctx, (dsf * inv).to(BF16), x16, p16)
+        return (dx.to(ctx.dtypes[0]) if dx is not None else None, dp.to(ctx.dtypes[1]) if dp is not None else None,
+                dtb.to(ctx.dtypes[2]) if dtb is not None else None, dls.to(ctx.dtypes[3]) if dls is not None else None)
+
+
+class _GroundTokenLoss(torch.autograd.Function):
+    """The fused path: forward = one launch that writes a scalar; backward = one launch that recomputes the tile and emits ds
+    (bf16) + the dtbias / dlog_scale sums, then the two GEMMs.  Nothing of size [B, A, T] is saved."""
+
+    @staticmethod
+    def forward(ctx, x, p, tbias, log_scale, targets, text_mask, alpha, gamma):
+        x16, p16, tb, ls, B, A, T, C = _ground_inputs(x, p, tbias, log_scale)
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        ws = _ground_workspace(B, A, T, x.device)
+        lib.call("fiber_ground_fwd_bf16", lib.ptr(x16), lib.ptr(p16), lib.ptr(tb), lib.ptr(ls), lib.ptr(targets), lib.ptr(text_mask), None,
+                 lib.ptr(loss), lib.ptr(ws), B, A, T, C, float(alpha), float(gamma))
+        ctx.save_for_backward(x16, p16, tb, ls, targets, text_mask)
+        ctx.hyper = (float(alpha), float(gamma))
+        ctx.dtypes = (x.dtype, p.dtype, tbias.dtype, log_scale.dtype, log_scale.shape)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x16, p16, tb, ls, targets, text_mask = ctx.saved_tensors
+        B, A, C = x16.shape
+        T = p16.shape[1]
+        dev = x16.device
+        ds = torch.empty((B, A, T), dtype=BF16, device=dev)
+        dtb = torch.empty((B, T), dtype=torch.float32, device=dev)
+        dls = torch.empty(1, dtype=torch.float32, device=dev)
+        ws = _ground_workspace(B, A, T, dev)
+        g32 = _c(g.detach().float().reshape(1))
+        lib.call("fiber_ground_bwd_bf16", lib.ptr(x16), lib.ptr(p16), lib.ptr(tb), lib.ptr(ls), lib.ptr(targets), lib.ptr(text_mask),
+                 lib.ptr(g32), lib.ptr(ds), lib.ptr(dtb), lib.ptr(dls), lib.ptr(ws), B, A, T, C, *ctx.hyper)
+        dx, dp = _ground_operand_grads(ctx, ds, x16, p16)
+        return (dx.to(ctx.dtypes[0]) if dx is not None else None, dp.to(ctx.dtypes[1]) if dp is not None else None,
+                dtb.to(ctx.dtypes[2]) if ctx.needs_input_grad[2] else None,
+                dls.reshape(ctx.dtypes[4]).to(ctx.dtypes[3]) if ctx.needs_input_grad[3] else None, None, None, None, None)
+
+
+def ground_logits(x, p, tbias, log_scale):
+    """fp32 [B, A, T] alignment logits clamp(x . p^T * exp(-log_scale) + tbias, +-50000) (vldyhead.py:857-891); x [B, A, 256] tower
+    features (rounded to bf16), p [B, 256, 256] projected tokens (rounded to bf16), tbias fp32 [B, 256], log_scale one element."""
+    return _GroundLogits.apply(x, p, tbias, log_scale)
+
+
+def ground_token_loss(x, p, tbias, log_scale, targets, text_mask=None, alpha=0.25, gamma=2.0):
+    """Sum over anchors and unmasked tokens of the binary token focal loss of the alignment logits (sigmoid_focal_loss.py:130-195,
+    TokenSigmoidFocalLoss version="binary"), without materialising them.  targets [B, A, T] holding 0/1 in any dtype (converted to
+    uint8 once); text_mask [B, T] (> 0 = live) or None = all tokens."""
+    if targets.numel() == 0:
+        return torch.zeros((), dtype=torch.float32, device=x.device)
+    if targets.shape != (x.shape[0], x.shape[1], p.shape[1]):
+        raise ValueError(f"ground_token_loss: targets {tuple(targets.shape)} for x {tuple(x.shape)}, p {tuple(p.shape)}")
+    t8 = _c(targets if targets.dtype == torch.uint8 else (targets != 0).to(torch.uint8))
+    m8 = torch.ones(p.shape[:2], dtype=torch.uint8, device=x.device) if text_mask is None else _c((text_mask > 0).to(torch.uint8))
+    return _GroundTokenLoss.apply(x, p, tbias, log_scale, t8, m8, alpha, gamma)

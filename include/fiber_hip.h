@@ -276,6 +276,28 @@ long fiber_dcn_dx_workspace(int B, int H, int W, int C, int Ho, int Wo, int stri
 int fiber_dcn_dx_bf16(const void* dcols, const float* offset, const float* mask, void* dx, float* workspace, int B, int H, int W,
                       int C, int Ho, int Wo, int kh, int kw, int stride, int pad, fiber_stream_t stream);
 
+/* Region-word alignment of the grounding head VLDyHead + the binary token focal loss reduced in its epilogue (csrc/ground.hip); file:line
+ * relative to /root/reference/fine_grained/maskrcnn_benchmark/.  replaces modeling/rpn/vldyhead.py:857-891 (permute_and_flatten, matmul /
+ * log_scale.exp() + bias, clamp to +-50000) and layers/sigmoid_focal_loss.py:130-195 (token_sigmoid_binary_focal_loss, TokenSigmoidFocalLoss
+ * .sum()) as called from modeling/rpn/loss.py:1222-1226.
+ *   s[b,a,t] = clamp(dot(X[b,a,:], P[b,t,:]) * exp(-log_scale[0]) + tbias[b,t], -50000, 50000)
+ * X bf16 [B,A,C] (tower outputs, channels-last, all levels concatenated along A; A arbitrary), P bf16 [B,T,C] (projected tokens), tbias fp32
+ * [B,T], log_scale one fp32 in device memory (no host synchronisation).  C = T = 256 only (anything else -> 1).
+ * fwd: logits (nullable) fp32 [B,A,T] receives s; loss (nullable, one fp32, overwritten) receives the sum over the tokens with text_mask != 0
+ * of alpha_t * softplus(-z) * sigmoid(-z)^gamma, z = +s where target != 0 and -s elsewhere; target uint8 [B,A,T], text_mask uint8 [B,T] (both
+ * required with loss); alpha < 0 = no alpha weighting; gamma >= 0.  The loss path writes no [B,A,T] tensor.  At least one output.
+ * bwd: recomputes s; with ds = g[0] * dloss/ds (g: upstream scalar in device memory; zero for masked tokens and where the clamp is active):
+ * dtbias fp32 [B,T] = sum_a ds, dlog_scale (one fp32) = -sum ds * (s_unclamped - tbias), and `ds` bf16 [B,A,T] receives ds * exp(-log_scale[0]),
+ * the gradient of the raw dot product, so that dX = ds . P and dP = ds^T . X are fiber_gemm_nt_bf16 / fiber_gemm_tn_bf16 on it as stored.  workspace: fiber_ground_workspace(B, A, T) floats (per-workgroup partials, folded in a
+ * fixed order by fiber_fold_rows_f32; no atomics). */
+long fiber_ground_workspace(int B, int A, int T);
+int fiber_ground_fwd_bf16(const void* X, const void* P, const float* tbias, const float* log_scale, const unsigned char* target,
+                          const unsigned char* text_mask, float* logits, float* loss, float* workspace, int B, int A, int T, int C,
+                          float alpha, float gamma, fiber_stream_t stream);
+int fiber_ground_bwd_bf16(const void* X, const void* P, const float* tbias, const float* log_scale, const unsigned char* target,
+                          const unsigned char* text_mask, const float* g, void* ds, float* dtbias, float* dlog_scale, float* workspace,
+                          int B, int A, int T, int C, float alpha, float gamma, fiber_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
