@@ -8,23 +8,25 @@
 // swin_transformer.py:431; fiber_module.py:349-350 cross-modal transforms).
 //
 // Kernel family (CDNA4, all NT = both operands K-contiguous, v_mfma_f32_32x32x16_bf16 issued with swapped operands so each
-// lane owns 4 consecutive output columns):
-//   gemm_nt_wide_persist2_kernel 256x256 tile, 8 waves, two 64-KB LDS-DMA stages, two wave groups half a sub-tile apart,
-//                                persistent over output tiles (>= 512 tiles, N % 256 == 0), wave-private epilogue with no
+// lane owns 4 consecutive output columns), in the order gemm_plan() tries them:
+//   gemm_nt_q8_kernel            256x256 tile, 8 waves in two groups, two 64-KB LDS-DMA stages re-staged a quarter at a time,
+//                                persistent over output tiles (>= 200 tiles, N % 64 == 0), wave-private epilogue with no
 //                                workgroup barrier, bias as accumulator seed                          <- the large shapes
-//   gemm_nt_wide_persist_kernel  its predecessor (workgroup-wide staged epilogue): still serves the fused gelu' * aux + column
-//                                sums backward and the residual-without-DropPath forms, which spill in the v4 structure
-//   gemm_nt_wide_kernel          the same K loop, one tile per workgroup (200..511 tiles)
-//   gemm_nt_glds_kernel          256x128 (3-stage ring, counted vmcnt) / 128x128 / 64x64 tiles for N not a multiple of 256 or
-//                                few tiles (stage-0 qkv / proj, text layers at small batch, edge configs)
-//   gemm_nt_kernel               register-staged fallback for K % 64 != 0 (patch embedding K = 48 -> 64 padded is DMA-able;
-//                                this covers odd test shapes)
+//   gemm_nt_wide_persist_kernel  the same tile and tile walk with a K-split loop and a workgroup-wide staged epilogue
+//                                (N % 256 == 0): GELU + residual and the fp32 residual stream without a row scale, which
+//                                spill in the q8 structure
+//   gemm_nt_glds_kernel          256x128 (3-stage ring, counted vmcnt) / 128x128 / 64x64 tiles for N not a multiple of 64,
+//                                few tiles or gelu' * aux with column sums (stage-0 qkv / proj, text layers at small batch,
+//                                edge configs)
+//   gemm_nt_kernel               register-staged 128x128 / 64x64 for K % 64 != 0 (patch embedding K = 48 -> 64 padded is
+//                                DMA-able; this covers odd test shapes) and for fp32 outputs
 // Operands go global -> LDS by global_load_lds_dwordx4 with a 16-byte-chunk XOR swizzle (chunk ^= (row>>1)&7) applied on the
 // per-lane SOURCE address (the DMA writes lane-linear) and on the ds_read_b128 side: conflict-free for both (LDS bank row =
 // 256 B = two 128-B tile rows).  Every epilogue (bias, exact-erf GELU + pre-activation copy, DropPath row scale, residual,
-// gelu' * aux + column sums) is a compile-time variant of tile_epilogue<>, staged through LDS so that global stores and
-// residual loads are 16-byte row-contiguous.  Workgroup ids are remapped so that consecutive tiles of one X row panel land on
-// the same XCD (shared L2).  Measurements behind each choice: profiles/r01_summary.md.
+// gelu' * aux + column sums) is a compile-time variant of tile_epilogue<> / wave_epilogue<>, staged through LDS so that global
+// stores and residual loads are 16-byte row-contiguous.  Workgroup ids are remapped so that consecutive tiles of one X row panel
+// land on the same XCD (shared L2).  Measurements behind each choice: profiles/r01_summary.md; the generations this file no
+// longer carries: profiles/gemm_nt_retired.md.
 #include <stdlib.h>
 
 #include "gemm_epilogue.h"
@@ -331,9 +333,10 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_glds_kernel(GemmArgs a) 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// v3 ("wide"): 256x256 output tile, 8 waves as 2(M) x 4(N) -> 128x64 per wave, two 64-KB LDS stages of 64-deep K tiles.
+// Wide persistent: 256x256 output tile, 8 waves as 2(M) x 4(N) -> 128x64 per wave, two 64-KB LDS stages of 64-deep K tiles, one
+// workgroup per CU walking a run of output tiles.  Serves the wide shapes whose epilogue gemm_nt_q8_kernel is not built for.
 //
-// What the measurements said (tools/gemm_ab.py / gemm_dbg.py / gemm_trace.py, rocprofv3 PMC, M = 295k..74k):
+// What the measurements said (tools/gemm_ab.py / gemm_trace.py, rocprofv3 PMC, M = 295k..74k):
 //  * lock-step waves (all eight in the same phase) add their phases up: MFMA-only 1640 TFLOP/s, +DMA 1016, +ds_read
 //    1150, all three 830.  So the eight waves form two groups (wm = 0 / 1: one wave of each per SIMD) that run the same K
 //    loop HALF A SUB-TILE APART: a load phase (12 fragment ds_reads) and a math phase (16 MFMAs) per 32-deep sub-tile,
@@ -344,174 +347,15 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_glds_kernel(GemmArgs a) 
 //    the math phase (512).  128-byte rows halve the requests per byte, hence K tiles of 64 and only two stages (three do not
 //    fit the 160-KB LDS): the whole next K tile is requested in the first load phase of the current one and has 2.5 phases
 //    to land.
-template <int WM, int WN, int EPI, bool HAS_R, bool HAS_RS, bool TRACE = false>
-__global__ __launch_bounds__(64 * WM * WN) void gemm_nt_wide_kernel(GemmArgs a) {
-  constexpr int BM = 256, BN = 256, NS = 2;
-  constexpr int NT = 64 * WM * WN;
-  static_assert(NT == 512 && WM == 2, "two wave groups of four; DMA pass geometry for 8 waves");
-  constexpr int WTM = BM / WM, WTN = BN / WN;
-  constexpr int TM = WTM / 32, TN = WTN / 32;
-  constexpr int RPD = NT / 8;                          // 64 tile rows per DMA pass (8 lanes x 16 B per 128-B row)
-  constexpr int PA = BM / RPD, PB = BN / RPD;          // 4 + 4 DMA instructions per wave per K tile
-  constexpr int NDMA = PA + PB;
-  constexpr int STAGE = (BM + BN) * BK;
-  constexpr int CLD = BN + 8;
-  static_assert((size_t)(BM / 2) * CLD * 2 <= (size_t)NS * STAGE * 2, "epilogue half tile must fit in the ring");
-  // ring stages + 1 KB of bias (ONE LDS object: a second __shared__ array next to LDS-DMA makes the compiler's waitcnt
-  // pass guard ds_reads with vmcnt(0))
-  __shared__ __attribute__((aligned(16))) bf16 smem[NS * STAGE + 512];
-  float* bias_s = reinterpret_cast<float*>(smem + NS * STAGE);
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / WN, wn = wave % WN;
-  const int tilesN = (a.N + BN - 1) / BN, tilesM = (a.M + BM - 1) / BM;
-  const int nblk = tilesM * tilesN;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int tm0 = (bid / tilesN) * BM, tn0 = (bid % tilesN) * BN;
-
-  const int srow = wave * 8 + (lane >> 3), spc = lane & 7;
-  const bf16* xsrc[PA];
-  const bf16* wsrc[PB];
-#pragma unroll
-  for (int p = 0; p < PA; ++p) {
-    const int row = srow + p * RPD;
-    xsrc[p] = a.X + (size_t)min(tm0 + row, a.M - 1) * a.ldx + ((spc ^ ((row >> 1) & 7)) << 3);
-  }
-#pragma unroll
-  for (int p = 0; p < PB; ++p) {
-    const int row = srow + p * RPD;
-    wsrc[p] = a.W + (size_t)min(tn0 + row, a.N - 1) * a.ldw + ((spc ^ ((row >> 1) & 7)) << 3);
-  }
-  auto dma = [&](int kt) {
-    bf16* st = smem + (kt & 1) * STAGE;
-#pragma unroll
-    for (int p = 0; p < PA; ++p)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xsrc[p] + kt * BK),
-                                       (__attribute__((address_space(3))) void*)(st + (p * RPD + wave * 8) * BK), 16, 0, 0);
-#pragma unroll
-    for (int p = 0; p < PB; ++p)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wsrc[p] + kt * BK),
-                                       (__attribute__((address_space(3))) void*)(st + BM * BK + (p * RPD + wave * 8) * BK), 16, 0, 0);
-  };
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int nk = a.K / BK;
-  const int frow = lane & 31, fk = lane >> 5;
-  bf16x8 fa[2][TM], fb[2][TN];
-  // fragments of the 32-deep sub-tile `sub` of K tile kt (two MFMA k-steps)
-  auto load_phase = [&](int kt, int sub) {
-    const bf16* Ac = smem + (kt & 1) * STAGE;
-    const bf16* Bc = Ac + BM * BK;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i) fa[ks][i] = *reinterpret_cast<const bf16x8*>(Ac + swz(wm * WTM + i * 32 + frow, sub * 4 + ks * 2 + fk));
-#pragma unroll
-      for (int j = 0; j < TN; ++j) fb[ks][j] = *reinterpret_cast<const bf16x8*>(Bc + swz(wn * WTN + j * 32 + frow, sub * 4 + ks * 2 + fk));
-    }
-  };
-  auto math_phase = [&]() {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[ks][j], fa[ks][i], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  // workgroup barrier closing a phase; `landed`: first make this wave's share of the next K tile resident (all of its
-  // requests were issued two or more phases ago, nothing newer is in flight, so the wait is a plain vmcnt(0))
-  auto phase_barrier = [&](bool landed) {
-    if (landed) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-  stage_bias<BN>(a, bias_s, tn0);
-  dma(0);
-  phase_barrier(true);                                    // K tile 0 resident for everyone
-  if (wm == 1) phase_barrier(false);                      // stagger: group 1 runs one phase behind
-  // TRACE build (tools/gemm_trace.py): s_memtime deltas of the segments of a K tile, summed per wave
-  unsigned long long tr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long t0 = 0;
-  if constexpr (TRACE) t0 = __builtin_amdgcn_s_memtime();
-  const unsigned long long tstart = t0;
-  auto mark = [&](int i) {
-    if constexpr (TRACE) {
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      tr[i] += t - t0;
-      t0 = t;
-    }
-  };
-  // Global phase p of group 0 = 4 kt + {0: load sub 0, 1: math, 2: load sub 1, 3: math}; group 1 does the same at p + 1.
-  // Stage (kt+1)&1 was last read in phase 4 kt - 1 (group 1, sub-tile 1 of K tile kt-1), so the requests for K tile kt+1
-  // go out in the first load phase of K tile kt; every wave makes its share resident before the barrier that closes global
-  // phase 4 kt + 3 -- the end of math(sub 1) for group 0, of load(sub 1) for group 1 -- after which group 0 reads it.
-  for (int kt = 0; kt < nk; ++kt) {
-    load_phase(kt, 0);
-    if (kt + 1 < nk) dma(kt + 1);
-    if constexpr (TRACE) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    mark(0);
-    phase_barrier(false);
-    mark(1);
-    math_phase();
-    mark(2);
-    phase_barrier(false);
-    mark(3);
-    load_phase(kt, 1);
-    if constexpr (TRACE) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    mark(4);
-    phase_barrier(wm == 1);
-    mark(5);
-    math_phase();
-    mark(6);
-    phase_barrier(wm == 0);
-    mark(7);
-  }
-  if (wm == 0) phase_barrier(false);                      // re-align the barrier count of the two groups
-  if constexpr (TRACE) {
-    if (lane == 0 && blockIdx.x < 8) {
-      float* o = a.colpart + (blockIdx.x * 8 + wave) * 16;
-      for (int i = 0; i < 8; ++i) o[i] = (float)tr[i];
-      o[8] = (float)(__builtin_amdgcn_s_memtime() - tstart);
-      o[9] = (float)nk;
-    }
-    return;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  // ---- epilogue: two 128-row slabs through the (now idle) ring -------------------------------------------------
-  if (tm0 + BM <= a.M && tn0 + BN <= a.N)
-    tile_epilogue<BM, BN, WM, WN, 2, EPI, HAS_R, HAS_RS, true>(a, acc, smem, bias_s, tm0, tn0);
-  else
-    tile_epilogue<BM, BN, WM, WN, 2, EPI, HAS_R, HAS_RS, false>(a, acc, smem, bias_s, tm0, tn0);
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------
-// v3 persistent: the wide kernel walking a run of output tiles per workgroup (one workgroup per CU).  At K = 512 the
-// non-persistent kernel spends ~9 of 23 us per tile outside the K loop, most of it waiting for its 128 KB of output to drain
-// to HBM before the workgroup may retire and the next one may even start fetching.  Here the K-tile stream simply continues
-// across tiles (the last K tile of tile t requests the first of tile t+1), the epilogue goes through the stage that tile's
-// last K tile just vacated (four 64-row rounds of 33 KB), its stores drain under the next tile's MFMAs, and the bias slice
-// arrives by LDS-DMA ahead of the tile's first K tile (double-buffered by tile parity).
+//  * with one output tile per workgroup, ~9 of the 23 us of a K = 512 tile went by outside the K loop, most of it waiting for
+//    the 128 KB of output to drain to HBM before the workgroup may retire and the next one may even start fetching.  Here the
+//    K-tile stream simply continues across tiles (the last K tile of tile t requests the first of tile t+1), the epilogue goes
+//    through the stage that tile's last K tile just vacated (four 64-row rounds of 33 KB), its stores drain under the next
+//    tile's MFMAs, and the bias slice arrives by LDS-DMA ahead of the tile's first K tile (double-buffered by tile parity).
+// Global phase p of group 0 = 4 kt + {0: load sub 0, 1: math, 2: load sub 1, 3: math}; group 1 does the same at p + 1.
+// Stage (kt+1)&1 was last read in phase 4 kt - 1 (group 1, sub-tile 1 of K tile kt-1), so the requests for K tile kt+1
+// go out in the first load phase of K tile kt; every wave makes its share resident before the barrier that closes global
+// phase 4 kt + 3 -- the end of math(sub 1) for group 0, of load(sub 1) for group 1 -- after which group 0 reads it.
 template <int WM, int WN, int EPI, bool HAS_R, bool HAS_RS>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_wide_persist_kernel(GemmArgs a) {
   constexpr int BM = 256, BN = 256, NS = 2;
@@ -610,6 +454,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_wide_persist_kernel(Gemm
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[ks][j], fa[ks][i], acc[i][j], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
   };
+  // workgroup barrier closing a phase; `landed`: first make this wave's share of the next K tile resident (all of its
+  // requests were issued two or more phases ago, nothing newer is in flight, so the wait is a plain vmcnt(0))
   auto phase_barrier = [&](bool landed) {
     if (landed) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -626,7 +472,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_wide_persist_kernel(Gemm
   for (int seq = 0; seq < T; ++seq) {
     const int id = first + seq * P;
     const int tm0 = (id / tilesN) * BM, tn0 = (id % tilesN) * BN;
-    if (wm == 1) phase_barrier(false);                    // stagger: group 1 runs one phase behind (see the wide kernel)
+    if (wm == 1) phase_barrier(false);                    // stagger: group 1 runs one phase behind (see the kernel's comment)
     for (int kt = 0; kt < nk; ++kt, ++g) {
       load_phase(g, 0);
       if (kt + 1 < nk) dma(g + 1, kt + 1);
@@ -651,206 +497,18 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_wide_persist_kernel(Gemm
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// v4 persistent: the same K loop, but nothing between two output tiles is a workgroup-wide event any more.
+// q8: the persistent 256x256 kernel of the large shapes.  Tile, LDS images, wave groups and tile walk are those of
+// gemm_nt_wide_persist_kernel; nothing between two output tiles is a workgroup-wide event, and the K loop is cut along the OUTPUT
+// instead of along K.
 //  * epilogue = wave_epilogue<>: each wave drains its own 128x64 sub-tile through a private 4-KB LDS slab (dedicated: 8 x 4 KB
-//    next to the two ring stages = the whole 160 KB), no barriers -- the v3 epilogue (4 rounds x 2 workgroup barriers, half
+//    next to the two ring stages = the whole 160 KB), no barriers -- the staged epilogue (4 rounds x 2 workgroup barriers, half
 //    the waves idle during each staging pass, MFMA pipe idle throughout) cost ~7 of the ~21 us of a K = 512 tile;
-//  * the two wave groups keep their stagger ACROSS tiles (one extra barrier for group 1 before the first tile, one for group 0
-//    after the last), so one group's epilogue runs under the other group's last / first MFMAs;
-//  * bias = accumulator seed: the first MFMAs of a tile take C from 32 VGPRs built out of scalar loads of the wave's 64 bias
-//    values (or constant 0) -- no zeroing pass (128 VALU per wave per tile), no bias adds, no bias slice in LDS.
-template <int WM, int WN, int EPI, bool HAS_R, bool HAS_RS, bool TRACE = false>
-__global__ __launch_bounds__(64 * WM * WN) void gemm_nt_wide_persist2_kernel(GemmArgs a) {
-  constexpr int BM = 256, BN = 256, NS = 2;
-  constexpr int NT = 64 * WM * WN;
-  static_assert(NT == 512 && WM == 2 && WN == 4, "two wave groups of four; DMA pass geometry for 8 waves");
-  constexpr int WTM = BM / WM, WTN = BN / WN;
-  constexpr int TM = WTM / 32, TN = WTN / 32;
-  static_assert(TN == 2 && WTN == 64, "wave_epilogue slab = 32 x 64");
-  constexpr int RPD = NT / 8;
-  constexpr int PA = BM / RPD, PB = BN / RPD;
-  constexpr int STAGE = (BM + BN) * BK;
-  constexpr int SLAB = 32 * 64;                                                   // elements of one wave's slab (4 KB)
-  __shared__ __attribute__((aligned(16))) bf16 smem[NS * STAGE + 8 * SLAB];       // ONE LDS object: 128 KB ring + 32 KB slabs
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WN, wn = wave % WN;
-  bf16* cw = smem + NS * STAGE + wave * SLAB;
-  const int tilesN = (a.N + BN - 1) / BN, tilesM = (a.M + BM - 1) / BM;
-  const int nblk = tilesM * tilesN;
-  const int P = gridDim.x >> 3, xcd = blockIdx.x & 7, widx = blockIdx.x >> 3;
-  const int q8 = nblk >> 3, r8 = nblk & 7;
-  const int first = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + widx;
-  const int count = q8 + (xcd < r8 ? 1 : 0);
-  const int T = widx < count ? (count - widx + P - 1) / P : 0;
-  if (T == 0) return;
-
-  const int srow = wave * 8 + (lane >> 3), spc = lane & 7;
-  const bf16* xbase; const bf16* wbase;
-  unsigned xo[PA], wo[PB];
-  auto aim = [&](int seq) {
-    const int id = first + seq * P;
-    const int m0 = (id / tilesN) * BM, n0 = (id % tilesN) * BN;
-    xbase = a.X + (size_t)m0 * a.ldx;
-    wbase = a.W + (size_t)n0 * a.ldw;
-#pragma unroll
-    for (int p = 0; p < PA; ++p) {
-      const int row = srow + p * RPD;
-      xo[p] = (unsigned)(min(row, a.M - 1 - m0) * a.ldx + ((spc ^ ((row >> 1) & 7)) << 3)) * 2u;
-    }
-#pragma unroll
-    for (int p = 0; p < PB; ++p) {
-      const int row = srow + p * RPD;
-      wo[p] = (unsigned)(min(row, a.N - 1 - n0) * a.ldw + ((spc ^ ((row >> 1) & 7)) << 3)) * 2u;
-    }
-  };
-  auto dma = [&](int g, int kt) {
-    bf16* st = smem + (g & 1) * STAGE;
-#pragma unroll
-    for (int p = 0; p < PA; ++p)
-      lds_dma16(xbase + kt * BK, xo[p], st + (p * RPD + wave * 8) * BK);
-#pragma unroll
-    for (int p = 0; p < PB; ++p)
-      lds_dma16(wbase + kt * BK, wo[p], st + BM * BK + (p * RPD + wave * 8) * BK);
-  };
-
-  f32x16 acc[TM][TN];
-  const int nk = a.K / BK;
-  const int frow = lane & 31, fk = lane >> 5;
-  bf16x8 fa[2][TM], fb[2][TN];
-  auto load_phase = [&](int g, int sub) {
-    const bf16* Ac = smem + (g & 1) * STAGE;
-    const bf16* Bc = Ac + BM * BK;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i) fa[ks][i] = *reinterpret_cast<const bf16x8*>(Ac + swz(wm * WTM + i * 32 + frow, sub * 4 + ks * 2 + fk));
-#pragma unroll
-      for (int j = 0; j < TN; ++j) fb[ks][j] = *reinterpret_cast<const bf16x8*>(Bc + swz(wn * WTN + j * 32 + frow, sub * 4 + ks * 2 + fk));
-    }
-  };
-  auto math_phase = [&]() {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[ks][j], fa[ks][i], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  // first math phase of a tile: C = the bias of the wave's 64 columns in accumulator layout (element q*4+e of block j is
-  // column j*32 + q*8 + 4*(lane>>5) + e), read with SCALAR loads (wave-uniform address) and picked per half-wave
-  auto math_phase_seeded = [&](int n0w) {
-    f32x16 seed[TN];
-    if (EPI != 2 && a.bias) {
-      typedef __attribute__((address_space(4))) const float cfloat;
-      cfloat* bp = (cfloat*)(uintptr_t)(a.bias + n0w);
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float lo = bp[j * 32 + q * 8 + e], hi = bp[j * 32 + q * 8 + 4 + e];
-            seed[j][q * 4 + e] = fk ? hi : lo;
-          }
-    } else {
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) seed[j][r] = 0.f;
-    }
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[0][j], fa[0][i], seed[j], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[1][j], fa[1][i], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  auto phase_barrier = [&](bool landed) {
-    if (landed) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-  aim(0);
-  dma(0, 0);
-  phase_barrier(true);
-  if (wm == 1) phase_barrier(false);                      // group 1 runs one phase behind group 0 from here to the end
-  int g = 0;
-  // TRACE build (tools/gemm_trace.py persist): s_memtime ticks per wave, summed over its tiles --
-  //   [0] first K tile of a tile  [1] other K tiles  [2] epilogue  [3..6] the four barriers of a K tile (wait + barrier)  [7] load+dma issue
-  unsigned long long tr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long t0 = 0, tb = 0;
-  if constexpr (TRACE) t0 = __builtin_amdgcn_s_memtime();
-  const unsigned long long tstart = t0;
-  auto mark = [&](int i) {
-    if constexpr (TRACE) {
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      tr[i] += t - t0;
-      t0 = t;
-    }
-  };
-  auto bar_t = [&](int i, bool landed) {
-    if constexpr (TRACE) tb = __builtin_amdgcn_s_memtime();
-    phase_barrier(landed);
-    if constexpr (TRACE) tr[3 + i] += __builtin_amdgcn_s_memtime() - tb;
-  };
-  for (int seq = 0; seq < T; ++seq) {
-    const int id = first + seq * P;
-    const int tm0 = (id / tilesN) * BM, tn0 = (id % tilesN) * BN;
-    for (int kt = 0; kt < nk; ++kt, ++g) {
-      if constexpr (TRACE) tb = __builtin_amdgcn_s_memtime();
-      load_phase(g, 0);
-      if (kt + 1 < nk) dma(g + 1, kt + 1);
-      else if (seq + 1 < T) { aim(seq + 1); dma(g + 1, 0); }
-      if constexpr (TRACE) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tr[7] += __builtin_amdgcn_s_memtime() - tb; }
-      bar_t(0, false);
-      if (kt == 0) math_phase_seeded(tn0 + wn * WTN); else math_phase();
-      bar_t(1, false);
-      load_phase(g, 1);
-      bar_t(2, wm == 1);
-      math_phase();
-      bar_t(3, wm == 0);
-      mark(kt == 0 ? 0 : 1);
-    }
-    if (tm0 + BM <= a.M)
-      wave_epilogue<TM, EPI, HAS_R, HAS_RS, true>(a, acc, cw, tm0 + wm * WTM, tn0 + wn * WTN);
-    else
-      wave_epilogue<TM, EPI, HAS_R, HAS_RS, false>(a, acc, cw, tm0 + wm * WTM, tn0 + wn * WTN);
-    mark(2);
-  }
-  if (wm == 0) phase_barrier(false);                      // every wave passes the same number of barriers
-  if constexpr (TRACE) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0 && blockIdx.x < 8) {
-      float* o = a.colpart + (blockIdx.x * 8 + wave) * 16;
-      for (int i = 0; i < 8; ++i) o[i] = (float)tr[i];
-      o[8] = (float)(__builtin_amdgcn_s_memtime() - tstart);
-      o[9] = (float)nk;
-      o[10] = (float)T;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// v5 ("q8", round 3): the persistent kernel with the K loop re-cut along the OUTPUT instead of along K -- the 8-phase schedule of
-// cdna_hip_programming.md section 5 ("The 256^2 8-phase template") on this kernel's LDS images, tile walk and wave-private epilogue.
+//  * bias = accumulator seed: the first MFMAs of a tile take C from VGPRs built out of scalar loads of the wave's 64 bias
+//    values (or constant 0) -- no zeroing pass (128 VALU per wave per tile), no bias adds, no bias slice in LDS;
+//  * the K loop is the 8-phase schedule of cdna_hip_programming.md section 5 ("The 256^2 8-phase template").
 //
-// Why: in v4 a wave requests the whole next K tile (8 LDS-DMA instructions) at the head of one load phase.  The texture addresser
-// takes ~31 cycles per 1-KB instruction, so the 4 x 8 instructions of a wave group hold that phase for ~1000 cycles while the
+// Why: in the K-split loop of gemm_nt_wide_persist_kernel a wave requests the whole next K tile (8 LDS-DMA instructions) at the
+// head of one load phase.  The texture addresser takes ~31 cycles per 1-KB instruction, so the 4 x 8 instructions of a wave group hold that phase for ~1000 cycles while the
 // partner group's 16 MFMAs need 512: two of the four phases of every K tile run at half the matrix pipe's pace (trace: 3.3-3.6 k
 // cycles per K tile for 2.05 k of MFMA).  Spreading the same requests over all four phases INCLUDING the math phases made it
 // slower (662 vs 568 us at 294912 x 512 x 2048: a wave stalled on a full DMA queue stops feeding the matrix pipe), and a K-split
@@ -1141,13 +799,14 @@ __global__ __launch_bounds__(512) void gemm_nt_q8_kernel(GemmArgs a) {
   }
 }
 
-// Variants the v4 (wave-private epilogue) persistent kernel serves: those it compiles without scratch.  gelu' * aux WITH column sums
-// and the residual-without-DropPath forms spill 60-120 VGPRs around its longer live ranges and stay on v3; gelu' * aux without
-// column sums (the caller takes the bias gradient from the weight-gradient kernel) is served.
-__device__ float g_gemm_one = 1.0f;        // the scale of the residual-without-DropPath form served by the DropPath instantiation
-
-template <int EPI, bool R, bool RS>
-constexpr bool kV4Ok = (EPI == 0 && (!R || RS)) || (EPI == 1 && !R) || EPI == 2 || (EPI == 3 && RS);
+// Epilogue variants gemm_nt_q8_kernel is built for: those it compiles without scratch.  GELU + residual and the fp32 residual stream
+// without a row scale spill 60-120 VGPRs around its longer live ranges and stay on gemm_nt_wide_persist_kernel; gelu' * aux is served
+// without column sums only (with them: the ring kernels; the caller may also take the bias gradient from the weight-gradient kernel).
+constexpr bool q8_ok(int epi, bool r, bool rs) { return (epi == 0 && (!r || rs)) || (epi == 1 && !r) || epi == 2 || (epi == 3 && rs); }
+// The bf16 residual without a row scale spills in q8 too (120 bytes per lane); the DropPath instantiation does not, and serves it with
+// this scale (x * 1.0f is exact).  So gemm_nt_wide_persist_kernel is never built for EPI 0.
+__device__ float g_gemm_one = 1.0f;
+constexpr bool wide_persist_ok(int epi, bool r, bool rs) { return epi != 0 && !q8_ok(epi, r, rs); }
 
 }  // namespace
 
@@ -1160,46 +819,66 @@ extern "C" void fiber_p2_probe(GemmArgs a, hipStream_t st) {
 }
 #else
 // C ABI ---------------------------------------------------------------------------------------------------------
-// Shape decision of the dispatcher, shared with fiber_gemm_row_tile (which sizes the caller's `colpart`: the two must not disagree).
-//   shape: 0 wide (256x256), 1 256x128, 2 128x128, 3 64x64, 4/5 register-staged 128x128 / 64x64;  -1: rejected
-// Tile choice.  256x256 (K step 32, two wave groups half a tile apart) whenever N is a multiple of 256 and there are
-// enough tiles; otherwise 256x128 / 128x128 / 64x64 on the 64-deep ring.  FIBER_GEMM_TILE / FIBER_GEMM_NOWIDE force a
-// choice for A/B runs (tools/gemm_ab.py).
-struct GemmPlan { int shape; bool persist; int persist_env, q8_env; };
+// The dispatcher's one decision: which kernel family serves a call, the row tile that implies (fiber_gemm_row_tile sizes the caller's
+// `colpart` by it) and the launch grid.
+enum GemmFamily { kRejected, kQ8, kWidePersist, kRing256x128, kRing128, kRing64, kReg128, kReg64 };
+struct GemmPlan { GemmFamily family; int rows; unsigned grid; };
+
+// 256x256 tiles from which the two persistent kernels take a call: about one per CU (q8 wins from there on: at 240 tiles
+// 31.5 -> 28.1 us, 97.5 -> 85.1 us at K = 3072)
+constexpr long kWideMinTiles = 200;
+
+// Tile choice.  256x256 whenever there are enough tiles, K >= 128 and N is a multiple of 256 -- of 64 where q8 serves the epilogue
+// (only q8 masks a partial tile column); otherwise 256x128 / 128x128 / 64x64 on the 64-deep ring, or register-staged where the
+// LDS-DMA kernels cannot go.  FIBER_GEMM_TILE / FIBER_GEMM_NOWIDE / FIBER_GEMM_V1 force a choice for A/B runs (tools/gemm_ab.py).
 static GemmPlan gemm_plan(int M, int N, int K, int ldy, int ldr, bool has_r, bool has_rs, bool colpart, int act) {
   static const int force = getenv("FIBER_GEMM_TILE") ? atoi(getenv("FIBER_GEMM_TILE")) : 0;
   static const int nowide = getenv("FIBER_GEMM_NOWIDE") ? atoi(getenv("FIBER_GEMM_NOWIDE")) : 0;
-  static const int persist_env = getenv("FIBER_GEMM_PERSIST") ? atoi(getenv("FIBER_GEMM_PERSIST")) : 1;
-  static const int persist_min = getenv("FIBER_GEMM_PERSIST_MIN") ? atoi(getenv("FIBER_GEMM_PERSIST_MIN")) : 200;
-  static const int q8_env = getenv("FIBER_GEMM_Q8") ? atoi(getenv("FIBER_GEMM_Q8")) : 1;   // 0: the v4 K loop (A/B runs)
+  static const int tile[8][2] = {{0, 0}, {256, 256}, {256, 256}, {256, 128}, {128, 128}, {64, 64}, {128, 128}, {64, 64}};   // by family
   const long big = (long)cdiv(M, 128) * cdiv(N, 128);
   const long huge = (long)cdiv(M, 256) * cdiv(N, 128);
   const long wide = (long)cdiv(M, 256) * cdiv(N, 256);
   const int mode = act & 0xff;
+  const int epi = (act & 0x800) ? 3 : (mode == 1 || mode == 2) ? mode : 0;     // the EPI the entry point instantiates
+  const bool trace = (act & 0x1000) != 0;                 // tools/gemm_trace.py: built for whole tile columns only
   const bool v2 = (K % 64 == 0) && (N % 8 == 0) && (ldy % 8 == 0) && (!has_r || ldr % 8 == 0) && !getenv("FIBER_GEMM_V1");
-  // will FIBER_LAUNCH_EPI pick gemm_nt_q8_kernel for this call?  (run-time mirror of kV4Ok and of the colpart exclusion)
-  const bool v4ok = (act & 0x800) ? has_rs : mode == 0 ? (!has_r || has_rs) : mode == 1 ? !has_r : mode == 2;
-  const bool q8_serves = persist_env == 1 && q8_env && wide >= persist_min && v4ok && !(mode == 2 && colpart) && !(act & 0x1600);
-  // (q8 wins from one tile per CU on: 240 tiles 31.5 -> 28.1 us, 97.5 -> 85.1 us at K = 3072)
-  GemmPlan p{-1, persist_env != 0 && wide >= persist_min, persist_env, q8_env};
+  const bool wide_ok = v2 && !nowide && force == 0 && wide >= kWideMinTiles && K >= 128;
+  const bool q8 = q8_ok(epi, has_r, has_rs) && !(epi == 2 && colpart) && !trace;
+  GemmFamily f;
   if (act & 0x100) {                                      // fp32 output: the register-staged kernels only
-    if (mode != 0 || has_r || colpart) return p;
-    p.shape = big >= 192 ? 4 : 5;
-  } else if (v2 && !nowide && force == 0 && wide >= 200 && K >= 128 && !(mode == 2 && !q8_serves) &&
-             (N % 256 == 0 || (N % 64 == 0 && N > 256 && q8_serves))) p.shape = 0;   // (only the q8 kernel masks a partial tile column; gelu' * aux
-                                                                                        //  with column sums / without q8: the 256x128 ring kernel)
-  else if (v2 && ((huge >= 400 && K >= 256 && force == 0) || force == 256)) p.shape = 1;
-  else if (big >= 192 || force == 128) p.shape = v2 ? 2 : 4;
-  else p.shape = v2 ? 3 : 5;
-  return p;
+    if (mode != 0 || has_r || colpart) return GemmPlan{kRejected, 0, 0};
+    f = big >= 192 ? kReg128 : kReg64;
+  } else if (wide_ok && q8 && (N % 256 == 0 || (N % 64 == 0 && N > 256))) f = kQ8;
+  else if (wide_ok && epi != 2 && N % 256 == 0) f = (epi == 0 || trace) ? kQ8 : kWidePersist;   // (EPI 0 here: residual without a row scale,
+                                                                                                  //  which q8 serves through g_gemm_one)
+  else if (v2 && ((huge >= 400 && K >= 256 && force == 0) || force == 256)) f = kRing256x128;
+  else if (big >= 192 || force == 128) f = v2 ? kRing128 : kReg128;
+  else f = v2 ? kRing64 : kReg64;
+  const bool persistent = f == kQ8 || f == kWidePersist;  // one workgroup per CU
+  return GemmPlan{f, tile[f][0], persistent ? 256u : (unsigned)(cdiv(M, tile[f][0]) * cdiv(N, tile[f][1]))};
 }
 
 // Row-tile height of the fused gelu' * aux column-sum call (act 2 with `colpart`, ldy = N) for an [M,N,K] problem: the rows of
 // `colpart` = ceil(M / tile).  0: the dispatcher rejects that call.
 extern "C" int fiber_gemm_row_tile(int M, int N, int K) {
-  static const int rows[6] = {256, 256, 128, 64, 128, 64};
-  const GemmPlan p = gemm_plan(M, N, K, N, 0, false, false, true, 2);
-  return p.shape < 0 ? 0 : rows[p.shape];
+  return gemm_plan(M, N, K, N, 0, false, false, true, 2).rows;
+}
+
+// One LDS-DMA launch.  Each (EPI, R, RS) instantiates the persistent kernels only where they are built for it; gemm_plan() pairs a
+// family with no other epilogue, and if it ever did the call is refused, not served by something else.
+template <int EPI, bool R, bool RS>
+static int launch_nt(const GemmPlan& p, const GemmArgs& a, hipStream_t stream) {
+  const dim3 grid(p.grid);
+  if (p.family == kQ8) {
+    if constexpr (q8_ok(EPI, R, RS)) hipLaunchKernelGGL((gemm_nt_q8_kernel<EPI, R, RS>), grid, dim3(512), 0, stream, a);
+    else return FIBER_EINVAL;
+  } else if (p.family == kWidePersist) {
+    if constexpr (wide_persist_ok(EPI, R, RS)) hipLaunchKernelGGL((gemm_nt_wide_persist_kernel<2, 4, EPI, R, RS>), grid, dim3(512), 0, stream, a);
+    else return FIBER_EINVAL;
+  } else if (p.family == kRing256x128) hipLaunchKernelGGL((gemm_nt_glds_kernel<256, 128, 4, 2, 3, EPI, R, RS>), grid, dim3(512), 0, stream, a);
+  else if (p.family == kRing128) hipLaunchKernelGGL((gemm_nt_glds_kernel<128, 128, 2, 2, 2, EPI, R, RS>), grid, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((gemm_nt_glds_kernel<64, 64, 2, 2, 2, EPI, R, RS>), grid, dim3(256), 0, stream, a);
+  return FIBER_OK;
 }
 
 // Y = rowscale * act(X.W^T + bias) + residual.  bias: fp32[N] or NULL; residual: bf16[M,ldr] or NULL; act: 0 none, 1 exact GELU;
@@ -1223,59 +902,28 @@ extern "C" int fiber_gemm_nt_bf16(const void* X, const void* W, const float* bia
   static const int stagger_env = getenv("FIBER_GEMM_STAGGER") ? atoi(getenv("FIBER_GEMM_STAGGER")) : 0;   // 1: round-3 barrier form (A/B runs)
   if (stagger_env) a.act |= 0x4000;
   if ((size_t)M * N * 2 > ((size_t)256 << 20)) a.act |= 0x2000;   // output larger than the last-level cache: streaming stores (gemm_epilogue.h st_out)
-  const long big = (long)cdiv(M, 128) * cdiv(N, 128);
-  const long huge = (long)cdiv(M, 256) * cdiv(N, 128);
-  const long wide = (long)cdiv(M, 256) * cdiv(N, 256);
   const int mode = act & 0xff;
   if ((mode == 2 || colpart) && !((K % 64 == 0) && (N % 8 == 0) && (ldy % 8 == 0))) return FIBER_EINVAL;   // LDS-DMA kernels only
   if (mode == 2 && residual) return FIBER_EINVAL;
   if ((act & 0x800) && (mode != 0 || !residual || !Ypre || colpart || (act & 0x100))) return FIBER_EINVAL;
-  if (colpart && mode != 2 && !(act & 0x1600)) return FIBER_EINVAL;
+  if (colpart && mode != 2 && !(act & 0x1000)) return FIBER_EINVAL;
   const GemmPlan plan = gemm_plan(M, N, K, ldy, ldr, residual != nullptr, rowscale != nullptr, colpart != nullptr, act);
-  if (plan.shape < 0) return FIBER_EINVAL;
-  const int shape = plan.shape;                          // 0 wide, 1 256x128, 2 128x128, 3 64x64, 4/5 register-staged
-  const bool persist = plan.persist;
-  const int persist_env = plan.persist_env, q8_env = plan.q8_env;
-  const long small = (long)cdiv(M, 64) * cdiv(N, 64);
-#define FIBER_LAUNCH_EPI(EPI, R, RS)                                                                                          \
-  do {                                                                                                                        \
-    if (shape == 0 && EPI == 2 && !(persist && q8_env && !a.colpart)) return FIBER_EINVAL;   /* (the pre-q8 kernels are not built for gelu' * aux: 104-168 B of scratch) */ \
-    if (shape == 0 && persist && persist_env == 2) hipLaunchKernelGGL((gemm_nt_wide_persist_kernel<2, 4, (EPI == 2 ? 0 : EPI), R, RS>), dim3(256), dim3(512), 0, stream, a); \
-    else if (shape == 0 && persist && q8_env && kV4Ok<EPI, R, RS> && !(EPI == 2 && a.colpart)) hipLaunchKernelGGL((gemm_nt_q8_kernel<kV4Ok<EPI, R, RS> ? EPI : 0, kV4Ok<EPI, R, RS> && R, RS>), dim3(256), dim3(512), 0, stream, a); \
-    else if (shape == 0 && persist && kV4Ok<EPI, R, RS> && !(EPI == 2 && a.colpart)) hipLaunchKernelGGL((gemm_nt_wide_persist2_kernel<2, 4, kV4Ok<EPI, R, RS> ? EPI : 0, kV4Ok<EPI, R, RS> && R, RS>), dim3(256), dim3(512), 0, stream, a); \
-    else if (shape == 0 && persist) hipLaunchKernelGGL((gemm_nt_wide_persist_kernel<2, 4, (EPI == 2 ? 0 : EPI), R, RS>), dim3(256), dim3(512), 0, stream, a); \
-    else if (shape == 0) hipLaunchKernelGGL((gemm_nt_wide_kernel<2, 4, (EPI == 2 ? 0 : EPI), R, RS>), dim3((unsigned)wide), dim3(512), 0, stream, a);   \
-    else if (shape == 1) hipLaunchKernelGGL((gemm_nt_glds_kernel<256, 128, 4, 2, 3, EPI, R, RS>), dim3((unsigned)huge), dim3(512), 0, stream, a); \
-    else if (shape == 2) hipLaunchKernelGGL((gemm_nt_glds_kernel<128, 128, 2, 2, 2, EPI, R, RS>), dim3((unsigned)big), dim3(256), 0, stream, a);  \
-    else hipLaunchKernelGGL((gemm_nt_glds_kernel<64, 64, 2, 2, 2, EPI, R, RS>), dim3((unsigned)small), dim3(256), 0, stream, a);                   \
-  } while (0)
-  if (shape == 0 && (act & 0x1000)) {                     // tools/gemm_trace.py q8: per-phase timing of the v5 kernel
+  if (plan.family == kRejected) return FIBER_EINVAL;
+  const dim3 grid(plan.grid);
+  int rc = FIBER_OK;
+  if (plan.family == kQ8 && (act & 0x1000)) {             // tools/gemm_trace.py q8: per-phase timing of the q8 kernel
     a.act &= 0x40ff;
-    if ((act & 0xff) == 1) hipLaunchKernelGGL((gemm_nt_q8_kernel<1, false, false, true>), dim3(256), dim3(512), 0, stream, a);
-    else hipLaunchKernelGGL((gemm_nt_q8_kernel<0, false, false, true>), dim3(256), dim3(512), 0, stream, a);
-    FIBER_CHECK_LAUNCH();
-    return FIBER_OK;
+    if (mode == 1) hipLaunchKernelGGL((gemm_nt_q8_kernel<1, false, false, true>), grid, dim3(512), 0, stream, a);
+    else hipLaunchKernelGGL((gemm_nt_q8_kernel<0, false, false, true>), grid, dim3(512), 0, stream, a);
   }
-  if (shape == 0 && (act & 0x400)) {                      // tools/gemm_trace.py persist: per-segment timing of the persistent kernel
-    a.act &= 0xff;
-    if ((act & 0xff) == 1) hipLaunchKernelGGL((gemm_nt_wide_persist2_kernel<2, 4, 1, false, false, true>), dim3(256), dim3(512), 0, stream, a);
-    else hipLaunchKernelGGL((gemm_nt_wide_persist2_kernel<2, 4, 0, false, false, true>), dim3(256), dim3(512), 0, stream, a);
-    FIBER_CHECK_LAUNCH();
-    return FIBER_OK;
-  }
-  if (shape == 0 && (act & 0x200)) {                      // tools/gemm_trace.py: per-segment timing build of the wide kernel
-    hipLaunchKernelGGL((gemm_nt_wide_kernel<2, 4, 0, false, false, true>), dim3((unsigned)wide), dim3(512), 0, stream, a);
-    FIBER_CHECK_LAUNCH();
-    return FIBER_OK;
-  }
-  if (shape == 4) hipLaunchKernelGGL((gemm_nt_kernel<128, 128>), dim3((unsigned)big), dim3(256), 0, stream, a);
-  else if (shape == 5) hipLaunchKernelGGL((gemm_nt_kernel<64, 64>), dim3((unsigned)small), dim3(256), 0, stream, a);
-  else if (act & 0x800) { if (rowscale) FIBER_LAUNCH_EPI(3, true, true); else FIBER_LAUNCH_EPI(3, true, false); }
-  else if (mode == 2) { if (rowscale) FIBER_LAUNCH_EPI(2, false, true); else FIBER_LAUNCH_EPI(2, false, false); }
-  else if (mode == 1 && residual) { if (rowscale) FIBER_LAUNCH_EPI(1, true, true); else FIBER_LAUNCH_EPI(1, true, false); }
-  else if (mode == 1) { if (rowscale) FIBER_LAUNCH_EPI(1, false, true); else FIBER_LAUNCH_EPI(1, false, false); }
-  else if (residual && rowscale) FIBER_LAUNCH_EPI(0, true, true);
-  else if (residual && shape == 0 && persist && persist_env == 1 && q8_env) {
+  else if (plan.family == kReg128) hipLaunchKernelGGL((gemm_nt_kernel<128, 128>), grid, dim3(256), 0, stream, a);
+  else if (plan.family == kReg64) hipLaunchKernelGGL((gemm_nt_kernel<64, 64>), grid, dim3(256), 0, stream, a);
+  else if (act & 0x800) rc = rowscale ? launch_nt<3, true, true>(plan, a, stream) : launch_nt<3, true, false>(plan, a, stream);
+  else if (mode == 2) rc = rowscale ? launch_nt<2, false, true>(plan, a, stream) : launch_nt<2, false, false>(plan, a, stream);
+  else if (mode == 1 && residual) rc = rowscale ? launch_nt<1, true, true>(plan, a, stream) : launch_nt<1, true, false>(plan, a, stream);
+  else if (mode == 1) rc = rowscale ? launch_nt<1, false, true>(plan, a, stream) : launch_nt<1, false, false>(plan, a, stream);
+  else if (residual && rowscale) rc = launch_nt<0, true, true>(plan, a, stream);
+  else if (residual && plan.family == kQ8) {
     // residual without DropPath (text-layer output projections, blocks with drop_path = 0) on the large-shape path: the q8 instantiation
     // for it spills 120 bytes per lane, the DropPath one does not -- run that one with a one-element scale of 1.0f (x * 1.0f is exact)
     // (a __device__ symbol has one address PER DEVICE: cached per device id, not per process)
@@ -1286,12 +934,12 @@ extern "C" int fiber_gemm_nt_bf16(const void* X, const void* W, const float* bia
     const float* one = one_of[dev];
     if (one == nullptr) return FIBER_ELAUNCH;
     a.rowscale = one; a.rows_per_sample = a.M;
-    FIBER_LAUNCH_EPI(0, true, true);
+    rc = launch_nt<0, true, true>(plan, a, stream);
   }
-  else if (residual) FIBER_LAUNCH_EPI(0, true, false);
-  else if (rowscale) FIBER_LAUNCH_EPI(0, false, true);
-  else FIBER_LAUNCH_EPI(0, false, false);
-#undef FIBER_LAUNCH_EPI
+  else if (residual) rc = launch_nt<0, true, false>(plan, a, stream);
+  else if (rowscale) rc = launch_nt<0, false, true>(plan, a, stream);
+  else rc = launch_nt<0, false, false>(plan, a, stream);
+  if (rc != FIBER_OK) return rc;
   FIBER_CHECK_LAUNCH();
   return FIBER_OK;
 }

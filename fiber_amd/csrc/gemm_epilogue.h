@@ -19,8 +19,8 @@ __device__ __forceinline__ int swz(int row, int chunk) { return (row * 8 + (chun
 // ---------------------------------------------------------------------------------------------------------------
 // Epilogue shared by the LDS-DMA kernels: accumulators -> LDS tile (bf16, in ROUNDS row slabs) -> coalesced 16-byte rows.
 // Everything that selects code is a template parameter: with the variants as run-time flags the unrolled store passes
-// compiled to ~560 instructions each and the epilogue of a 256x256 tile cost 7 us *without* its stores (ablation in
-// tools/gemm_dbg.py) -- as much as the tile's MFMAs at K = 512.
+// compiled to ~560 instructions each and the epilogue of a 256x256 tile cost 7 us *without* its stores (ablation recorded
+// in profiles/r01_summary.md) -- as much as the tile's MFMAs at K = 512.
 //   EPI 0: Y = rowscale * (acc + bias) + R          (HAS_RS / HAS_R)
 //   EPI 1: Ypre = acc + bias (optional);  Y = rowscale * gelu(bf16(acc + bias))
 //   EPI 3: EPI 0 on the fp32 RESIDUAL STREAM (HAS_R must be set): R is fp32 [M, ldr], the sum rowscale * (acc + bias) + R is

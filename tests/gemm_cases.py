@@ -12,7 +12,7 @@ Kernels (gemm.hip) and the shapes that select them:
   r64     gemm_nt_glds_kernel<64, 64>    fewer tiles
   reg128  gemm_nt_kernel<128, 128>       K % 64 != 0 or N % 8 != 0 (no LDS-DMA), >= 192 tiles; fp32 outputs
   reg64   gemm_nt_kernel<64, 64>         the same, fewer tiles
-gemm_nt_wide_persist2_kernel and gemm_nt_wide_kernel are only reached with FIBER_GEMM_Q8=0 / FIBER_GEMM_PERSIST=0 (A/B builds).
+These are all the NT GEMM kernels gemm.hip builds (the trace form of q8 apart: tools/gemm_trace.py).
 Every case has a ragged last row tile, a ragged last column tile where the kernel allows one, and a row-strided X (ldx > K)."""
 import torch
 

@@ -1,5 +1,5 @@
 """A/B of the hand-written GEMM at the bench shapes (2*B*L rows): run once per build / env setting and diff the lines.
-   python tools/gemm_ab.py [images=512]      env: FIBER_GEMM_PERSIST=0|1, FIBER_GEMM_TILE=..."""
+   python tools/gemm_ab.py [images=512]      env: FIBER_GEMM_NOWIDE=1, FIBER_GEMM_TILE=256|128|64"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,7 +24,7 @@ def timeit(fn, reps=10, warm=3):
 def main():
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 512
     lib.load()
-    print(f"PERSIST={os.environ.get('FIBER_GEMM_PERSIST', '1')} TILE={os.environ.get('FIBER_GEMM_TILE', '-')}")
+    print(f"NOWIDE={os.environ.get('FIBER_GEMM_NOWIDE', '0')} TILE={os.environ.get('FIBER_GEMM_TILE', '-')}")
     shapes = [("s1.fc1", B * 2304, 1024, 256), ("s1.fc2", B * 2304, 256, 1024), ("s2.qkv", B * 576, 1536, 512),
               ("s2.proj", B * 576, 512, 512), ("s2.fc1", B * 576, 2048, 512), ("s2.fc2", B * 576, 512, 2048),
               ("s3.fc1", B * 144, 4096, 1024), ("s3.fc2", B * 144, 1024, 4096)]

@@ -1,12 +1,12 @@
-"""NT GEMM timings at the shapes with 200..511 output tiles (text stack at B=256, stage 3, small batches): which kernel serves them
-is FIBER_GEMM_PERSIST_MIN (tiles from which the persistent q8 kernel is used; default 512)."""
+"""NT GEMM timings at the shapes with 200..511 output tiles (text stack at B=256, stage 3, small batches): the smallest the persistent
+q8 kernel serves (kWideMinTiles = 200 in csrc/gemm.hip; FIBER_GEMM_NOWIDE=1 sends them to the ring kernels for an A/B run)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from fiber_amd import lib, ops
 from tools.gemm_ab import timeit
 lib.load()
-print("PERSIST_MIN", os.environ.get("FIBER_GEMM_PERSIST_MIN", "512"))
+print("NOWIDE", os.environ.get("FIBER_GEMM_NOWIDE", "0"))
 for M, N, K in [(20480, 768, 768), (20480, 3072, 768), (20480, 768, 3072), (20480, 2304, 768), (73728, 1024, 1024), (73728, 3072, 1024),
                 (36864, 512, 512), (36864, 2048, 512), (36864, 1536, 512), (147456, 256, 256)]:
     x = torch.randn(M, K, device="cuda").to(torch.bfloat16)
