@@ -1,0 +1,269 @@
+// Grounding inference (gfx950): from VLDyHead's outputs to boxes without a host synchronisation.  Replaces, of the fine-grained reference
+// (fine_grained/maskrcnn_benchmark/), modeling/rpn/inference.py:620-650 + :741-795 (sigmoid, convert_grounding_to_od_logits[_v2], the
+// candidate test, the centerness product), :657-676 + modeling/box_coder.py:52-95 + BoxList.clip_to_image + remove_small_boxes (decode),
+// csrc/cuda/ml_nms.cu:15-75 (ml_nms_kernel) and the host loop ml_nms.cu:122-140 with select_over_all_levels (inference.py:717-738).
+// The reference's path synchronises per level and image (nonzero, a data-dependent topk, a boolean gather) and walks the N x N/64 mask on
+// the CPU; everything here has fixed shapes: padding entries carry score -1 and sink to the end of the per-image sort.
+// No atomics anywhere: two runs give the same bits.  IoU and decode are evaluated in the reference's operation order with contraction off.
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int DT = 256;                    // tokens (the only supported size)
+constexpr int SEL_WORDS = 4;               // removed-bitmap words per lane of the select kernel
+constexpr int SEL_MAX_N = 64 * 64 * SEL_WORDS;   // 16384 candidates per image (refcoco: 5 x 3000)
+constexpr int SRC_A_BITS = 18, SRC_C_BITS = 10;  // source = level << 28 | a << 10 | c
+
+// the one-exp sigmoid of ground.hip's focal_term: e = exp(-|z|), sigmoid(z) = (z >= 0 ? 1 : e) / (1 + e)
+__device__ __forceinline__ float sigmoid1(float z) {
+  const float e = __expf(-fabsf(z));
+  return (z >= 0.f ? 1.f : e) * __builtin_amdgcn_rcpf(1.f + e);
+}
+
+// One wave per anchor: the 256 token probabilities go through LDS, lane c (+64, ...) folds its class's tokens in CSR order.
+__global__ __launch_bounds__(256) void det_scores_kernel(const float* __restrict__ logits, const float* __restrict__ ctr,
+                                                         const int* __restrict__ class_ptr, const int* __restrict__ tok_idx,
+                                                         float* __restrict__ out, int A, int C, float thresh, int use_max) {
+  __shared__ __attribute__((aligned(16))) float prob[4][DT];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, b = blockIdx.y;
+  const int a = blockIdx.x * 4 + wave;
+  if (a >= A) return;                                      // whole wave; no workgroup barrier below
+  const size_t row = (size_t)b * A + a;
+  const f32x4 z = *reinterpret_cast<const f32x4*>(logits + row * DT + lane * 4);
+  f32x4 p;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) p[r] = sigmoid1(z[r]);
+  *reinterpret_cast<f32x4*>(&prob[wave][lane * 4]) = p;
+  const float cs = sigmoid1(ctr[row]);
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  for (int c = lane; c < C; c += 64) {
+    const int lo = class_ptr[c], hi = class_ptr[c + 1];
+    float agg = 0.f;
+    if (hi > lo) {
+      if (use_max) {
+        agg = prob[wave][tok_idx[lo]];
+        for (int i = lo + 1; i < hi; ++i) agg = fmaxf(agg, prob[wave][tok_idx[i]]);
+      } else {
+        for (int i = lo; i < hi; ++i) agg += prob[wave][tok_idx[i]];
+        agg = agg / (float)(hi - lo);
+      }
+    }
+    out[row * C + c] = agg > thresh ? agg * cs : -1.f;
+  }
+}
+
+__global__ __launch_bounds__(256) void det_decode_kernel(const float* __restrict__ val, const long long* __restrict__ idx,
+                                                         const float* __restrict__ reg, const float* __restrict__ anchors,
+                                                         const float* __restrict__ sizes, float* __restrict__ boxes,
+                                                         float* __restrict__ scores, int* __restrict__ labels, int* __restrict__ source,
+                                                         int k, int A, int C, int N, int off, int level, float min_size) {
+  const int j = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+  if (j >= k) return;
+  const float v = val[(size_t)b * k + j];
+  const long long flat = idx[(size_t)b * k + j];
+  const size_t o = (size_t)b * N + off + j;
+  f32x4 box = f32x4{0.f, 0.f, 0.f, 0.f};
+  float sc = -1.f;
+  int lab = 0, src = -1;
+  if (v >= 0.f && flat >= 0 && flat < (long long)A * C) {
+    const int a = (int)(flat / C), c = (int)(flat - (long long)a * C);
+    const f32x4 an = *reinterpret_cast<const f32x4*>(anchors + (size_t)a * 4);
+    const float* r = reg + (size_t)b * 4 * A + a;
+    const float w = an[2] - an[0] + 1.f, h = an[3] - an[1] + 1.f;
+    const float cx = an[0] + 0.5f * w, cy = an[1] + 0.5f * h;
+    const float clip = 4.135166556742356f;                 // log(1000 / 16)
+    const float dx = r[0] / 10.f, dy = r[A] / 10.f;
+    const float dw = fminf(r[2 * (size_t)A] / 5.f, clip), dh = fminf(r[3 * (size_t)A] / 5.f, clip);
+    const float px = dx * w + cx, py = dy * h + cy;
+    const float pw = expf(dw) * w, ph = expf(dh) * h;
+    const float iw = sizes[b * 2] - 1.f, ih = sizes[b * 2 + 1] - 1.f;
+    box[0] = fminf(fmaxf(px - 0.5f * pw, 0.f), iw);
+    box[1] = fminf(fmaxf(py - 0.5f * ph, 0.f), ih);
+    box[2] = fminf(fmaxf(px + 0.5f * pw - 1.f, 0.f), iw);
+    box[3] = fminf(fmaxf(py + 0.5f * ph - 1.f, 0.f), ih);
+    lab = c + 1;
+    src = (level << (SRC_A_BITS + SRC_C_BITS)) | (a << SRC_C_BITS) | c;
+    // remove_small_boxes: both sides (with the +1 of the xywh conversion) >= min_size; a NaN side fails the test
+    const bool big = (box[2] - box[0] + 1.f >= min_size) && (box[3] - box[1] + 1.f >= min_size);
+    sc = big ? sqrtf(v) : -1.f;
+  }
+  *reinterpret_cast<f32x4*>(boxes + o * 4) = box;
+  scores[o] = sc;
+  labels[o] = lab;
+  source[o] = src;
+}
+
+__device__ __forceinline__ float lane_bcast(float v, int l) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+}
+
+// One wave64 = rows [64 by, 64 by + 64) x columns [64 bx, 64 bx + 64): lane l holds row box l and column box l; for each row the
+// 64 compares are one per lane and the ballot is the row's word.  Word bit j of row i: j > i, same label, IoU > thresh, both live.
+__global__ __launch_bounds__(64) void det_nms_mask_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                          const int* __restrict__ labels, unsigned long long* __restrict__ mask, int N,
+                                                          float thresh) {
+  const int bx = blockIdx.x, by = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
+  if (bx < by) return;                                     // below the diagonal: never read by the select kernel
+  const int NB = gridDim.x;
+  const int ri = by * 64 + lane, ci = bx * 64 + lane;
+  const bool r_in = ri < N, c_in = ci < N;
+  const size_t rb = (size_t)b * N + (r_in ? ri : 0), cb = (size_t)b * N + (c_in ? ci : 0);
+  const f32x4 rbox = *reinterpret_cast<const f32x4*>(boxes + rb * 4);
+  const f32x4 cbox = *reinterpret_cast<const f32x4*>(boxes + cb * 4);
+  const int rlab = labels[rb], clab = labels[cb];
+  const bool r_ok = r_in && scores[rb] >= 0.f, c_ok = c_in && scores[cb] >= 0.f;
+  const float Sb = (cbox[2] - cbox[0] + 1.f) * (cbox[3] - cbox[1] + 1.f);
+  const unsigned long long rows_ok = __ballot(r_ok);
+  unsigned long long mine = 0ull;
+#pragma unroll 8
+  for (int r = 0; r < 64; ++r) {
+    const float a0 = lane_bcast(rbox[0], r), a1 = lane_bcast(rbox[1], r), a2 = lane_bcast(rbox[2], r), a3 = lane_bcast(rbox[3], r);
+    const int al = __builtin_amdgcn_readlane(rlab, r);
+    const float left = fmaxf(a0, cbox[0]), right = fminf(a2, cbox[2]);
+    const float top = fmaxf(a1, cbox[1]), bottom = fminf(a3, cbox[3]);
+    const float width = fmaxf(right - left + 1.f, 0.f), height = fmaxf(bottom - top + 1.f, 0.f);
+    const float inter = width * height;
+    const float Sa = (a2 - a0 + 1.f) * (a3 - a1 + 1.f);
+    const float iou = inter / (Sa + Sb - inter);
+    unsigned long long word = __ballot(c_ok && al == clab && iou > thresh);
+    if (bx == by) word &= r == 63 ? 0ull : ~0ull << (r + 1);
+    if (!((rows_ok >> r) & 1ull)) word = 0ull;
+    if (lane == r) mine = word;
+  }
+  if (r_in) mask[((size_t)b * N + ri) * NB + bx] = mine;
+}
+
+__device__ __forceinline__ unsigned long long lane_bcast64(unsigned long long v, int l) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// One wave per image walks the sorted candidates a block of 64 at a time.  Lane l owns removed-bitmap words l, l + 64, ... in registers.
+// A block's 64 diagonal mask words (row i, word i / 64) do not depend on any decision: the next block's are in flight while this block
+// is resolved on wave-uniform values.  The rows of the candidates just kept are then OR-ed into the words to the right.
+__global__ __launch_bounds__(64) void det_nms_select_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                            const int* __restrict__ labels, const int* __restrict__ source,
+                                                            const unsigned long long* __restrict__ mask, float* __restrict__ oboxes,
+                                                            float* __restrict__ oscores, int* __restrict__ olabels,
+                                                            int* __restrict__ osource, int* __restrict__ ocount, int N, int D) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int NB = (N + 63) >> 6;
+  const unsigned long long* M = mask + (size_t)b * N * NB;
+  unsigned long long remv[SEL_WORDS];
+#pragma unroll
+  for (int s = 0; s < SEL_WORDS; ++s) remv[s] = 0ull;
+  int count = 0;
+  unsigned long long diag_next = lane < N ? M[(size_t)lane * NB] : 0ull;
+  for (int nb = 0; nb < NB && count < D; ++nb) {
+    const int i = nb * 64 + lane;
+    const unsigned long long diag = diag_next;
+    {
+      const int in = i + 64;
+      diag_next = (nb + 1 < NB && in < N) ? M[(size_t)in * NB + nb + 1] : 0ull;
+    }
+    const float sc = i < N ? scores[(size_t)b * N + i] : -1.f;
+    const unsigned long long valid = __ballot(sc >= 0.f);
+    if (valid == 0ull) break;                              // sorted: nothing but padding from here on
+    unsigned long long own = 0ull;
+#pragma unroll
+    for (int s = 0; s < SEL_WORDS; ++s) own = (nb >> 6) == s ? remv[s] : own;
+    unsigned long long cur = lane_bcast64(own, nb & 63) | ~valid;
+    unsigned long long keep = 0ull;
+    for (int l = 0; l < 64 && count < D; ++l) {
+      if ((cur >> l) & 1ull) continue;
+      keep |= 1ull << l;
+      ++count;
+      cur |= lane_bcast64(diag, l);
+    }
+    if ((keep >> lane) & 1ull) {
+      const int rank = count - __popcll(keep) + __popcll(keep & ((1ull << lane) - 1ull));
+      const size_t src = (size_t)b * N + i, dst = (size_t)b * D + rank;
+      *reinterpret_cast<f32x4*>(oboxes + dst * 4) = *reinterpret_cast<const f32x4*>(boxes + src * 4);
+      oscores[dst] = sc;
+      olabels[dst] = labels[src];
+      osource[dst] = source[src];
+    }
+    for (unsigned long long m = keep; m; m &= m - 1ull) {
+      const size_t row = (size_t)(nb * 64 + __builtin_ctzll(m)) * NB;
+#pragma unroll
+      for (int s = 0; s < SEL_WORDS; ++s) {
+        const int w = s * 64 + lane;
+        if (w > nb && w < NB) remv[s] |= M[row + w];
+      }
+    }
+  }
+  for (int d = count + lane; d < D; d += 64) {
+    const size_t dst = (size_t)b * D + d;
+    *reinterpret_cast<f32x4*>(oboxes + dst * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+    oscores[dst] = -1.f;
+    olabels[dst] = 0;
+    osource[dst] = -1;
+  }
+  if (lane == 0) ocount[b] = count;
+}
+
+}  // namespace
+
+// Largest N (candidates per image after the per-level top-k) the select kernel's register bitmap holds
+extern "C" int fiber_det_max_candidates(void) { return SEL_MAX_N; }
+
+extern "C" int fiber_det_scores_f32(const float* logits, const float* centerness, const int* class_ptr, const int* tok_idx, float* out,
+                                    int B, int A, int T, int C, float pre_nms_thresh, int agg_max, hipStream_t stream) {
+  if (T != DT || C <= 0 || B < 0 || A < 0) return FIBER_EINVAL;
+  if (B == 0 || A == 0) return FIBER_OK;
+  if (!logits || !centerness || !class_ptr || !tok_idx || !out) return FIBER_EINVAL;
+  if (fiber_misaligned(16, logits) || fiber_misaligned(4, centerness, class_ptr, tok_idx, out)) return FIBER_EINVAL;
+  hipLaunchKernelGGL(det_scores_kernel, dim3(cdiv(A, 4), B), dim3(256), 0, stream, logits, centerness, class_ptr, tok_idx, out, A, C,
+                     pre_nms_thresh, agg_max);
+  FIBER_CHECK_LAUNCH();
+  return FIBER_OK;
+}
+
+extern "C" int fiber_det_decode_f32(const float* topk_val, const long long* topk_idx, const float* bbox_reg, const float* anchors,
+                                    const float* image_sizes, float* boxes, float* scores, int* labels, int* source, int B, int k, int A,
+                                    int C, int N, int offset, int level, float min_size, hipStream_t stream) {
+  if (C <= 0 || C > (1 << SRC_C_BITS) || A < 0 || A > (1 << SRC_A_BITS) || level < 0 || level >= 8 || B < 0 || k < 0 || N < 0 ||
+      offset < 0 || (long long)offset + k > N)
+    return FIBER_EINVAL;
+  if (B == 0 || k == 0) return FIBER_OK;
+  if (!topk_val || !topk_idx || !bbox_reg || !anchors || !image_sizes || !boxes || !scores || !labels || !source) return FIBER_EINVAL;
+  if (fiber_misaligned(16, anchors, boxes) || fiber_misaligned(8, topk_idx) ||
+      fiber_misaligned(4, topk_val, bbox_reg, image_sizes, scores, labels, source))
+    return FIBER_EINVAL;
+  hipLaunchKernelGGL(det_decode_kernel, dim3(cdiv(k, 256), B), dim3(256), 0, stream, topk_val, topk_idx, bbox_reg, anchors, image_sizes,
+                     boxes, scores, labels, source, k, A, C, N, offset, level, min_size);
+  FIBER_CHECK_LAUNCH();
+  return FIBER_OK;
+}
+
+extern "C" int fiber_det_nms_mask(const float* boxes, const float* scores, const int* labels, unsigned long long* mask, int B, int N,
+                                  float nms_thresh, hipStream_t stream) {
+  if (B < 0 || N < 0 || N > SEL_MAX_N || B > 65535) return FIBER_EINVAL;
+  if (B == 0 || N == 0) return FIBER_OK;
+  if (!boxes || !scores || !labels || !mask) return FIBER_EINVAL;
+  if (fiber_misaligned(16, boxes) || fiber_misaligned(8, mask) || fiber_misaligned(4, scores, labels)) return FIBER_EINVAL;
+  const int NB = cdiv(N, 64);
+  hipLaunchKernelGGL(det_nms_mask_kernel, dim3(NB, NB, B), dim3(64), 0, stream, boxes, scores, labels, mask, N, nms_thresh);
+  FIBER_CHECK_LAUNCH();
+  return FIBER_OK;
+}
+
+extern "C" int fiber_det_nms_select(const float* boxes, const float* scores, const int* labels, const int* source,
+                                    const unsigned long long* mask, float* out_boxes, float* out_scores, int* out_labels,
+                                    int* out_source, int* out_count, int B, int N, int D, hipStream_t stream) {
+  if (B < 0 || N < 0 || N > SEL_MAX_N || D <= 0) return FIBER_EINVAL;
+  if (B == 0 || N == 0) return FIBER_OK;
+  if (!boxes || !scores || !labels || !source || !mask || !out_boxes || !out_scores || !out_labels || !out_source || !out_count)
+    return FIBER_EINVAL;
+  if (fiber_misaligned(16, boxes, out_boxes) || fiber_misaligned(8, mask) ||
+      fiber_misaligned(4, scores, labels, source, out_scores, out_labels, out_source, out_count))
+    return FIBER_EINVAL;
+  hipLaunchKernelGGL(det_nms_select_kernel, dim3(B), dim3(64), 0, stream, boxes, scores, labels, source, mask, out_boxes, out_scores,
+                     out_labels, out_source, out_count, N, D);
+  FIBER_CHECK_LAUNCH();
+  return FIBER_OK;
+}

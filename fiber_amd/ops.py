@@ -2036,3 +2036,67 @@ def ground_token_loss(x, p, tbias, log_scale, targets, text_mask=None, alpha=0.2
     t8 = _c(targets if targets.dtype == torch.uint8 else (targets != 0).to(torch.uint8))
     m8 = torch.ones(p.shape[:2], dtype=torch.uint8, device=x.device) if text_mask is None else _c((text_mask > 0).to(torch.uint8))
     return _GroundTokenLoss.apply(x, p, tbias, log_scale, t8, m8, alpha, gamma)
+
+
+# ---- grounding inference: scores, decode, multi-label NMS (csrc/detect.hip); inference only, no autograd ----------------------------
+def _det_f32(t):
+    return _c(t.detach().float())
+
+
+def det_scores(logits, centerness, class_ptr, tok_idx, pre_nms_thresh, score_agg="MEAN"):
+    """Dense class scores of one level (inference.py:620-650, :741-795): logits fp32 [B, A, 256] and centerness [B, 1, H, W] as
+    VLDyHead.forward returns them, the positive map as CSR (int32 class_ptr [C + 1], tok_idx [nnz]).  -> fp32 [B, A, C]:
+    agg * sigmoid(centerness) where agg > pre_nms_thresh, -1 elsewhere."""
+    if score_agg not in ("MEAN", "MAX"):
+        raise NotImplementedError(f"det_scores: score_agg {score_agg!r} (MEAN and MAX are built)")
+    B, A, T = logits.shape
+    C = class_ptr.numel() - 1
+    if centerness.numel() != B * A or class_ptr.dtype != torch.int32 or tok_idx.dtype != torch.int32:
+        raise ValueError(f"det_scores: logits {tuple(logits.shape)}, centerness {tuple(centerness.shape)}, CSR {class_ptr.dtype} / {tok_idx.dtype}")
+    lg, ct = _det_f32(logits), _det_f32(centerness)
+    out = torch.empty((B, A, C), dtype=torch.float32, device=logits.device)
+    lib.call("fiber_det_scores_f32", lib.ptr(lg), lib.ptr(ct), lib.ptr(_c(class_ptr)), lib.ptr(_c(tok_idx)), lib.ptr(out), B, A, T, C,
+             float(pre_nms_thresh), int(score_agg == "MAX"))
+    return out
+
+
+def det_decode(topk_val, topk_idx, bbox_reg, anchors, image_sizes, out, offset, level, num_classes, min_size=0.0):
+    """Decode one level's top-k into the slice [offset, offset + k) of the concatenated buffers out = (boxes [B, N, 4] fp32, scores
+    [B, N] fp32, labels [B, N] int32, source [B, N] int32) in place (inference.py:657-676, box_coder.py:52-95, clip_to_image,
+    remove_small_boxes).  bbox_reg fp32 [B, 4, H, W] is read in place; anchors [H * W, 4]; image_sizes fp32 [B, 2] as (w, h)."""
+    boxes, scores, labels, source = out
+    B, k = topk_val.shape
+    A = anchors.shape[0]
+    N = scores.shape[1]
+    if bbox_reg.shape[0] != B or bbox_reg.numel() != B * 4 * A or topk_idx.dtype != torch.int64 or image_sizes.shape != (B, 2):
+        raise ValueError(f"det_decode: bbox_reg {tuple(bbox_reg.shape)} for {A} anchors, topk_idx {topk_idx.dtype}, sizes {tuple(image_sizes.shape)}")
+    for t, dt in ((boxes, torch.float32), (scores, torch.float32), (labels, torch.int32), (source, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError("det_decode: the output buffers are contiguous fp32 / fp32 / int32 / int32")
+    lib.call("fiber_det_decode_f32", lib.ptr(_det_f32(topk_val)), lib.ptr(_c(topk_idx)), lib.ptr(_det_f32(bbox_reg)),
+             lib.ptr(_det_f32(anchors)), lib.ptr(_det_f32(image_sizes)), lib.ptr(boxes), lib.ptr(scores), lib.ptr(labels), lib.ptr(source),
+             B, k, A, int(num_classes), N, int(offset), int(level), float(min_size))
+
+
+def nms_ml(boxes, scores, labels, source, nms_thresh, detections_per_img):
+    """Multi-label NMS of candidates ALREADY SORTED by descending score per image (ml_nms.cu; padding = score < 0 at the end) and the
+    cut to detections_per_img (select_over_all_levels).  boxes [B, N, 4], scores [B, N] fp32, labels / source [B, N] int32.
+    -> (boxes [B, D, 4], scores [B, D], labels [B, D], source [B, D], count [B]); no host synchronisation."""
+    B, N = scores.shape
+    D = int(detections_per_img)
+    dev = scores.device
+    if B == 0 or N == 0:                                     # no launch: the padding the select kernel would have written
+        return (torch.zeros((B, D, 4), dtype=torch.float32, device=dev), torch.full((B, D), -1.0, dtype=torch.float32, device=dev),
+                torch.zeros((B, D), dtype=torch.int32, device=dev), torch.full((B, D), -1, dtype=torch.int32, device=dev),
+                torch.zeros((B,), dtype=torch.int32, device=dev))
+    ob = torch.empty((B, D, 4), dtype=torch.float32, device=dev)   # the select kernel writes every element, past count included
+    osc = torch.empty((B, D), dtype=torch.float32, device=dev)
+    ol, osr = torch.empty((B, D), dtype=torch.int32, device=dev), torch.empty((B, D), dtype=torch.int32, device=dev)
+    cnt = torch.empty((B,), dtype=torch.int32, device=dev)
+    bx, sc = _det_f32(boxes), _det_f32(scores)
+    lb, sr = _c(labels.to(torch.int32)), _c(source.to(torch.int32))
+    mask = torch.empty((B, N, (N + 63) // 64), dtype=torch.int64, device=dev)
+    lib.call("fiber_det_nms_mask", lib.ptr(bx), lib.ptr(sc), lib.ptr(lb), lib.ptr(mask), B, N, float(nms_thresh))
+    lib.call("fiber_det_nms_select", lib.ptr(bx), lib.ptr(sc), lib.ptr(lb), lib.ptr(sr), lib.ptr(mask), lib.ptr(ob), lib.ptr(osc),
+             lib.ptr(ol), lib.ptr(osr), lib.ptr(cnt), B, N, D)
+    return ob, osc, ol, osr, cnt

@@ -298,6 +298,36 @@ int fiber_ground_bwd_bf16(const void* X, const void* P, const float* tbias, cons
                           const unsigned char* text_mask, const float* g, void* ds, float* dtbias, float* dlog_scale, float* workspace,
                           int B, int A, int T, int C, float alpha, float gamma, fiber_stream_t stream);
 
+/* Grounding inference: VLDyHead's outputs -> boxes with fixed shapes and no host synchronisation (csrc/detect.hip); file:line relative to
+ * the reference's fine_grained/maskrcnn_benchmark/.  No atomics: two runs give the same bits.  T = 256 only; NULL or misaligned pointers,
+ * C <= 0 and N > fiber_det_max_candidates() -> 1; B == 0 or N == 0 -> 0 without a launch.
+ * fiber_det_scores_f32 replaces modeling/rpn/inference.py:620-650 and :741-795 (sigmoid, convert_grounding_to_od_logits[_v2] MEAN / MAX, the
+ * candidate test, the centerness product): logits fp32 [B,A,T] and centerness fp32 [B,1,H,W] (= [B,A]) as the head returns them, the positive
+ * map as CSR (class_ptr int32 [C+1], tok_idx int32 [nnz], token sets may overlap, an empty class scores 0); out fp32 [B,A,C] =
+ * agg * sigmoid(ctr) where agg > pre_nms_thresh (tested BEFORE the centerness product) and -1 elsewhere; agg_max 0 = MEAN, 1 = MAX.
+ * fiber_det_decode_f32 replaces inference.py:657-676, modeling/box_coder.py:52-95 (weights 10,10,5,5, log(1000/16) clamp, TO_REMOVE 1),
+ * structures/bounding_box.py:214-225 (clip_to_image) and structures/boxlist_ops.py:77-91 (remove_small_boxes): one level's top-k
+ * (topk_val fp32 [B,k], topk_idx int64 [B,k] into [A*C], val < 0 = padding), bbox_reg fp32 [B,4,H,W] read in place, anchors fp32 [A,4],
+ * image_sizes fp32 [B,2] (w,h) -> the slice [offset, offset+k) of boxes fp32 [B,N,4], scores (sqrt; -1 for padding and small boxes),
+ * labels int32 (c+1), source int32 (level << 28 | a << 10 | c; -1 for padding).  level < 8, A <= 2^18, C <= 2^10.
+ * fiber_det_nms_mask replaces csrc/cuda/ml_nms.cu:15-75 (devIoU with the +1 convention in its operation order, label-aware, strict >) on
+ * candidates sorted by score: mask uint64 [B,N,ceil(N/64)], bit j of row i set iff j > i, same label, IoU > thresh, both scores >= 0.
+ * Only words on or right of the diagonal block are written.
+ * fiber_det_nms_select replaces the host loop ml_nms.cu:122-140 and select_over_all_levels inference.py:717-738: walks each image's sorted
+ * candidates, stops at D kept; out_boxes fp32 [B,D,4], out_scores [B,D] (-1 past count), out_labels, out_source int32 [B,D], out_count
+ * int32 [B].  Deviation: the reference keeps every score >= the kthvalue cut, i.e. more than D on an exact tie at the cut. */
+int fiber_det_max_candidates(void);
+int fiber_det_scores_f32(const float* logits, const float* centerness, const int* class_ptr, const int* tok_idx, float* out, int B, int A,
+                         int T, int C, float pre_nms_thresh, int agg_max, fiber_stream_t stream);
+int fiber_det_decode_f32(const float* topk_val, const long long* topk_idx, const float* bbox_reg, const float* anchors,
+                         const float* image_sizes, float* boxes, float* scores, int* labels, int* source, int B, int k, int A, int C, int N,
+                         int offset, int level, float min_size, fiber_stream_t stream);
+int fiber_det_nms_mask(const float* boxes, const float* scores, const int* labels, unsigned long long* mask, int B, int N, float nms_thresh,
+                       fiber_stream_t stream);
+int fiber_det_nms_select(const float* boxes, const float* scores, const int* labels, const int* source, const unsigned long long* mask,
+                         float* out_boxes, float* out_scores, int* out_labels, int* out_source, int* out_count, int B, int N, int D,
+                         fiber_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
