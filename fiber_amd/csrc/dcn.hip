@@ -148,8 +148,8 @@ __global__ __launch_bounds__(256) void dcn_scatter_kernel(DcnP p, const bf16* dc
 //   LDS accumulation is FIXED POINT on ds_add_u32: float LDS atomics (ds_add_f32) serialise per lane on this part (the same
 //   kernel: 3.3 ms with them, 0.89 with integer atomics, 0.78 with racy plain adds).  Scale 2^(19-e) with 2^e > max |dcol| (a
 //   small reduction kernel): one contribution is < 2^19 in magnitude and the bilinear weights of a sample sum to <= 1, so a
-//   window cell receives at most T*T*taps = 2304 full-size contributions < 2^31 -- no overflow for any input; resolution
-//   2^-19 of the largest column gradient per contribution (bf16 keeps 2^-9 of each value).
+//   window cell receives at most T*T*taps = 2304 full-size contributions < 2^31 -- no overflow for any input (the up to four windows
+//   over one pixel are added in 64 bits); resolution 2^-19 of the largest column gradient per contribution (bf16 keeps 2^-9 of each value).
 constexpr int DCN_CS = 16, DCN_WIN = 24;   // window = T*stride + (k - 1) + halo = 24 for (T 16, stride 1) and (T 8, stride 2), k = 3
 constexpr int DCN_HALO = 3;
 
@@ -169,11 +169,12 @@ __global__ __launch_bounds__(256) void absmax_bf16_kernel(const bf16* v, long n8
   if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(out, __float_as_uint(m));
 }
 
-__device__ __forceinline__ float dcn_fixed_scale(unsigned maxbits) {
-  // 2^(19 - e), 2^e > max: the exponent field of max gives floor(log2 max) = E - 127
+// k with 2^k = 2^(19 - e) the fixed-point scale, 2^e > max strictly: e = floor(log2 max) + 1.  An exponent, applied with ldexpf, because
+// the scale itself leaves fp32 at both ends (2^146 and more for a denormal maximum); a denormal's floor(log2) is its leading mantissa bit.
+__device__ __forceinline__ int dcn_fixed_exp(unsigned maxbits) {
   const int E = (int)(maxbits >> 23);
-  const int ef = min(max(127 + 19 - (E - 127 + 1), 1), 254);      // clamped: a denormal maximum would ask for 2^146
-  return maxbits ? __uint_as_float((unsigned)ef << 23) : 1.f;
+  const int fl = E ? E - 127 : 31 - __clz((int)maxbits) - 149;
+  return maxbits ? 19 - (fl + 1) : 0;
 }
 
 __global__ __launch_bounds__(256) void dcn_dx_tile_kernel(DcnP p, DcnT g, const bf16* dcols, int* tiles, float* far, const unsigned* maxbits) {
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(256) void dcn_dx_tile_kernel(DcnP p, DcnT g, const 
   const int tile = blockIdx.x / nslice;
   const int tx = tile % g.tiles_x, ty = (tile / g.tiles_x) % g.tiles_y, b = tile / (g.tiles_x * g.tiles_y);
   const int y0 = ty * g.T * p.stride - p.pad - DCN_HALO, x0 = tx * g.T * p.stride - p.pad - DCN_HALO;
-  const float scale = dcn_fixed_scale(*maxbits);
+  const int sexp = dcn_fixed_exp(*maxbits);
   for (int i = threadIdx.x; i < DCN_WIN * DCN_WIN * DCN_CS / 4; i += 256) reinterpret_cast<int4*>(win)[i] = int4{0, 0, 0, 0};
   __syncthreads();
   const int grp = threadIdx.x >> 2, l4 = threadIdx.x & 3;                                   // 4 lanes x 4 channels per (position, tap)
@@ -204,6 +205,9 @@ __global__ __launch_bounds__(256) void dcn_dx_tile_kernel(DcnP p, DcnT g, const 
     const float hh = 1.f - q.lh, hw = 1.f - q.lw;
     const float wt[4] = {hh * hw * mk, hh * q.lw * mk, q.lh * hw * mk, q.lh * q.lw * mk};
     const bool ok[4] = {q.v00, q.v01, q.v10, q.v11};
+    float ds[4];                                                                              // the column gradients in fixed-point units (exact)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ds[e] = ldexpf(bf2f(d[e]), sexp);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       if (!ok[c]) continue;
@@ -212,7 +216,7 @@ __global__ __launch_bounds__(256) void dcn_dx_tile_kernel(DcnP p, DcnT g, const 
       if ((unsigned)ry < (unsigned)DCN_WIN && (unsigned)rx < (unsigned)DCN_WIN) {
         int* dst = win + (ry * DCN_WIN + rx) * DCN_CS + l4 * 4;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) atomicAdd(dst + e, __float2int_rn(wt[c] * bf2f(d[e]) * scale));   // ds_add_u32
+        for (int e = 0; e < 4; ++e) atomicAdd(dst + e, __float2int_rn(wt[c] * ds[e]));   // ds_add_u32
       } else {
         float* dst = far + (((long)b * p.H + yy) * p.W + xx) * p.C + cs * DCN_CS + l4 * 4;
 #pragma unroll
@@ -231,12 +235,12 @@ __global__ __launch_bounds__(256) void dcn_dx_tile_kernel(DcnP p, DcnT g, const 
 // dx[b,y,x,c] = far + (sum of the windows covering (y,x)) / scale; one thread = 8 channels of one pixel
 __global__ __launch_bounds__(256) void dcn_dx_sum_kernel(DcnP p, DcnT g, const int* tiles, const float* far, bf16* dx, long total, const unsigned* maxbits) {
   const int C8 = p.C >> 3, span = g.T * p.stride;
-  const float inv = 1.f / dcn_fixed_scale(*maxbits);
+  const int sexp = dcn_fixed_exp(*maxbits);
   for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
     const int c8 = (int)(idx % C8);
     const long pix = idx / C8;
     const int x = (int)(pix % p.W), y = (int)((pix / p.W) % p.H), b = (int)(pix / ((long)p.W * p.H));
-    int acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // 64 bits: a pixel under four windows can receive 4 x 2304 full-size contributions
     const int ay = y + p.pad + DCN_HALO, ax = x + p.pad + DCN_HALO;          // window-relative coordinate + tile origin
     const int ty_hi = min(ay / span, g.tiles_y - 1), tx_hi = min(ax / span, g.tiles_x - 1);
     for (int ty = ty_hi; ty >= 0 && ay - ty * span < DCN_WIN; --ty)
@@ -250,7 +254,7 @@ __global__ __launch_bounds__(256) void dcn_dx_sum_kernel(DcnP p, DcnT g, const i
     const float fr[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
     bf16x8 o;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = f2bf(fr[e] + (float)acc[e] * inv);
+    for (int e = 0; e < 8; ++e) o[e] = f2bf(fr[e] + ldexpf((float)acc[e], -sexp));
     *reinterpret_cast<bf16x8*>(dx + pix * p.C + c8 * 8) = o;
   }
 }
