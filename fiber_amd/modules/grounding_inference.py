@@ -288,7 +288,7 @@ def make_atss_postprocessor(config, box_coder, is_train=False):
 
 
 class VLDyHeadModule(nn.Module):
-    """vldyhead.py:917-1155, eval side: head (checkpoint keys `head.*`) + anchors + box selector."""
+    """vldyhead.py:917-1155: head (checkpoint keys `head.*`) + anchors + box selector (eval) / loss evaluator (training with targets)."""
 
     def __init__(self, cfg):
         super().__init__()
@@ -298,13 +298,30 @@ class VLDyHeadModule(nn.Module):
         self.anchor_generator = make_anchor_generator_complex(cfg)
         if any(n != 1 for n in self.anchor_generator.num_anchors_per_location()):
             raise NotImplementedError(f"VLDyHeadModule: {_UNSUPPORTED['num_anchors']}")
+        self._loss_evaluator = None                          # grounding_train.ATSSLossComputation, built by the first training step
 
-    def forward(self, image_sizes, features, language_dict_features, positive_map):
-        """image_sizes: [(h, w)] per image as ImageList.image_sizes, or a [B, 2] tensor of (w, h); features: the FPN levels
+    def _train(self, features, language_dict_features, targets):
+        """vldyhead.py:1022-1105 with RPN_ONLY: the reference's loss dict; targets: grounding_train.GroundingTargets on the device."""
+        from .grounding_train import ATSSLossComputation
+        if self._loss_evaluator is None:
+            self._loss_evaluator = ATSSLossComputation(self.cfg)
+        h = self.head
+        logits, bbox_reg, centerness, q, proj, tbias = h.training_outputs(features, language_dict_features["embedded"])
+        cls, reg, ctr, token = self._loss_evaluator(logits, bbox_reg, centerness, targets, self.anchor_generator(features), q, proj, tbias,
+                                                    h.log_scale, language_dict_features.get("masks"))
+        w = getattr(self.cfg.MODEL.DYHEAD.FUSE_CONFIG, "DOT_PRODUCT_TOKEN_LOSS_WEIGHT", 1.0)
+        return {"loss_reg": reg, "loss_centerness": ctr, "loss_cls": cls, "loss_dot_product_token": token * w}
+
+    def forward(self, image_sizes, features, language_dict_features, positive_map=None, targets=None):
+        """Training mode with `targets`: -> {"loss_reg", "loss_centerness", "loss_cls", "loss_dot_product_token"} (image_sizes and
+        positive_map are not read: the anchors do not depend on the image and the targets carry their positive map).  Eval: image_sizes: [(h, w)] per image as ImageList.image_sizes, or a [B, 2] tensor of (w, h); features: the FPN levels
         [B, C, H, W]; language_dict_features["embedded"]: [B, 256, LANG_DIM].  -> Detections.  A list of sizes is copied to the device
         here (a host-to-device copy per call); pass the tensor, already on the device, to avoid it or to capture the call in a graph."""
         if self.training:
-            raise NotImplementedError("VLDyHeadModule is the inference side: train the head with VLDyHead.token_loss (module.head.token_loss)")
+            if targets is None:
+                raise NotImplementedError("VLDyHeadModule in training mode needs targets= (grounding_train.pack_targets); without them "
+                                          "it is the inference side")
+            return self._train(features, language_dict_features, targets)
         dev = features[0].device
         if not torch.is_tensor(image_sizes):
             image_sizes = torch.tensor([[float(w), float(h)] for h, w in image_sizes], dtype=torch.float32)

@@ -172,6 +172,19 @@ class VLDyHead(nn.Module):
             dot_product_logits.append(ops.ground_logits(q, proj, tbias, self.log_scale))
         return logits, bbox_reg, centerness, None, None, None, dot_product_logits, None, None, fused
 
+    def training_outputs(self, x, embedding):
+        """What training needs from ONE run of the tower (grounding_train.ATSSLossComputation): the per-level cls_logits, bbox_reg and
+        centerness, all levels' anchor features concatenated [B, sum HW, C], the projected tokens and the token bias.  The alignment
+        logits are never materialised."""
+        self._clamped()
+        tower = self.dyhead_tower({"visual": x, "lang": None})["visual"]
+        proj, tbias = self._tokens(embedding)
+        logits = [self.cls_logits(f) for f in tower]
+        bbox_reg = [self.scales[l](self.bbox_pred(f)) for l, f in enumerate(tower)]
+        centerness = [self.centerness(f) for f in tower]
+        q = torch.cat([permute_and_flatten(f, f.shape[0], -1, f.shape[1], f.shape[2], f.shape[3]) for f in tower], dim=1)
+        return logits, bbox_reg, centerness, q, proj, tbias
+
     def token_loss(self, x, embedding, targets, text_masks, num_pos, alpha=None, gamma=None):
         """Training entry point (modeling/rpn/loss.py:1222-1226): tower -> all levels' anchors concatenated [B, sum HW, C] ->
         ops.ground_token_loss / num_pos.  targets [B, sum HW, T] in the level order of `x`; the logits are never materialised.

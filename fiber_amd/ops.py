@@ -2100,3 +2100,123 @@ def nms_ml(boxes, scores, labels, source, nms_thresh, detections_per_img):
     lib.call("fiber_det_nms_select", lib.ptr(bx), lib.ptr(sc), lib.ptr(lb), lib.ptr(sr), lib.ptr(mask), lib.ptr(ob), lib.ptr(osc),
              lib.ptr(ol), lib.ptr(osr), lib.ptr(cnt), B, N, D)
     return ob, osc, ol, osr, cnt
+
+
+# ---- grounding training: ATSS assignment + GIoU / centerness losses (csrc/atss.hip) --------------------------------------------------
+class Assignment:
+    """ops.atss_assign's result, fixed shapes: matched int32 [B, A] (-1 unassigned), labels int32 [B, A] (0), reg_targets fp32 [B, A, 4]
+    (0), token_targets uint8 [B, A, T] (unassigned: the one-hot on token T - 1), num_pos int32 [B]; anchors fp32 [A, 4] (the levels
+    concatenated) and level_off (host list of L + 1 offsets) travel along for the losses."""
+
+    def __init__(self, matched, labels, reg_targets, token_targets, num_pos, anchors, level_off):
+        self.matched, self.labels, self.reg_targets, self.token_targets, self.num_pos = matched, labels, reg_targets, token_targets, num_pos
+        self.anchors, self.level_off = anchors, level_off
+
+
+def _level_offsets(anchors_per_level):
+    off = [0]
+    for a in anchors_per_level:
+        if a.dim() != 2 or a.shape[1] != 4:
+            raise ValueError(f"atss: anchors of a level are [A_l, 4], got {tuple(a.shape)}")
+        off.append(off[-1] + a.shape[0])
+    return off
+
+
+def _host_ints(values):
+    import ctypes
+    return (ctypes.c_int * len(values))(*values)
+
+
+def atss_assign(anchors_per_level, targets, topk=9):
+    """ATSS target assignment (modeling/rpn/loss.py:626-827) for one anchor per location.  anchors_per_level: the [A_l, 4] tensors of
+    AnchorGenerator; targets: boxes fp32 [B, Gmax, 4], labels int32 [B, Gmax], num_gt int32 [B], positive_map uint8 [B, Gmax, 256] on
+    the device (modules/grounding_train.py's GroundingTargets).  Tie rules: equal centre distances go to the lowest anchor index, equal
+    IoU to the lowest gt index.  -> Assignment; no host synchronisation, no data-dependent shape."""
+    off = _level_offsets(anchors_per_level)
+    L, A = len(anchors_per_level), off[-1]
+    hoff = _host_ints(off)
+    K = lib.plain("fiber_atss_num_candidates", hoff, L, int(topk))
+    if K < 0:
+        raise lib.FiberHipError(f"atss_assign: {L} levels of sizes {[b - a for a, b in zip(off, off[1:])]} with topk {topk}: the candidates "
+                                "per gt must number 2..128 (below 2 the reference's std is NaN) on at most 8 levels")
+    boxes, labels = _det_f32(targets.boxes), _c(targets.labels.to(torch.int32))
+    num_gt, pmap = _c(targets.num_gt.to(torch.int32)), _c(targets.positive_map.to(torch.uint8))
+    B, G = boxes.shape[:2]
+    T = pmap.shape[-1]
+    if boxes.shape != (B, G, 4) or labels.shape != (B, G) or num_gt.shape != (B,) or pmap.shape != (B, G, T):
+        raise ValueError(f"atss_assign: boxes {tuple(boxes.shape)}, labels {tuple(labels.shape)}, num_gt {tuple(num_gt.shape)}, "
+                         f"positive_map {tuple(pmap.shape)}")
+    dev = boxes.device
+    anchors = _c(torch.cat([a.detach().float() for a in anchors_per_level], dim=0))
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)      # noqa: E731  (every element is written by the kernels)
+    cand_idx, cand_iou, key = e((B, G, K), torch.int32), e((B, G, K), torch.float32), e((B, A), torch.int64)
+    out = Assignment(e((B, A), torch.int32), e((B, A), torch.int32), e((B, A, 4), torch.float32), e((B, A, T), torch.uint8),
+                     e((B,), torch.int32), anchors, off)
+    lib.call("fiber_atss_candidates_f32", lib.ptr(anchors), hoff, L, lib.ptr(boxes), lib.ptr(num_gt), lib.ptr(cand_idx), lib.ptr(cand_iou),
+             B, G, A, int(topk))
+    lib.call("fiber_atss_resolve_f32", lib.ptr(anchors), lib.ptr(boxes), lib.ptr(num_gt), lib.ptr(cand_idx), lib.ptr(cand_iou), lib.ptr(key),
+             B, G, A, K)
+    lib.call("fiber_atss_finalize_f32", lib.ptr(anchors), lib.ptr(boxes), lib.ptr(labels), lib.ptr(pmap), lib.ptr(key), lib.ptr(out.matched),
+             lib.ptr(out.labels), lib.ptr(out.reg_targets), lib.ptr(out.token_targets), lib.ptr(out.num_pos), B, G, A, T)
+    return out
+
+
+class _AtssBoxLosses(torch.autograd.Function):
+    """Forward: one launch per level into per-workgroup partials + one fold; backward: one launch per level writing the NCHW gradients.
+    Returns fp32 [3] = (sum w (1 - giou), sum w, sum BCE(centerness, w)); its upstream gradient is read from device memory."""
+
+    @staticmethod
+    def forward(ctx, anchors, labels, reg_targets, level_off, *levels):
+        L = len(level_off) - 1
+        regs, ctrs = [_det_f32(t) for t in levels[:L]], [_det_f32(t) for t in levels[L:]]
+        B, A = labels.shape
+        rows = [lib.plain("fiber_atss_loss_rows", B, level_off[l + 1] - level_off[l]) for l in range(L)]
+        part = torch.empty((max(1, sum(rows)), 3), dtype=torch.float32, device=labels.device)
+        sums = torch.zeros(3, dtype=torch.float32, device=labels.device)
+        row0 = 0
+        for l in range(L):
+            lib.call("fiber_atss_loss_fwd_f32", lib.ptr(regs[l]), lib.ptr(ctrs[l]), lib.ptr(anchors), lib.ptr(labels), lib.ptr(reg_targets),
+                     lib.ptr(part), None, B, A, level_off[l + 1] - level_off[l], level_off[l], row0)
+            row0 += rows[l]
+        if row0:
+            lib.call("fiber_fold_rows_f32", lib.ptr(part), lib.ptr(sums), row0, 3)
+        ctx.save_for_backward(anchors, labels, reg_targets, *regs, *ctrs)
+        ctx.level_off = level_off
+        ctx.meta = [(t.shape, t.dtype) for t in levels]
+        return sums
+
+    @staticmethod
+    def backward(ctx, g):
+        anchors, labels, reg_targets, *saved = ctx.saved_tensors
+        off = ctx.level_off
+        L = len(off) - 1
+        B, A = labels.shape
+        g32 = _c(g.detach().float().reshape(3))
+        dregs, dctrs = [], []
+        for l in range(L):
+            reg, ctr = saved[l], saved[L + l]
+            dreg, dctr = torch.empty_like(reg), torch.empty_like(ctr)
+            lib.call("fiber_atss_loss_bwd_f32", lib.ptr(reg), lib.ptr(ctr), lib.ptr(anchors), lib.ptr(labels), lib.ptr(reg_targets),
+                     lib.ptr(g32), lib.ptr(dreg), lib.ptr(dctr), B, A, off[l + 1] - off[l], off[l])
+            dregs.append(dreg), dctrs.append(dctr)
+        grads = [d.view(s).to(dt) for d, (s, dt) in zip(dregs + dctrs, ctx.meta)]
+        return (None, None, None, None, *grads)
+
+
+def atss_box_losses(bbox_reg_levels, centerness_levels, anchors_per_level, assignment):
+    """The box-regression and centerness loss sums over the assigned anchors (loss.py:583-624, :829-844, :1237-1254) with bbox_reg
+    [B, 4, H, W] and centerness [B, 1, H, W] read in place per level.  -> (sum w (1 - giou), sum w, sum BCE(centerness, w)), w the
+    centerness target; differentiable in bbox_reg and centerness; all three are 0 when nothing is assigned."""
+    off = _level_offsets(anchors_per_level)
+    if off != list(assignment.level_off):
+        raise ValueError(f"atss_box_losses: level offsets {off} differ from the assignment's {assignment.level_off}")
+    L, (B, A) = len(off) - 1, assignment.labels.shape
+    if len(bbox_reg_levels) != L or len(centerness_levels) != L:
+        raise ValueError(f"atss_box_losses: {len(bbox_reg_levels)} / {len(centerness_levels)} prediction levels for {L} anchor levels")
+    for l, (r, c) in enumerate(zip(bbox_reg_levels, centerness_levels)):
+        n = off[l + 1] - off[l]
+        if r.shape[0] != B or r.numel() != B * 4 * n or c.numel() != B * n:
+            raise NotImplementedError(f"atss_box_losses level {l}: bbox_reg {tuple(r.shape)} / centerness {tuple(c.shape)} for {n} anchors "
+                                      "(one anchor per location)")
+    sums = _AtssBoxLosses.apply(assignment.anchors, assignment.labels, assignment.reg_targets, off, *bbox_reg_levels, *centerness_levels)
+    return sums[0], sums[1], sums[2]

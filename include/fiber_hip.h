@@ -328,6 +328,47 @@ int fiber_det_nms_select(const float* boxes, const float* scores, const int* lab
                          float* out_boxes, float* out_scores, int* out_labels, int* out_source, int* out_count, int B, int N, int D,
                          fiber_stream_t stream);
 
+/* Grounding training: ATSS target assignment and the box / centerness losses with fixed shapes and no host synchronisation
+ * (csrc/atss.hip); file:line relative to the reference's fine_grained/maskrcnn_benchmark/.  Targets: gt_boxes fp32 [B,Gmax,4] (xyxy),
+ * gt_labels int32 [B,Gmax], num_gt int32 [B], positive_map uint8 [B,Gmax,T]; rows g >= num_gt[b] are never read.  anchors fp32 [A,4]: the
+ * levels concatenated in level order; level_off: HOST array of L + 1 anchor offsets (L <= 8, level_off[0] = 0, level_off[L] = A).
+ * K = sum_l min(topk, A_l) candidates per gt = fiber_atss_num_candidates (-1 if refused).  NULL or misaligned pointers, T != 256,
+ * K < 2 (the reference's unbiased std is NaN) and K > 128 -> 1; B == 0 -> 0 without a launch.  The only atomics are integer (a 64-bit
+ * max, a count): two runs give the same bits.
+ * fiber_atss_candidates_f32 replaces modeling/rpn/loss.py:697-719 and structures/boxlist_ops.py:96-135 (the [A,G] IoU and distance
+ * matrices and the per-level topk): per live (image, gt) and level the min(topk, A_l) anchors nearest to the gt centre by
+ * sqrt(dx^2 + dy^2), EQUAL DISTANCES TO THE LOWEST ANCHOR INDEX, in ascending (distance, index) order -> cand_idx int32 [B,Gmax,K]
+ * (index into the concatenated anchors) and cand_iou fp32 [B,Gmax,K] (+1 convention).
+ * fiber_atss_resolve_f32 replaces loss.py:721-755: threshold mean + unbiased std of the gt's K IoUs (summed in a fixed order),
+ * positive = iou >= threshold and min(l,t,r,b) > 0.01 of the anchor centre in the gt; key uint64 [B,A] (zeroed here) receives the maximum
+ * over the anchor's positive gts of (iou bits << 32 | 0xFFFFFFFF - g): highest IoU wins, EQUAL IoU TO THE LOWEST GT INDEX; 0 = unassigned.
+ * fiber_atss_finalize_f32 replaces loss.py:756-804 and modeling/box_coder.py:22-50 (encode, weights 10,10,5,5): matched int32 [B,A]
+ * (-1 unassigned), labels int32 [B,A] (0), reg_targets fp32 [B,A,4] (0), token_targets uint8 [B,A,T] (the matched gt's positive_map row;
+ * unassigned: the one-hot on token T-1), num_pos int32 [B] = anchors with labels > 0.
+ * fiber_atss_loss_fwd_f32 / _bwd_f32 replace loss.py:583-624 (GIoULoss), :829-844 (compute_centerness_targets), BCEWithLogitsLoss(sum),
+ * the pos_inds gathers (:1194, :1237-1254), box_coder.py:52-95 (decode, log(1000/16) clamp) and concat_box_prediction_layers for ONE
+ * level: bbox_reg fp32 [B,4,H,W] and centerness fp32 [B,1,H,W] read in place (A_level = H*W anchors at `offset` of the concatenation),
+ * dense over the anchors and masked by labels > 0.  fwd: part[(row0 + i)*3 + {0,1,2}], i < fiber_atss_loss_rows(B, A_level), receive
+ * per-workgroup sums of w (1 - giou), w and BCE(centerness, w), w the centerness target, to be folded by fiber_fold_rows_f32;
+ * ctr_targets (nullable) fp32 [B,A] receives w (0 unassigned) in the level's slice.  bwd: g = three upstream gradients (of the three
+ * sums) in device memory; d_bbox_reg [B,4,H,W] and d_centerness [B,1,H,W] are written in full, zeros on unassigned anchors and on a
+ * clamped coordinate; max / min ties split the gradient in halves and the clamp passes it at equality, as torch does. */
+int fiber_atss_num_candidates(const int* level_off, int L, int topk);
+int fiber_atss_candidates_f32(const float* anchors, const int* level_off, int L, const float* gt_boxes, const int* num_gt, int* cand_idx,
+                              float* cand_iou, int B, int Gmax, int A, int topk, fiber_stream_t stream);
+int fiber_atss_resolve_f32(const float* anchors, const float* gt_boxes, const int* num_gt, const int* cand_idx, const float* cand_iou,
+                           unsigned long long* key, int B, int Gmax, int A, int K, fiber_stream_t stream);
+int fiber_atss_finalize_f32(const float* anchors, const float* gt_boxes, const int* gt_labels, const unsigned char* positive_map,
+                            const unsigned long long* key, int* matched, int* labels, float* reg_targets, unsigned char* token_targets,
+                            int* num_pos, int B, int Gmax, int A, int T, fiber_stream_t stream);
+int fiber_atss_loss_rows(int B, int A_level);
+int fiber_atss_loss_fwd_f32(const float* bbox_reg, const float* centerness, const float* anchors, const int* labels,
+                            const float* reg_targets, float* part, float* ctr_targets, int B, int A, int A_level, int offset, int row0,
+                            fiber_stream_t stream);
+int fiber_atss_loss_bwd_f32(const float* bbox_reg, const float* centerness, const float* anchors, const int* labels,
+                            const float* reg_targets, const float* g, float* d_bbox_reg, float* d_centerness, int B, int A, int A_level,
+                            int offset, fiber_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
