@@ -75,6 +75,9 @@ SIGNATURES = {
     "fiber_atss_finalize_f32": [P, P, P, P, P, P, P, P, P, P, I, I, I, I],
     "fiber_atss_loss_fwd_f32": [P, P, P, P, P, P, P, I, I, I, I, I],
     "fiber_atss_loss_bwd_f32": [P, P, P, P, P, P, P, P, I, I, I, I],
+    "fiber_dropblock_mask_u8": [P, I, U64, P, F, I, P, P, I, I, I],
+    "fiber_fpn_merge_fwd_bf16": [P, P, P, P, P, P, I, I, I, I, I, I],
+    "fiber_fpn_merge_bwd_bf16": [P, P, P, P, P, P, I, I, I, I, I, I],
 }
 # host-side helpers without a stream argument
 PLAIN = {"fiber_layernorm_bwd_grid": [I], "fiber_window_attn_bwd_slices": [I, I], "fiber_window_attn_colsum_rows": [I, I, I], "fiber_colsum_slabs": [I, I], "fiber_tn_fold_blocks": [I, I, I, I], "fiber_colsum_labelled_slabs": [I], "fiber_gemm_row_tile": [I, I, I], "fiber_gemm_tn_splits": [I, I, I],

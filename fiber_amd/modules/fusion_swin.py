@@ -14,7 +14,8 @@ coarse path (fiber_amd.ops): what the detection variant adds is geometry, not ar
   * odd blocks always shift, also when the padded grid is a single window;
   * the i2t query is the projected self-attention output with no LayerNorm in front (:205-215);
   * each stage emits a LayerNorm'ed NCHW map (norm0 = identity for the RETINANET arch) for the FPN, which -- like the DyHead and
-    the detection losses -- is outside this path (`fpn` may be passed in; default: the stage maps are returned as they are).
+    the detection losses -- is outside this path (`fpn` may be passed in, modules/fpn.py's is handed the channels-last stage tokens
+    directly; default: the stage maps are returned as they are).
 """
 import torch
 import torch.nn as nn
@@ -223,12 +224,15 @@ class FusionSwinTransformer(nn.Module):
         for layer in tm.encoder.layer[:6]:                          # num_pre_text = 6 (:849)
             text = layer(text, ext)[0]
         outs = []
+        fpn = self.backbone.fpn
+        nhwc = hasattr(fpn, "forward_nhwc")                         # modules/fpn.py: takes the channels-last tokens as they lie
 
         def emit(i, t, H, W):
             if f"stage{i + 2}" in sw.out_features:
                 n = getattr(sw, f"norm{i}")
                 t = t if isinstance(n, nn.Identity) else ops.layernorm(t, n.weight, n.bias, n.eps)
-                outs.append(t.view(-1, H, W, sw.num_features[i]).permute(0, 3, 1, 2).contiguous())
+                t = t.view(-1, H, W, sw.num_features[i])
+                outs.append(t if nhwc else t.permute(0, 3, 1, 2).contiguous())
         for i in (0, 1):                                            # num_pre_vision = 2 (:854)
             x_out, H, W, x, Wh, Ww = sw.layers[i](x, Wh, Ww)
             emit(i, x_out, H, W)
@@ -254,5 +258,8 @@ class FusionSwinTransformer(nn.Module):
             x = fused
         emit(3, x, Wh, Ww)
         lang = self.get_aggregated_output(text, tokenizer_input["input_ids"], tokenizer_input["attention_mask"])
-        visual = self.backbone.fpn(outs) if self.backbone.fpn is not None else outs
+        if nhwc:                                                    # the same values fpn(outs) would transpose back (bit for bit)
+            visual = tuple(t.permute(0, 3, 1, 2).float() for t in fpn.forward_nhwc(outs))
+        else:
+            visual = fpn(outs) if fpn is not None else outs
         return visual, lang, None

@@ -1,0 +1,118 @@
+"""The fine-grained (grounding) model end to end on the MI355X kernels: fused backbone -> FPN neck -> VLDyHead.
+
+Mirrors fine_grained/maskrcnn_benchmark/modeling/detector/generalized_vl_rcnn.py:64-404 (GeneralizedVLRCNN) in the configuration every FIBER
+yaml uses: SWINT.VERSION "fusion" with BACKBONE.FUSION_VERSION "v2" (fusion_in_backbone), RPN_ONLY, RPN_ARCHITECTURE "VLDYHEAD".  Same
+submodule names, hence the checkpoint key prefixes `fusion_backbone.backbone.body.*` (fusion_swin.py), `fusion_backbone.backbone.fpn.*`
+(fpn.py), `fusion_backbone.language_backbone.body.model.*` and `rpn.head.*` (grounding_inference.VLDyHeadModule): a reference grounding
+checkpoint loads with load_state_dict.  train() reproduces the freezing rules that apply here (:163-240).
+
+Differences in the call surface, none in the computation:
+  * no tokenizer files are assumed: `captions` are tokenised only by a tokenizer the caller supplied (anything with the
+    batch_encode_plus of :268-275); otherwise the caller passes tokenizer_input = {"input_ids", "attention_mask"};
+  * training targets are grounding_train.GroundingTargets (fixed-shape device tensors carrying their positive map), the result the
+    four-entry loss dict; eval returns grounding_inference.Detections instead of a list of BoxLists;
+  * `images` is a padded [B, 3, H, W] tensor, a (tensor, image_sizes) pair, or an object with .tensors / .image_sizes (ImageList).
+"""
+import torch.nn as nn
+
+from . import roberta as RB
+from .fpn import build_swint_fpn
+from .fusion_swin import FusionSwinTransformer
+from .grounding_inference import VLDyHeadModule
+
+
+def _need(cond, name, why):
+    if not cond:
+        raise NotImplementedError(f"{name}: {why}")
+
+
+class GeneralizedVLRCNN(nn.Module):
+    def __init__(self, cfg, tokenizer=None):
+        super().__init__()
+        m = cfg.MODEL
+        fc = m.DYHEAD.FUSE_CONFIG
+        _need(m.SWINT.VERSION == "fusion", "MODEL.SWINT.VERSION", "only \"fusion\" (fusion in the backbone) is built, as every FIBER yaml sets")
+        _need(m.BACKBONE.FUSION_VERSION == "v2", "MODEL.BACKBONE.FUSION_VERSION", "only \"v2\" (fusion_swin_transformer_v2 / roberta_fused_model_v2) is built")
+        _need(m.RPN_ONLY, "MODEL.RPN_ONLY", "the ROI heads are not built (every FIBER yaml is RPN-only)")
+        _need(m.RPN_ARCHITECTURE == "VLDYHEAD", "MODEL.RPN_ARCHITECTURE", "only \"VLDYHEAD\" is built")
+        _need(getattr(m.BACKBONE, "CONV_BODY", "SWINT-FPN-RETINANET") == "SWINT-FPN-RETINANET", "MODEL.BACKBONE.CONV_BODY",
+              "only the SWINT-FPN-RETINANET wiring (stage 2 skipped, P6 / P7 on top) is built")
+        _need(not fc.MLM_LOSS, "MODEL.DYHEAD.FUSE_CONFIG.MLM_LOSS", "the masked-language-modelling branch (random_word, :276-285) is out of scope")
+        _need(not getattr(fc, "ADD_LINEAR_LAYER", False), "MODEL.DYHEAD.FUSE_CONFIG.ADD_LINEAR_LAYER", "the prompt-tuning linear layer is not built")
+        _need(not getattr(m.RPN, "FORCE_BOXES", False), "MODEL.RPN.FORCE_BOXES", "proposals forced from the targets feed ROI heads, which are not built")
+        _need(not getattr(m, "LINEAR_PROB", False), "MODEL.LINEAR_PROB", "linear probing is not built")
+        _need(not getattr(m.RPN, "RETURN_FUSED_FEATURES", False), "MODEL.RPN.RETURN_FUSED_FEATURES", "fused features feed ROI heads, which are not built")
+        _need(not getattr(m.LANGUAGE_BACKBONE, "MASK_SPECIAL", False) and not getattr(getattr(cfg, "DATASETS", None), "ONE_HOT", False),
+              "LANGUAGE_BACKBONE.MASK_SPECIAL / DATASETS.ONE_HOT", "these rewrite the text mask on the non-fusion path only (:299-309)")
+        self.cfg = cfg
+        self.fusion_in_backbone = True
+        self.tokenizer = tokenizer
+        s = m.SWINT
+        self.fusion_backbone = FusionSwinTransformer(embed_dim=s.EMBED_DIM, depths=tuple(s.DEPTHS), num_heads=tuple(s.NUM_HEADS),
+                                                     window_size=s.WINDOW_SIZE, drop_path_rate=s.DROP_PATH_RATE, fpn=build_swint_fpn(cfg),
+                                                     text_config=RB.roberta_base_config())
+        self.rpn = VLDyHeadModule(cfg)
+        self.roi_heads = None
+        self.freeze_backbone = m.BACKBONE.FREEZE
+        self.freeze_fpn = m.FPN.FREEZE
+        self.freeze_rpn = m.RPN.FREEZE
+        self.freeze_language_backbone = m.LANGUAGE_BACKBONE.FREEZE
+        self.freeze_cls_logits = fc.USE_DOT_PRODUCT_TOKEN_LOSS
+        if self.freeze_cls_logits:                                   # :141-145
+            for p in self.rpn.head.cls_logits.parameters():
+                p.requires_grad = False
+        if self.freeze_language_backbone:                            # :147-151
+            for p in self.fusion_backbone.language_backbone.parameters():
+                p.requires_grad = False
+
+    def train(self, mode=True):
+        """Training mode with the frozen parts kept in eval (:163-240)."""
+        super().train(mode)
+        frozen = []
+        if self.freeze_backbone:
+            frozen.append(self.fusion_backbone.backbone.body)
+        if self.freeze_fpn:
+            frozen.append(self.fusion_backbone.backbone.fpn)
+        if self.freeze_cls_logits:
+            frozen.append(self.rpn.head.cls_logits)
+        if self.freeze_language_backbone:
+            frozen.append(self.fusion_backbone.language_backbone)
+        for mod in frozen:
+            mod.eval()
+            for p in mod.parameters():
+                p.requires_grad = False
+        if self.freeze_rpn:                                          # :184-188: the head in eval, every rpn parameter frozen
+            self.rpn.head.eval()
+            for p in self.rpn.parameters():
+                p.requires_grad = False
+        return self
+
+    def _tokenize(self, captions, device):
+        if self.tokenizer is None:
+            raise ValueError("GeneralizedVLRCNN: captions need a tokenizer (pass tokenizer= to the constructor), or pass tokenizer_input")
+        lb = self.cfg.MODEL.LANGUAGE_BACKBONE
+        tok = self.tokenizer.batch_encode_plus(captions, max_length=lb.MAX_QUERY_LEN, padding="max_length" if lb.PAD_MAX else "longest",
+                                               return_special_tokens_mask=True, return_tensors="pt", truncation=True)
+        return {"input_ids": tok["input_ids"].to(device), "attention_mask": tok["attention_mask"].to(device)}
+
+    def forward(self, images, targets=None, captions=None, positive_map=None, greenlight_map=None, tokenizer_input=None):
+        """Training (with targets: GroundingTargets) -> {"loss_reg", "loss_centerness", "loss_cls", "loss_dot_product_token"}; eval ->
+        Detections.  greenlight_map is read by the MLM branch only and is accepted for signature parity."""
+        if self.training and targets is None:
+            raise ValueError("In training mode, targets should be passed")
+        sizes = None
+        if isinstance(images, (tuple, list)):
+            images, sizes = images
+        elif hasattr(images, "tensors"):
+            images, sizes = images.tensors, getattr(images, "image_sizes", None)
+        if sizes is None:
+            sizes = [tuple(images.shape[-2:])] * images.shape[0]     # (h, w) per image, as ImageList.image_sizes
+        if tokenizer_input is None:
+            if captions is None:
+                raise ValueError("GeneralizedVLRCNN: captions (with a tokenizer) or tokenizer_input is required")
+            tokenizer_input = self._tokenize(captions, images.device)
+        visual_features, language_dict_features, _ = self.fusion_backbone(tokenizer_input, images)
+        language_dict_features["mlm_labels"] = None
+        if targets is not None and self.training:
+            targets = targets.to(images.device)
+        return self.rpn(sizes, list(visual_features), language_dict_features, positive_map, targets if self.training else None)

@@ -2220,3 +2220,125 @@ def atss_box_losses(bbox_reg_levels, centerness_levels, anchors_per_level, assig
                                       "(one anchor per location)")
     sums = _AtssBoxLosses.apply(assignment.anchors, assignment.labels, assignment.reg_targets, off, *bbox_reg_levels, *centerness_levels)
     return sums[0], sums[1], sums[2]
+
+
+# ---- FPN neck: DropBlock mask + lateral / nearest-upsample merge (csrc/fpn.hip) ----------------------------------------------------
+def dropblock_mask(B, H, W, drop_prob, block, device, seeds=None):
+    """layers/dropblock.py:42-51, :61-77 -> (keep uint8 [B, H, W], kept int32 [1] = keep.sum(), both on the device; nothing is read on the
+    host).  seeds None: the Bernoulli(drop_prob / block^2) draw comes from the dropout key stream (next_seed: capturable in a hipGraph);
+    seeds given ([B, H, W], non-zero = block centre): they are used as they are -- how a test replays the reference's own draws."""
+    gamma = float(drop_prob) / float(block * block)
+    keep = torch.empty((B, H, W), dtype=torch.uint8, device=device)
+    kept = torch.empty(1, dtype=torch.int32, device=device)
+    if seeds is None:
+        s8, draw, seed, base = torch.empty((B, H, W), dtype=torch.uint8, device=device), 1, next_seed(), seed_base_ptr()
+    else:
+        if tuple(seeds.shape) != (B, H, W):
+            raise ValueError(f"dropblock_mask: seeds {tuple(seeds.shape)} for a [{B}, {H}, {W}] map")
+        s8, draw, seed, base = (seeds != 0).to(device=device, dtype=torch.uint8).contiguous(), 0, 0, None
+    lib.call("fiber_dropblock_mask_u8", lib.ptr(s8), draw, seed, base, gamma, int(block), lib.ptr(keep), lib.ptr(kept), B, H, W)
+    return keep, kept
+
+
+class _FpnMerge(torch.autograd.Function):
+    """(inner, dropped) = (lateral + nearest_up(coarse), that * keep * numel / kept) in one launch; backward: one launch for both
+    gradients.  coarse / keep may be None; either output's gradient may be None."""
+
+    @staticmethod
+    def forward(ctx, lateral, coarse, keep, kept):
+        lateral = _c(lateral)
+        coarse = _c(coarse) if coarse is not None else None
+        B, H, W, C = lateral.shape
+        Hc, Wc = (coarse.shape[1], coarse.shape[2]) if coarse is not None else (H, W)
+        inner = torch.empty_like(lateral)
+        dropped = torch.empty_like(lateral) if keep is not None else None
+        lib.call("fiber_fpn_merge_fwd_bf16", lib.ptr(lateral), lib.ptr(coarse), lib.ptr(keep), lib.ptr(kept), lib.ptr(inner), lib.ptr(dropped),
+                 B, H, W, C, Hc, Wc)
+        ctx.save_for_backward(keep, kept)
+        ctx.geom = (B, H, W, C, Hc, Wc, coarse is not None)
+        ctx.set_materialize_grads(False)
+        if dropped is None:
+            return inner, None
+        return inner, dropped
+
+    @staticmethod
+    def backward(ctx, d_inner, d_dropped):
+        keep, kept = ctx.saved_tensors
+        B, H, W, C, Hc, Wc, has_coarse = ctx.geom
+        ref = d_inner if d_inner is not None else d_dropped
+        if ref is None:
+            return None, None, None, None
+        d_inner = _c(d_inner.to(BF16)) if d_inner is not None else None
+        d_dropped = _c(d_dropped.to(BF16)) if d_dropped is not None else None
+        d_lat = torch.empty((B, H, W, C), dtype=BF16, device=ref.device)
+        d_coarse = torch.empty((B, Hc, Wc, C), dtype=BF16, device=ref.device) if has_coarse else None
+        lib.call("fiber_fpn_merge_bwd_bf16", lib.ptr(d_inner), lib.ptr(d_dropped), lib.ptr(keep), lib.ptr(kept), lib.ptr(d_lat),
+                 lib.ptr(d_coarse), B, H, W, C, Hc, Wc)
+        return d_lat, d_coarse, None, None
+
+
+def fpn_merge(lateral, coarse, keep=None, kept=None):
+    """FPN top-down step on channels-last bf16 maps (fpn.py:97-110): inner = lateral [B, H, W, C] + coarse [B, Hc, Wc, C] up-sampled to
+    H x W by F.interpolate's nearest rule; with (keep, kept) of dropblock_mask also dropped = inner * keep * (B H W / kept) formed from the
+    unrounded sum.  -> (inner, dropped or None).  coarse None: inner = lateral (DropBlock on a map of its own)."""
+    if lateral.dtype != BF16 or lateral.dim() != 4 or (coarse is not None and (coarse.dtype != BF16 or coarse.dim() != 4
+                                                                              or coarse.shape[0] != lateral.shape[0] or coarse.shape[3] != lateral.shape[3])):
+        raise ValueError(f"fpn_merge: lateral {tuple(lateral.shape)} {lateral.dtype}, coarse {None if coarse is None else tuple(coarse.shape)}")
+    if (keep is None) != (kept is None):
+        raise ValueError("fpn_merge: keep and kept come together (ops.dropblock_mask)")
+    if keep is not None:
+        if tuple(keep.shape) != tuple(lateral.shape[:3]) or keep.dtype != torch.uint8 or kept.dtype != torch.int32:
+            raise ValueError(f"fpn_merge: keep {tuple(keep.shape)} {keep.dtype} for lateral {tuple(lateral.shape)}")
+        keep = keep.contiguous()
+    return _FpnMerge.apply(lateral, coarse, keep, kept)
+
+
+def _weight_2d(weight):
+    """The [N, K] view of a [N, K, 1, 1] convolution parameter, ONE object per parameter: the bf16 working copies are keyed by tensor
+    identity, so a fresh .view per call would rebuild them every time.  It shares the parameter's storage and version counter."""
+    key = ("V2", id(weight))
+    hit = _cache_get(key, weight)
+    if hit is not None and hit[1].data_ptr() == weight.data_ptr():
+        return hit[1]
+    v = weight.detach().view(weight.shape[0], weight.shape[1])
+    _cache_put(key, None, v, weight)
+    return v
+
+
+class _Conv1x1(torch.autograd.Function):
+    """1x1 convolution on channels-last tokens [..., Cin] with an nn.Conv2d-shaped weight: the NT GEMM on the tokens as they lie (no
+    im2col copy), dX on the NT kernel, dW / db on the TN kernel."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        shp = x.shape
+        x2 = _c(x).view(-1, shp[-1])
+        w2 = _weight_2d(weight)
+        y, _ = gemm_nt(x2, bf16_weight(w2), bias)
+        ctx.save_for_backward(x2, weight)
+        ctx.shp, ctx.has_bias = shp, bias is not None
+        return y.view(*shp[:-1], weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, weight = ctx.saved_tensors
+        dy2 = _c(dy.to(BF16)).view(-1, weight.shape[0])
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = _dgrad(dy2, _weight_2d(weight)).view(ctx.shp)
+        need_db = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1]:
+            dw = wgrad(dy2, x2, want_bias=need_db)
+            if need_db:
+                dw, db = dw
+            dw = dw.view(weight.shape)
+        elif need_db:
+            db = colsum(dy2)
+        return dx, dw, db
+
+
+def conv1x1(x, weight, bias=None):
+    """nn.Conv2d(Cin, Cout, 1) on channels-last bf16 tokens [..., Cin] -> [..., Cout] (the FPN laterals, fpn.py:48, :95)."""
+    if weight.dim() != 4 or weight.shape[2:] != (1, 1) or (weight.shape[0] % 8) or (weight.shape[1] % 8):
+        raise lib.FiberHipError(f"conv1x1: weight {tuple(weight.shape)} (1x1, channel counts multiples of 8)")
+    return _Conv1x1.apply(x, weight, bias)

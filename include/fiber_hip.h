@@ -369,6 +369,31 @@ int fiber_atss_loss_bwd_f32(const float* bbox_reg, const float* centerness, cons
                             const float* reg_targets, const float* g, float* d_bbox_reg, float* d_centerness, int B, int A, int A_level,
                             int offset, fiber_stream_t stream);
 
+/* FPN top-down pathway of the fine-grained neck (csrc/fpn.hip); file:line relative to the reference's fine_grained/maskrcnn_benchmark/.
+ * Channels-last bf16 maps [B,H,W,C], fp32 arithmetic, C % 8 == 0 (16-byte accesses; any other C -> 1).  No floating-point atomics and
+ * every output element written exactly once: two runs give the same bits.  Nothing synchronises the host.
+ * Nearest index rule of all three: src = min((int)floorf(dst * ((float)Hc / (float)H)), Hc - 1) and the same for W, the scale formed in
+ * fp32 -- F.interpolate(mode="nearest", size=...).  (The exact rational dst * Hc / H differs, first at H = 58, Hc = 30.)
+ * fiber_dropblock_mask_u8 replaces layers/dropblock.py:45-48 (host torch.rand, the copy) and :61-74 (max_pool2d block mask) and the
+ * block_mask.sum() of :57: seeds uint8 [B,H,W] in/out; draw != 0 first sets seeds[i] = hash_u32(seed + *seed_base, i) < (uint32)(gamma *
+ * 2^32) (i the flat index; seed by value + optional DEVICE base as fiber_dropout_bf16, so a captured graph draws anew on every replay),
+ * draw == 0 reads seeds as given; keep uint8 [B,H,W] = 1 - maxpool_{block x block, stride 1, pad block/2}(seeds); kept int32[1] = sum keep,
+ * overwritten (integer accumulation).  block odd (even -> 1), 0 <= gamma < 1.
+ * fiber_fpn_merge_fwd_bf16 replaces modeling/backbone/fpn.py:97-108 and dropblock.py:54-57: s = f32(lateral) + f32(coarse[src]),
+ * inner_out = bf16(s), dropped_out (nullable, with keep and kept) = bf16(s * keep * scale), scale = (float)(B*H*W) / (float)kept[0] read
+ * from device memory and applied to the UNROUNDED sum.  kept[0] == 0 gives what IEEE gives (NaN where keep is 0 -- everywhere), as the
+ * reference.  coarse [B,Hc,Wc,C]; Hc == H and Wc == W is the plain add (fpn.py:100-101); coarse NULL: s = f32(lateral) (DropBlock2D alone).
+ * fiber_fpn_merge_bwd_bf16 is the backward of it in ONE launch: g = f32(d_inner) + f32(d_dropped) * keep * scale (a NULL term is absent;
+ * d_dropped needs keep and kept), d_lateral_out = bf16(g), d_coarse_out[b,hc,wc,:] = bf16(sum of the unrounded g over the fine pixels whose
+ * src is (hc,wc), in fp32, row-major child order; 0 where a coarse pixel has no child).  The children are found with the forward rule
+ * itself.  d_coarse_out NULL: not written (Hc, Wc ignored). */
+int fiber_dropblock_mask_u8(unsigned char* seeds, int draw, uint64_t seed, const uint64_t* seed_base, float gamma, int block,
+                            unsigned char* keep, int* kept, int B, int H, int W, fiber_stream_t stream);
+int fiber_fpn_merge_fwd_bf16(const void* lateral, const void* coarse, const unsigned char* keep, const int* kept, void* inner_out,
+                             void* dropped_out, int B, int H, int W, int C, int Hc, int Wc, fiber_stream_t stream);
+int fiber_fpn_merge_bwd_bf16(const void* d_inner, const void* d_dropped, const unsigned char* keep, const int* kept, void* d_lateral_out,
+                             void* d_coarse_out, int B, int H, int W, int C, int Hc, int Wc, fiber_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
