@@ -69,11 +69,12 @@ class ModulatedDeformConv(nn.Module):
             self.register_parameter("bias", None)
         self.reset_parameters()
 
-    def reset_parameters(self):
+    @torch.no_grad()
+    def reset_parameters(self):                             # in place on the parameters (not `.data`): ops.py's weight copies follow
         n = self.in_channels * self.kernel_size[0] * self.kernel_size[1]
-        self.weight.data.uniform_(-n ** -0.5, n ** -0.5)
+        self.weight.uniform_(-n ** -0.5, n ** -0.5)
         if self.bias is not None:
-            self.bias.data.zero_()
+            self.bias.zero_()
 
     def forward_nhwc(self, x, offset, mask):
         B, H, W, _ = x.shape
@@ -163,18 +164,19 @@ class DyConv(nn.Module):
             self.offset.out_fp32 = True                  # sampling positions and modulation logits stay fp32
         self.init_weights()
 
+    @torch.no_grad()
     def init_weights(self):
         for m in self.DyConv.modules():
             if isinstance(m, nn.Conv2d):
-                nn.init.normal_(m.weight.data, 0, 0.01)
+                m.weight.normal_(0, 0.01)
                 if m.bias is not None:
-                    m.bias.data.zero_()
+                    m.bias.zero_()
         if self.AttnConv is not None:
             for m in self.AttnConv.modules():
                 if isinstance(m, nn.Conv2d):
-                    nn.init.normal_(m.weight.data, 0, 0.01)
+                    m.weight.normal_(0, 0.01)
                     if m.bias is not None:
-                        m.bias.data.zero_()
+                        m.bias.zero_()
 
     def forward(self, x):
         xs = [_nhwc(f) for f in x]                       # one layout change per level; each level feeds up to three convolutions

@@ -399,11 +399,14 @@ def caption_test_wrapup(outs, model_name, out_dir="result"):
     os.remove(shard)
 
 
+@torch.no_grad()
 def init_weights(module):
+    # in-place ops on the parameters themselves, not on `.data`: they bump the version counter, so the derived weight copies of
+    # fiber_amd/ops.py see a re-initialisation after a forward pass (same values, same generator draws as the `.data` form)
     if isinstance(module, (nn.Linear, nn.Embedding)):
-        module.weight.data.normal_(mean=0.0, std=0.02)
+        module.weight.normal_(mean=0.0, std=0.02)
     elif isinstance(module, nn.LayerNorm):
-        module.bias.data.zero_()
-        module.weight.data.fill_(1.0)
+        module.bias.zero_()
+        module.weight.fill_(1.0)
     if isinstance(module, nn.Linear) and module.bias is not None:
-        module.bias.data.zero_()
+        module.bias.zero_()

@@ -220,14 +220,15 @@ class RobertaModel(nn.Module):
         self.apply(self._init_weights)
 
     @staticmethod
-    def _init_weights(m):                                   # HF PreTrainedModel._init_weights, N(0, 0.02)
-        if isinstance(m, (nn.Linear, nn.Embedding)):
-            m.weight.data.normal_(mean=0.0, std=0.02)
+    @torch.no_grad()
+    def _init_weights(m):                                   # HF PreTrainedModel._init_weights, N(0, 0.02); in place on the parameters
+        if isinstance(m, (nn.Linear, nn.Embedding)):        # (not `.data`): the version counter tells ops.py's weight copies
+            m.weight.normal_(mean=0.0, std=0.02)
             if isinstance(m, nn.Linear) and m.bias is not None:
-                m.bias.data.zero_()
+                m.bias.zero_()
         elif isinstance(m, nn.LayerNorm):
-            m.bias.data.zero_()
-            m.weight.data.fill_(1.0)
+            m.bias.zero_()
+            m.weight.fill_(1.0)
 
     @classmethod
     def from_pretrained(cls, name, **over):

@@ -6,6 +6,13 @@ cores, embeddings and the element-wise glue are hand-written HIP kernels, and so
 dX = dY.W on the NT kernel (transposed bf16 working copy of W), dW = dY^T.X (+ the bias gradient) on the TN kernel
 (csrc/gemm_tn.hip).  Only the caller-side heads (vocabulary decoder, 2-way ITM, VQA classifier) use the library GEMM.
 Nothing here runs on the CPU: tensors must live on a HIP device.
+
+The derived weight copies (`_wcache`, `_packs`) follow their fp32 masters through a stamp, `_stamp(w)` = (version counter,
+generation, storage address).  What changes one of the three is seen by itself: an in-place op on the parameter (`copy_`, `mul_`,
+`load_state_dict`, torch's optimizers), `mark_weights_dirty()`, and `p.data = other` (`module.to()`, `module.float()`,
+`vector_to_parameters`).  An in-place write THROUGH `p.data` (`p.data.mul_(2)`) changes none of them and cannot be seen from the
+parameter: whoever writes that way calls `mark_weights_dirty()` afterwards -- that call is the contract.  FiberAdamW writes
+through raw pointers and keeps its side of it in step() (restamp_bf16_copies and the two one-launch refreshes).
 """
 import math
 import threading
@@ -53,14 +60,16 @@ def mark_weights_dirty():
 
 
 def _stamp(w):
-    return (w._version, _gen[0])
+    """What a derived copy was made from: the version counter (in-place ops on the parameter), the generation
+    (mark_weights_dirty) and the storage address (`w.data = other` keeps the version: model.to(), module.float())."""
+    return (w._version, _gen[0], w.data_ptr())
 
 
 def bf16_weight(w):
     """bf16 copy of an fp32 parameter, refreshed when the parameter changes (version counter or optimizer step)."""
     key = id(w)
     hit = _cache_get(key, w)
-    if hit is not None and hit[0] == _stamp(w):
+    if hit is not None and hit[0] == _stamp(w) and hit[1].device == w.device:
         return hit[1]
     if hit is not None and hit[1].shape == w.shape and hit[1].device == w.device:
         wb = hit[1]
@@ -77,7 +86,7 @@ def bf16_weight_t(w):
     optimizer step refresh_transposed_copies() rewrites all of them in one launch instead of one strided copy per weight."""
     key = ("T", id(w))
     hit = _cache_get(key, w)
-    if hit is not None and hit[0] == _stamp(w):
+    if hit is not None and hit[0] == _stamp(w) and hit[1].device == w.device:
         return hit[1]
     wb = bf16_weight(w)
     if hit is not None and hit[1].shape == (wb.shape[1], wb.shape[0]) and hit[1].device == wb.device:
@@ -156,7 +165,7 @@ def refresh_head_major_copies():
         if not (isinstance(key, tuple) and key[0] == "HM"):
             continue
         w = ref()
-        b = val[3]() if len(val) > 3 else None
+        b = val[3]() if len(val) > 3 else None              # (a bias Parameter that was REPLACED: the forward checks identity and rebuilds)
         if w is None or b is None or not val[0].is_cuda or w.dtype != torch.float32 or b.dtype != torch.float32 or not w.is_contiguous():
             continue
         if (w.shape[0] % 8) or (w.shape[1] % 8):
@@ -870,18 +879,21 @@ def _ln_mlp_weights(gamma, beta, w1, b1, w2):
     fp32, ONE bf16 rounding); the copies whose K dimension is the hidden one (w2p, w1tp) in the kernel's K order; rebuilt when any of
     the five parameters changes."""
     key = ("LNMLP", id(w1))
-    stamp = tuple(_stamp(t) for t in (gamma, beta, w1, b1, w2))
+    five = (gamma, beta, w1, b1, w2)
+    stamp = tuple(_stamp(t) for t in five)
     hit = _cache_get(key, w1)
-    if hit is not None and hit[0] == stamp:
-        return hit[1]
+    # the entry is keyed by w1 alone, so it remembers (weakly) WHICH five parameters it was built from: a replaced gamma with the
+    # same version and generation is not a hit
+    if hit is not None and hit[0] == stamp and all(r() is t for r, t in zip(hit[1][5], five)) and hit[1][0].device == w1.device:
+        return hit[1][:5]
     with torch.no_grad():
         w1f = w1.detach().float()
         w1p16 = (w1f * gamma.detach().float()[None, :]).to(BF16)
         b1p = torch.addmv(b1.detach().float(), w1f, beta.detach().float()).contiguous()
         w2_16 = w2.detach().to(BF16)
-        val = (w1p16.contiguous(), b1p, _fa(w2_16), w2_16.t().contiguous(), _fa(w1p16.t()))
+        val = (w1p16.contiguous(), b1p, _fa(w2_16), w2_16.t().contiguous(), _fa(w1p16.t()), tuple(weakref.ref(t) for t in five))
     _cache_put(key, stamp, val, w1)
-    return val
+    return val[:5]
 
 
 # widths the fused kernels are USED at (they exist for 128 and 256; FIBER_LN_MLP_WIDTHS=128,256 for A/B runs).  Measured at 512 images,
@@ -1182,7 +1194,7 @@ class _LinearQKVHeadMajor(torch.autograd.Function):
         perm, inv = _qkv_perm(C, heads, x.device)
         key = ("HM", id(weight))
         hit = _cache_get(key, weight)
-        if hit is None or hit[0] != (_stamp(weight), _stamp(bias)):
+        if hit is None or hit[0] != (_stamp(weight), _stamp(bias)) or hit[1][3]() is not bias or hit[1][0].device != weight.device:
             wp = weight.detach()[perm].to(BF16).contiguous()
             _cache_put(key, (_stamp(weight), _stamp(bias)), (wp, bias.detach()[perm].contiguous(), wp.t().contiguous(), weakref.ref(bias), heads), weight)
             _hm_table.clear()                                # (new storage: the one-launch refresh rebuilds its descriptor table)
@@ -1794,7 +1806,7 @@ class _PatchEmbedProj(torch.autograd.Function):
             lib.call("fiber_im2col_patch4", lib.ptr(img), lib.ptr(cols), B, H, W)
         key = ("pe", id(weight))
         hit = _cache_get(key, weight)
-        if hit is None or hit[0] != _stamp(weight):
+        if hit is None or hit[0] != _stamp(weight) or hit[1].device != img.device:
             wp = torch.zeros((Cout, 64), dtype=BF16, device=img.device)
             wp[:, :48] = weight.detach().reshape(Cout, 48).to(BF16)
             _cache_put(key, _stamp(weight), wp, weight)
@@ -1832,7 +1844,7 @@ def _conv_weight_rows(weight, transposed=False):
     with zeros to a multiple of 8 -- the 27-channel offset convolution), or its transpose [kh*kw*Cin, Cp] for the dgrad GEMM."""
     key = ("KCT" if transposed else "KC", id(weight))
     hit = _cache_get(key, weight)
-    if hit is not None and hit[0] == _stamp(weight):
+    if hit is not None and hit[0] == _stamp(weight) and hit[1].device == weight.device:
         return hit[1]
     if transposed:
         v = _conv_weight_rows(weight).t().contiguous()

@@ -1,5 +1,6 @@
-"""AdamW for the fused path on the HIP kernel of csrc/optim.hip: one launch per parameter group, bf16 working copies of
-the weights refreshed in the same pass.  The update rule is transformers 4.6.0 `AdamW(correct_bias=True)` (reference
+"""AdamW for the fused path on the HIP kernel of csrc/optim.hip: one launch per parameter group (one per distinct step count in
+a group whose members' counts differ: the rule counts steps per parameter, the kernel takes one count per launch), bf16 working
+copies of the weights refreshed in the same pass.  The update rule is transformers 4.6.0 `AdamW(correct_bias=True)` (reference
 fiber_utils.py:248-252) in ITS form -- eps added to the un-corrected sqrt(v), weight decay applied after the Adam update --
 which differs from torch.optim.AdamW for small gradients / early steps.  `HFAdamW` is the same rule in plain torch for host
 tensors (CPU wiring tests).  Parameter groups, `lr` scheduling through LambdaLR, state_dict / load_state_dict work as for
@@ -59,6 +60,7 @@ class FiberAdamW(torch.optim.Optimizer):
     def enable_graph_mode(self):
         if not self._tables:
             raise lib.FiberHipError("FiberAdamW.enable_graph_mode: take one eager step first (device tables not built yet)")
+        self._check_uniform_steps("enable_graph_mode")
         dev = next(p for g in self.param_groups for p in g["params"]).device
         n = len(self.param_groups)
         self._hyper = torch.zeros((n, 2), dtype=torch.float32, device=dev)
@@ -66,10 +68,20 @@ class FiberAdamW(torch.optim.Optimizer):
     def disable_graph_mode(self):
         self._hyper = None
 
+    def _check_uniform_steps(self, who):
+        """The device `hyper` row holds ONE bias-corrected step size per group: a group whose members have taken different numbers
+        of steps (a parameter that got its first gradient later, a loaded state dict) cannot be replayed from it."""
+        for gi, tab in self._tables.items():
+            steps = {st["step"] for st in tab["states"]}
+            if len(steps) > 1:
+                raise lib.FiberHipError(f"FiberAdamW.{who}: the parameters of group {gi} have taken different numbers of steps "
+                                        f"({sorted(steps)}); graph mode keeps one step count per group")
+
     def prepare_replay(self):
         # The host runs ahead of the GPU (replays are asynchronous), so the upload must not read host memory that a LATER
         # prepare_replay() may already have overwritten: a FRESH pageable host tensor per call -- the runtime stages a pageable
         # source before copy_() returns (as for the pointer tables in step()), so step k's graph always sees step k's values.
+        self._check_uniform_steps("prepare_replay")
         dev_t = self._hyper
         host_t = torch.zeros(tuple(dev_t.shape), dtype=torch.float32)
         for gi, group in enumerate(self.param_groups):
@@ -108,6 +120,20 @@ class FiberAdamW(torch.optim.Optimizer):
             st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
         return st
+
+    def _split_by_step(self, tab):
+        """Members of one table whose step counts differ: one launch per distinct count, each over that count's chunks of the SAME
+        pointer table.  Which members go together does not change while they step together, so the chunk lists are kept."""
+        steps = [st["step"] for st in tab["states"]]
+        sig = tuple(s - steps[0] for s in steps)
+        if tab.get("split_sig") != sig:
+            host = tab["chunks"].cpu()
+            tab["split"] = []
+            for d in sorted(set(sig)):
+                rows = host[torch.tensor([sig[i] == d for i in host[:, 0].tolist()])]
+                tab["split"].append((d, rows.contiguous().to(tab["chunks"].device), rows.shape[0]))
+            tab["split_sig"] = sig
+        return [(steps[0] + d, chunks, n) for d, chunks, n in tab["split"]]
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -160,15 +186,21 @@ class FiberAdamW(torch.optim.Optimizer):
                 tab["key"] = key
             b1, b2 = group["betas"]
             if self._hyper is None:
-                step = tab["states"][0]["step"] + 1
-                for st in tab["states"]:
-                    st["step"] = step
+                for st in tab["states"]:           # the rule counts per parameter: only members that have a gradient advance
+                    st["step"] += 1
+                step = tab["states"][0]["step"]
+                launches = [(step, tab["chunks"], tab["n"])]
+                if any(st["step"] != step for st in tab["states"]):
+                    launches = self._split_by_step(tab)
                 hyper = None
             else:                                  # graph mode: prepare_replay() owns the counters and the device scalars
-                step = max(1, tab["states"][0]["step"])
+                if any(st["step"] != tab["states"][0]["step"] for st in tab["states"]):
+                    self._check_uniform_steps("step")
+                launches = [(max(1, tab["states"][0]["step"]), tab["chunks"], tab["n"])]
                 hyper = self._hyper[gi].data_ptr()
-            lib.call("fiber_adamw_multi_f32", lib.ptr(tab["table"]), lib.ptr(tab["numel"]), lib.ptr(tab["chunks"]), tab["n"],
-                     float(group["lr"]), float(group["weight_decay"]), float(b1), float(b2), float(group["eps"]), int(step), hyper)
+            for step, chunks, n in launches:
+                lib.call("fiber_adamw_multi_f32", lib.ptr(tab["table"]), lib.ptr(tab["numel"]), lib.ptr(chunks), n,
+                         float(group["lr"]), float(group["weight_decay"]), float(b1), float(b2), float(group["eps"]), int(step), hyper)
             ops.restamp_bf16_copies(plist, bump=not bumped)
             bumped = True
         if bumped:

@@ -1,6 +1,7 @@
 """GPU parity: each HIP kernel (called through the C ABI via fiber_amd.ops / fiber_amd.lib) against a plain PyTorch
 fp32 reference of the same op on identical bf16-rounded inputs.  Tolerances are rel-L2 and written per test:
 bf16 storage rounds each output to 2^-9 relative, so a single op sits at ~2-3e-3."""
+import copy
 import math
 
 import pytest
@@ -744,6 +745,97 @@ def test_adamw_load_state_dict_and_moved_storage(ops):
         assert torch.allclose(pb, pr, rtol=2e-6, atol=1e-7), (pb - pr).abs().max().item()
     sd = ob.state_dict()["state"]
     assert all(int(v["step"]) == 4 for v in sd.values())
+
+
+def _adamw_calls(monkeypatch):
+    from fiber_amd import lib
+    made, orig = [], lib.call
+
+    def counted(name, *a, **k):
+        made.append(name)
+        return orig(name, *a, **k)
+    monkeypatch.setattr(lib, "call", counted)
+    return made
+
+
+def _adamw_trio():
+    shapes = [(300, 40), (77,), ()]
+    mine = [rnd(*s, seed=i).to(DEV).requires_grad_(True) if s else torch.tensor(0.3, device=DEV, requires_grad=True)
+            for i, s in enumerate(shapes)]
+    return shapes, mine, [p.detach().clone().requires_grad_(True) for p in mine]
+
+
+def test_adamw_counts_steps_per_parameter(ops, monkeypatch):
+    """The rule (transformers 4.6.0 AdamW, HFAdamW here) keeps one step count PER PARAMETER: a parameter whose first gradient
+    arrives at optimizer step 3 gets the bias correction of ITS step 1, and one that sits a step out does not advance.  One group,
+    three parameters, five steps: parameter 2 has no gradient at steps 1-2, parameter 1 none at step 4.  Values and per-parameter
+    counts against HFAdamW after every step; a group whose members share a count is ONE kernel launch, a mixed one is one
+    launch per distinct count."""
+    from fiber_amd.optim import FiberAdamW, HFAdamW
+    shapes, mine, ref = _adamw_trio()
+    om = FiberAdamW(mine, lr=1e-2, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.01)
+    ot = HFAdamW(ref, lr=1e-2, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.01)
+    made = _adamw_calls(monkeypatch)
+    for step in range(1, 6):
+        for i, (a, b) in enumerate(zip(mine, ref)):
+            if (i == 2 and step <= 2) or (i == 1 and step == 4):
+                a.grad = b.grad = None
+                continue
+            g = rnd(*shapes[i], seed=100 * step + i).to(DEV) if shapes[i] else torch.tensor(0.1 * step, device=DEV)
+            a.grad, b.grad = g.clone(), g.clone()
+        del made[:]
+        om.step()
+        ot.step()
+        for a, b in zip(mine, ref):
+            assert torch.allclose(a, b, rtol=2e-6, atol=1e-7), (step, a.shape, (a - b).abs().max().item())
+        sm, st = om.state_dict()["state"], ot.state_dict()["state"]
+        assert {i: int(v["step"]) for i, v in sm.items()} == {i: int(v["step"]) for i, v in st.items()}, step
+        counts = {int(om.state[a]["step"]) for a in mine if a.grad is not None}
+        assert made.count("fiber_adamw_multi_f32") == len(counts), (step, counts, made)
+        assert len(counts) == {1: 1, 2: 1, 3: 2, 4: 2, 5: 3}[step]  # steps 1-2: one shared count, hence exactly one launch
+    assert {i: int(v["step"]) for i, v in om.state_dict()["state"].items()} == {0: 5, 1: 4, 2: 3}
+
+
+def test_adamw_loaded_unequal_steps_are_kept_and_graph_mode_refuses_them(ops, monkeypatch):
+    """A state dict whose members' step counts differ (3, 1, 2) is continued per parameter, not flattened to the first member's;
+    the device `hyper` row of graph mode holds one step size per group, so enable_graph_mode() / prepare_replay() raise for such a
+    group instead of flattening it."""
+    from fiber_amd import lib
+    from fiber_amd.optim import FiberAdamW, HFAdamW
+    shapes, mine, ref = _adamw_trio()
+    src = HFAdamW(ref, lr=1e-2, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.01)
+    for step in range(1, 4):                                         # reference run that ends at counts (3, 1, 2)
+        for i, b in enumerate(ref):
+            b.grad = None if (i == 1 and step < 3) or (i == 2 and step < 2) else (
+                rnd(*shapes[i], seed=100 * step + i).to(DEV) if shapes[i] else torch.tensor(0.1 * step, device=DEV))
+        src.step()
+    sd = copy.deepcopy(src.state_dict())                             # (state_dict() hands out the live moment tensors)
+    assert [int(sd["state"][i]["step"]) for i in range(3)] == [3, 1, 2]
+    with torch.no_grad():
+        for a, b in zip(mine, ref):
+            a.copy_(b)
+    om = FiberAdamW(mine, lr=1e-2, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.01)
+    om.load_state_dict(sd)
+    made = _adamw_calls(monkeypatch)
+    for step in range(4, 6):
+        for i, (a, b) in enumerate(zip(mine, ref)):
+            g = rnd(*shapes[i], seed=100 * step + i).to(DEV) if shapes[i] else torch.tensor(0.1 * step, device=DEV)
+            a.grad, b.grad = g.clone(), g.clone()
+        del made[:]
+        om.step()
+        src.step()
+        assert made.count("fiber_adamw_multi_f32") == 3             # three distinct counts
+        for a, b in zip(mine, ref):
+            assert torch.allclose(a, b, rtol=2e-6, atol=1e-7), (step, a.shape, (a - b).abs().max().item())
+        assert [int(om.state_dict()["state"][i]["step"]) for i in range(3)] == [int(src.state_dict()["state"][i]["step"]) for i in range(3)]
+    assert [int(om.state_dict()["state"][i]["step"]) for i in range(3)] == [5, 3, 4]
+    with pytest.raises(lib.FiberHipError, match="different numbers of steps"):
+        om.enable_graph_mode()
+    assert om._hyper is None
+    om._hyper = torch.zeros((1, 2), dtype=torch.float32, device=DEV)       # (a group that became mixed after graph mode was entered)
+    with pytest.raises(lib.FiberHipError, match="different numbers of steps"):
+        om.prepare_replay()
+    om.disable_graph_mode()
 
 
 @pytest.mark.parametrize("B,L,C", [(4, 576, 512), (5, 2304, 256), (3, 144, 1024), (4, 128, 64)])
