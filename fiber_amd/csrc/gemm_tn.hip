@@ -360,24 +360,6 @@ __global__ __launch_bounds__(256) void tn_fold_kernel(const float* ws, const flo
   else tn_fold_block<4>(ws, ws_cs, out, cs, S, nk4, N, blockIdx.x, row_map);
 }
 
-// The folds of MANY weight gradients in one launch (ops.py can defer them to the end of the backward pass; measured slower than the immediate
-// folds, profiles/r06_summary.md section 3).  Same per-element summation order as tn_fold_kernel: same bits.
-struct FoldDesc { const float* ws; float* out; float* cs; int S, N, nk4, block0; };   // 40 bytes (cs: NULL = no bias sums)
-
-__global__ __launch_bounds__(256) void tn_fold_multi_kernel(const FoldDesc* __restrict__ table, int ndesc) {
-  int lo = 0, hi = ndesc - 1;                              // descriptor whose block range holds blockIdx.x (block0 ascending)
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (table[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const FoldDesc d = table[lo];
-  const long blk = (long)blockIdx.x - d.block0;
-  const int ql = tn_fold_ql(d.S);
-  if (ql == 16) tn_fold_block<16>(d.ws, d.ws + (size_t)d.S * d.nk4 * 4, d.out, d.cs, d.S, d.nk4, d.N, blk, nullptr);
-  else if (ql == 8) tn_fold_block<8>(d.ws, d.ws + (size_t)d.S * d.nk4 * 4, d.out, d.cs, d.S, d.nk4, d.N, blk, nullptr);
-  else tn_fold_block<4>(d.ws, d.ws + (size_t)d.S * d.nk4 * 4, d.out, d.cs, d.S, d.nk4, d.N, blk, nullptr);
-}
-
 struct TnPlan { int ts, bkm, tiles_n, tiles_k, S, kt_per_split, nk_total; };
 
 TnPlan tn_plan(int M, int N, int K) {
@@ -417,7 +399,7 @@ extern "C" int fiber_gemm_tn_splits(int M, int N, int K) {
 // of the branch: pass 1/keep as `scale`); rows_per_sample must be a multiple of 64 then.  Without a mask every row counts.
 // N % 8 == 0, K % 8 == 0, lddy % 8 == 0, ldx % 8 == 0, 16-byte aligned bases.
 static int tn_launch(const void* dY, const void* X, float* dW, float* dbias, float* workspace, int M, int N, int K, int lddy, int ldx,
-                     const float* row_mask, int rows_per_sample, float scale, bool fold, const int* row_map, hipStream_t stream) {
+                     const float* row_mask, int rows_per_sample, float scale, const int* row_map, hipStream_t stream) {
   if (M <= 0 || N <= 0 || K <= 0) return FIBER_OK;
   if ((N & 7) || (K & 7) || (lddy & 7) || (ldx & 7)) return FIBER_EINVAL;
   if (row_mask && (rows_per_sample <= 0 || (rows_per_sample & 63))) return FIBER_EINVAL;
@@ -425,9 +407,8 @@ static int tn_launch(const void* dY, const void* X, float* dW, float* dbias, flo
   // The row permutation is applied by the fold (one index per float4 of the result), never by the GEMM's epilogue: a `row_map ? row_map[n] : n`
   // in front of each of its 128 stores per lane cost EVERY weight gradient of the step 2.8 % (profiles/r06_kernel_diff_vs_r05.log).  A
   // permuted result therefore always goes through the workspace, as ONE slab when the reduction is not split.
-  const bool via_ws = p.S > 1 || (row_map != nullptr && fold);
+  const bool via_ws = p.S > 1 || row_map != nullptr;
   if (via_ws && !workspace) return FIBER_EINVAL;
-  if (row_map && !fold) return FIBER_EINVAL;
   TnArgs a;
   a.A = (const bf16*)dY; a.B = (const bf16*)X;
   a.out = via_ws ? workspace : dW;
@@ -439,7 +420,7 @@ static int tn_launch(const void* dY, const void* X, float* dW, float* dbias, flo
   if (p.ts == 256) hipLaunchKernelGGL((gemm_tn_kernel<256, 64, 2, true>), dim3(grid), dim3(512), 0, stream, a);
   else hipLaunchKernelGGL((gemm_tn_kernel<128, 32, 4, false>), dim3(grid), dim3(256), 0, stream, a);
   FIBER_CHECK_LAUNCH();
-  if (via_ws && fold) {
+  if (via_ws) {
     const long nk4 = (long)N * K / 4;
     hipLaunchKernelGGL(tn_fold_kernel, dim3((unsigned)tn_fold_nblocks(p.S, nk4, N, dbias != nullptr)), dim3(256), 0, stream, workspace,
                        workspace + (size_t)p.S * N * K, dW, dbias, p.S, nk4, N, row_map);
@@ -451,25 +432,7 @@ static int tn_launch(const void* dY, const void* X, float* dW, float* dbias, flo
 extern "C" int fiber_gemm_tn_bf16(const void* dY, const void* X, float* dW, float* dbias, float* workspace, int M, int N, int K,
                                   int lddy, int ldx, const float* row_mask, int rows_per_sample, float scale,
                                   hipStream_t stream) {
-  return tn_launch(dY, X, dW, dbias, workspace, M, N, K, lddy, ldx, row_mask, rows_per_sample, scale, true, nullptr, stream);
-}
-
-// The same without the fold when the M reduction is split (fiber_gemm_tn_splits > 1): the slabs stay in `workspace` (S*(N*K) floats of
-// weight slabs followed by S*N floats of bias slabs) for fiber_tn_fold_multi; dW / dbias are not written.  With one split it is the call above.
-extern "C" int fiber_gemm_tn_slabs_bf16(const void* dY, const void* X, float* dW, float* dbias, float* workspace, int M, int N, int K,
-                                        int lddy, int ldx, const float* row_mask, int rows_per_sample, float scale,
-                                        hipStream_t stream) {
-  return tn_launch(dY, X, dW, dbias, workspace, M, N, K, lddy, ldx, row_mask, rows_per_sample, scale, false, nullptr, stream);
-}
-
-// table: device array of ndesc 40-byte records {ws, out, cs (8-byte pointers; cs NULL = no bias sums), int32 S, N, nk4 = N*K/4, block0},
-// block0 ascending from 0, blocks of a record = fiber_tn_fold_blocks(S, N, K, cs != NULL); nblocks = their total.
-extern "C" int fiber_tn_fold_blocks(int S, int N, int K, int has_cs) { return (int)tn_fold_nblocks(S, (long)N * K / 4, N, has_cs != 0); }
-extern "C" int fiber_tn_fold_multi(const void* table, int ndesc, int nblocks, hipStream_t stream) {
-  if (ndesc <= 0 || nblocks <= 0) return FIBER_OK;
-  hipLaunchKernelGGL(tn_fold_multi_kernel, dim3((unsigned)nblocks), dim3(256), 0, stream, (const FoldDesc*)table, ndesc);
-  FIBER_CHECK_LAUNCH();
-  return FIBER_OK;
+  return tn_launch(dY, X, dW, dbias, workspace, M, N, K, lddy, ldx, row_mask, rows_per_sample, scale, nullptr, stream);
 }
 
 // fiber_gemm_tn_bf16 with its output rows permuted on the way out: row n of dW (and entry n of dbias) is written at row_map[n] (int32 [N], a
@@ -478,6 +441,6 @@ extern "C" int fiber_tn_fold_multi(const void* table, int ndesc, int nblocks, hi
 extern "C" int fiber_gemm_tn_rowmap_bf16(const void* dY, const void* X, float* dW, float* dbias, float* workspace, int M, int N, int K,
                                          int lddy, int ldx, const float* row_mask, int rows_per_sample, float scale, const int* row_map,
                                          hipStream_t stream) {
-  return tn_launch(dY, X, dW, dbias, workspace, M, N, K, lddy, ldx, row_mask, rows_per_sample, scale, true, row_map, stream);
+  return tn_launch(dY, X, dW, dbias, workspace, M, N, K, lddy, ldx, row_mask, rows_per_sample, scale, row_map, stream);
 }
 

@@ -17,9 +17,7 @@ P, I, F, L, U64 = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_uint64
 SIGNATURES = {
     "fiber_gemm_nt_bf16": [P, P, P, P, P, P, P, I, P, I, P, I, I, I, I, I, I, I, I],
     "fiber_gemm_tn_bf16": [P, P, P, P, P, I, I, I, I, I, P, I, F],
-    "fiber_gemm_tn_slabs_bf16": [P, P, P, P, P, I, I, I, I, I, P, I, F],
     "fiber_gemm_tn_rowmap_bf16": [P, P, P, P, P, I, I, I, I, I, P, I, F, P],
-    "fiber_tn_fold_multi": [P, I, I],
     "fiber_ln_mlp_fwd_bf16": [P, P, P, P, P, P, P, P, I, I, I, F],
     "fiber_ln_mlp_bwd_bf16": [P, P, P, P, P, P, P, P, P, P, I, I, I, F],
     "fiber_layernorm_fwd_bf16": [P, P, P, P, P, P, I, I, F],
@@ -80,7 +78,7 @@ SIGNATURES = {
     "fiber_fpn_merge_bwd_bf16": [P, P, P, P, P, P, I, I, I, I, I, I],
 }
 # host-side helpers without a stream argument
-PLAIN = {"fiber_layernorm_bwd_grid": [I], "fiber_window_attn_bwd_slices": [I, I], "fiber_window_attn_colsum_rows": [I, I, I], "fiber_colsum_slabs": [I, I], "fiber_tn_fold_blocks": [I, I, I, I], "fiber_colsum_labelled_slabs": [I], "fiber_gemm_row_tile": [I, I, I], "fiber_gemm_tn_splits": [I, I, I],
+PLAIN = {"fiber_layernorm_bwd_grid": [I], "fiber_window_attn_bwd_slices": [I, I], "fiber_window_attn_colsum_rows": [I, I, I], "fiber_colsum_slabs": [I, I], "fiber_colsum_labelled_slabs": [I], "fiber_gemm_row_tile": [I, I, I], "fiber_gemm_tn_splits": [I, I, I],
          "fiber_adamw_chunk": [], "fiber_resample_ksize": [I, I], "fiber_dcn_dx_workspace": [I, I, I, I, I, I, I],
          "fiber_roberta_embed_bwd_workspace": [I, I, I], "fiber_ground_workspace": [I, I, I], "fiber_det_max_candidates": [],
          "fiber_atss_num_candidates": [P, I, I], "fiber_atss_loss_rows": [I, I]}

@@ -15,14 +15,13 @@ parameter: whoever writes that way calls `mark_weights_dirty()` afterwards -- th
 through raw pointers and keeps its side of it in step() (restamp_bf16_copies and the two one-launch refreshes).
 """
 import math
+import os
 import threading
 import weakref
 
 import torch
 
 from . import lib
-
-import os
 
 BF16 = torch.bfloat16
 # Derived copies of parameters (bf16 / transposed / permuted working copies), keyed by (kind, id(parameter)).  The parameter
@@ -40,12 +39,8 @@ def _cache_get(key, w):
 
 def _cache_put(key, stamp, value, w):
     _wcache[key] = (stamp, value, weakref.ref(w, lambda _r, k=key: _wcache.pop(k, None)))
-# (dY.W2^T)*gelu'(H) + fc1 bias gradient as ONE hand-written GEMM instead of library GEMM + gelu_bwd_colsum.  Measured at 512
-# images (tools/op_bench.py 512 mlpbwd, persistent 256x256 kernel + select-free gelu', library dgrad in NT form): 3866 vs 4294 us
-# at C=128, 2084 vs 2369 at C=256, 1284 vs 1394 at C=512, 899 vs 859 at C=1024 in round 2 (hence "auto" = below C = 1024 then).  Round 4:
-# with both wave groups of the q8 kernel in the epilogue together the gelu' form gained 5-12 %, and the whole step is 0.8 ms faster with
-# stage 3 fused as well (275.1 / 275.6 -> 274.5 / 274.7 ms, same box) -> "auto" = everywhere; FIBER_FUSED_MLP_BWD=0 / 1 forces it off / on.
-_FUSED_MLP_BWD = os.environ.get("FIBER_FUSED_MLP_BWD", "auto")
+
+
 _WIN_COLSUM = os.environ.get("FIBER_WIN_COLSUM", "0") == "1"     # dqkv column sums inside the window backward (see _WindowAttn.backward)
 
 
@@ -151,15 +146,12 @@ def refresh_transposed_copies():
 
 
 _hm_table = {}                       # device -> (members, device table, tiles)
-_HM_REFRESH = os.environ.get("FIBER_HM_REFRESH", "1") != "0"      # 0: the lazy ATen refresh in the next forward (A/B)
 
 
 def refresh_head_major_copies():
     """Rewrite every cached head-major qkv working copy (permuted bf16 weight, its transpose, permuted fp32 bias: _LinearQKVHeadMajor) from the
     fp32 parameters in ONE launch and mark it current.  Called by FiberAdamW.step() after the parameter update, like refresh_transposed_copies();
     copies the optimizer did not touch are rewritten too (same values)."""
-    if not _HM_REFRESH:
-        return
     by_dev = {}
     for key, (stamp, val, ref) in list(_wcache.items()):
         if not (isinstance(key, tuple) and key[0] == "HM"):
@@ -481,127 +473,30 @@ def lib_linear(x, w, b=None):
     return _LibLinear.apply(x, w, b)
 
 
-# Weight-gradient GEMMs on a stream of their own: an EXPERIMENT, off unless FIBER_WGRAD_STREAM=1 (ops.enable_wgrad_stream(model) is
-# called by bench.py and is a no-op without the variable).  dW is needed by nobody before the optimizer step (or DDP's bucket hook),
-# while the next layer's backward only needs dX, so the TN kernel of layer l could share the GPU with the LayerNorm / attention
-# backward of layer l - 1.  Round-6 result at B = 256, same box, interleaved: 265.1 / 266.7 ms with the second stream against 259.8 /
-# 259.8 without -- the kernels contend more than they fill each other's gaps.  (A first, racy version read 239-246 ms: its garbage
-# gradients turned every tensor into NaN after one optimizer step, and a GPU multiplying NaNs draws less power and clocks higher.)
-# Who reads dW first is autograd's AccumulateGrad node: for gradients that come out of a Python Function it CLONES them (it never
-# steals them: tools/probes/wgrad_stream_dbg5.py), on the stream that was current when the parameter's accumulator node was created.
-# So the accumulator nodes of the model's parameters are created under the weight-gradient stream and kept alive (as DDP's reducer
-# keeps them): the clone -- or the add into an existing .grad -- then runs on that stream, in order behind the TN kernel, the engine
-# makes that stream wait for whatever produced the other gradients, and at the end of backward() the caller's stream waits for it.
-_WGRAD_STREAM = [False]
-_wg_streams = {}
-_wg_pending = set()
-_wg_accumulators = {}                # id(parameter) -> (weakref to it, its AccumulateGrad node)
-
-
-def wgrad_stream(device):
-    st = _wg_streams.get(device)
-    if st is None:
-        st = _wg_streams[device] = torch.cuda.Stream(device=device)
-    return st
+# Retired entry points.  bench.py calls set_fold_defer() and enable_wgrad_stream(model) on every run, and set_wgrad_stream(True) when its
+# environment asks for the stream experiment; the two experiments behind them (weight-gradient GEMMs on a second stream, one deferred
+# multi-tensor fold) were measured slower in round 6 and removed: profiles/wgrad_experiments_retired.md.  The names stay so that the
+# benchmark runs unchanged.
+def set_fold_defer(on):
+    pass
 
 
 def enable_wgrad_stream(module, on=True):
-    """Route the weight-gradient GEMMs of `module`'s parameters (and the accumulation of ALL its gradients) to a second stream.
-    Call it after module.to(device) and BEFORE the first forward / DistributedDataParallel wrap: an accumulator node that already
-    exists keeps the stream it was created on.  enable_wgrad_stream(module, False) switches the routing of the GEMMs off again."""
-    _WGRAD_STREAM[0] = bool(on) and os.environ.get("FIBER_WGRAD_STREAM", "0") == "1"
-    if not _WGRAD_STREAM[0]:
-        return False
-    for p_ in module.parameters():
-        if not (p_.requires_grad and p_.is_cuda) or id(p_) in _wg_accumulators:
-            continue
-        with torch.cuda.stream(wgrad_stream(p_.device)):
-            node = p_.view_as(p_).grad_fn.next_functions[0][0]      # the AccumulateGrad node: created here, on this stream
-        _wg_accumulators[id(p_)] = (weakref.ref(p_, lambda _r, k=id(p_): _wg_accumulators.pop(k, None)), node)
-    return True
-
-
-def wgrad_stream_active(t):
-    """inside a backward pass (grad mode off), not during graph capture, for GEMMs worth a hand-over"""
-    return (_WGRAD_STREAM[0] and t.is_cuda and t.shape[0] >= 4096 and not torch.is_grad_enabled()
-            and not torch.cuda.is_current_stream_capturing())
+    return False
 
 
 def set_wgrad_stream(on):
-    """Raw switch (tests / probes): routes the GEMMs without touching any accumulator node."""
-    _WGRAD_STREAM[0] = bool(on)
+    if on:
+        raise lib.FiberHipError("the weight-gradient stream experiment was retired (measured slower in round 6): "
+                                "profiles/wgrad_experiments_retired.md has its numbers")
 
 
-def join_wgrad_stream():
-    """The current stream of every device with weight gradients in flight waits for them (DDP bucket hook; the autograd engine itself
-    joins the accumulation streams at the end of backward())."""
-    for dev in list(_wg_pending):
-        torch.cuda.current_stream(dev).wait_stream(_wg_streams[dev])
-    _wg_pending.clear()
-
-
-# ---- deferred folds -----------------------------------------------------------------------------------------------------------------------
-# The TN kernel splits its M reduction into S slabs and a small fold kernel sums them: 187 fold launches of ~14 us per step at the bench
-# batch.  With ops.set_fold_defer(True) a weight gradient whose value nobody needs before the end of backward() (no `post`) leaves its
-# slabs in the workspace and ONE multi-tensor launch folds them all from the autograd engine's end-of-backward callback.  Only valid
-# when autograd takes the returned tensor over as .grad without reading it (zero_grad(set_to_none=True), one process: an existing .grad
-# would be added to -- and DDP's reducer would copy it -- before the fold has run), hence opt-in.
-# Round-6 result (same box, interleaved, B = 256): 267.2 / 262.0 ms per step deferred against 261.0 / 259.6 immediate -- a fold that runs
-# right behind its GEMM reads the slabs out of the 256-MB Infinity Cache, the one launch at the end reads all 4 GB of them from HBM; at
-# B = 32 (48.5-49.7 against 48.8-48.9 ms) the step is not launch-bound either.  So bench.py / Trainer call set_fold_defer, which stays a
-# no-op unless FIBER_TN_FOLD_DEFER=1.
-_FOLD_DEFER = [False]
-_fold_pending = {}                   # device -> [(ws, dW pointer, db pointer, storage weak refs, S, N, K, stream)]
-_fold_cb = [False]                   # an end-of-backward callback is queued
-
-
-def set_fold_defer(on):
-    _FOLD_DEFER[0] = bool(on) and os.environ.get("FIBER_TN_FOLD_DEFER", "0") == "1"
-
-
-def _fold_defer_active(t):
-    if not (_FOLD_DEFER[0] and t.is_cuda) or torch.is_grad_enabled() or torch.cuda.is_current_stream_capturing():
-        return False
-    import torch.distributed as dist
-    return not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
-
-
-def flush_folds():
-    """Fold every pending weight gradient (one launch per device) on the current stream, behind the streams their GEMMs ran on.
-    Runs as the autograd engine's end-of-backward callback; the optimizer calls it as well (a backward that raised never ran its callbacks)."""
-    _fold_cb[0] = False
-    for dev, items in list(_fold_pending.items()):
-        if not items:
-            continue
-        with torch.cuda.device(dev):
-            cur = torch.cuda.current_stream(dev)
-            rows, block0 = [], 0
-            for ws, dwp, dbp, alive, S, N, K, st in items:
-                # the outputs are NOT held here (a second reference would make autograd copy them instead of taking them over as .grad);
-                # their storages must still be alive -- a gradient that was copied after all has been freed by now
-                if any(w_.expired() for w_ in alive):
-                    raise lib.FiberHipError("a weight gradient with a deferred fold was copied, not taken over, by autograd "
-                                            "(ops.set_fold_defer needs .grad = None before backward, one process, no gradient hooks)")
-                if st != cur:
-                    cur.wait_stream(st)
-                    ws.record_stream(cur)
-                nk4 = N * K // 4
-                rows.append((ws.data_ptr(), dwp, dbp, S | (N << 32), nk4 | (block0 << 32)))
-                block0 += lib.plain("fiber_tn_fold_blocks", S, N, K, 1 if dbp else 0)
-            table = torch.tensor(rows, dtype=torch.int64).to(dev)      # (blocking: the host staging tensor dies with this statement)
-            lib.call("fiber_tn_fold_multi", lib.ptr(table), len(rows), block0)
-        items.clear()
-    _fold_pending.clear()
-
-
-def wgrad(dh, x2, want_bias=False, row_mask=None, scale=1.0, post=None, row_map=None):
+def wgrad(dh, x2, want_bias=False, row_mask=None, scale=1.0, row_map=None):
     """dW[N,K] = dh[M,N]^T . x2[M,K] in fp32 on the hand-written TN kernel (csrc/gemm_tn.hip): both operands are read as
     they lie (row-major, M slow) and transposed on the LDS -> register path; the M reduction is split inside the launch
     (fp32 slabs + one fold).  want_bias: also return the column sums of dh (the bias gradient) from the same pass.
     row_mask / scale: DropPath backward folded in -- samples whose factor in `row_mask` is 0 are skipped, the result is
     multiplied by `scale` (= 1/keep); see droppath_foldable().
-    post(dw, db): anything the caller computes FROM the result (row permutations, reshapes, the LayerNorm unfolding of ops._LnMlp)
-    -- it runs on the stream the kernel ran on, and its return value is returned instead of (dw, db).
     row_map (int32 [N], a permutation): row n of the result (entry n of the bias sums) is written at row_map[n]."""
     M, N = dh.shape
     K = x2.shape[1]
@@ -613,39 +508,11 @@ def wgrad(dh, x2, want_bias=False, row_mask=None, scale=1.0, post=None, row_map=
     rps = (M // row_mask.numel()) if row_mask is not None else 0
     args = (lib.ptr(dh), lib.ptr(x2), lib.ptr(dw), lib.ptr(db), lib.ptr(ws), M, N, K, dh.stride(0), x2.stride(0), lib.ptr(row_mask), rps,
             float(scale))
-    finish = (lambda: post(dw, db)) if post is not None else (lambda: (dw, db) if want_bias else dw)
-    if wgrad_stream_active(dh):
-        cur = torch.cuda.current_stream(dh.device)
-        side = wgrad_stream(dh.device)
-        side.wait_stream(cur)                               # the operands' producers
-        with torch.cuda.stream(side):
-            if row_map is not None:
-                lib.call("fiber_gemm_tn_rowmap_bf16", *args, lib.ptr(row_map))
-            else:
-                lib.call("fiber_gemm_tn_bf16", *args)
-            out = finish()
-        for t in (dh, x2, row_mask, ws, dw, db):            # memory handed back on `cur` must not be reused under the side stream
-            if t is not None:
-                t.record_stream(side)
-        if not _wg_pending:
-            torch.autograd.Variable._execution_engine.queue_callback(join_wgrad_stream)    # end of this backward pass
-        _wg_pending.add(dh.device)
-        return out
-    if S > 1 and post is None and row_map is None and _fold_defer_active(dh):
-        lib.call("fiber_gemm_tn_slabs_bf16", *args)
-        if not _fold_cb[0]:
-            torch.autograd.Variable._execution_engine.queue_callback(flush_folds)          # end of this backward pass
-            _fold_cb[0] = True
-        from torch.multiprocessing.reductions import StorageWeakRef
-        alive = [StorageWeakRef(t.untyped_storage()) for t in (dw, db) if t is not None]
-        _fold_pending.setdefault(dh.device, []).append((ws, dw.data_ptr(), db.data_ptr() if db is not None else 0, alive, S, N, K,
-                                                        torch.cuda.current_stream(dh.device)))
-        return finish()
     if row_map is not None:
         lib.call("fiber_gemm_tn_rowmap_bf16", *args, lib.ptr(row_map))
     else:
         lib.call("fiber_gemm_tn_bf16", *args)
-    return finish()
+    return (dw, db) if want_bias else dw
 
 
 def droppath_foldable(rows, rowscale, rs_value):
@@ -653,20 +520,14 @@ def droppath_foldable(rows, rowscale, rs_value):
     its own -- (s dY) W = s (dY W) in the dgrad epilogue, dW = (1/keep) * sum over kept samples in the weight-gradient kernel --
     when the caller knows 1/keep (`rs_value`) and a sample's rows are whole 64-row K tiles (true for Swin stages 0-2 at
     384^2: 9216 / 2304 / 576 tokens per image; stage 3 has 144)."""
-    return (_DROPPATH_FOLD and rowscale is not None and rs_value and rows % rowscale.numel() == 0
+    return (rowscale is not None and rs_value and rows % rowscale.numel() == 0
             and (rows // rowscale.numel()) % 64 == 0)
-
-
-_DROPPATH_FOLD = os.environ.get("FIBER_DROPPATH_FOLD", "1") != "0"      # A/B switch (tools): 0 = the separate s_b * dy pass
-
 
 
 # Column sums that a backward kernel produced together with its output (window attention: the qkv bias gradient).  The
 # producer leaves (data_ptr, shape, sums) here; the NEXT linear backward takes the slot -- and uses it only if it is about
 # the very tensor it received as dY.  Every linear backward clears the slot, so it can never be matched against a later
 # tensor that happens to reuse the address; a missed hand-over only costs the separate column-sum pass.
-import threading
-
 _hint_tls = threading.local()          # one hand-over slot per autograd thread (one per device): no cross-thread coupling
 
 
@@ -821,7 +682,10 @@ class _MLP(torch.autograd.Function):
         dy2 = _c(dy).view(-1, w2.shape[0])
         db2 = None
         C, C4 = dy2.shape[1], h.shape[1]
-        fused = C % 64 == 0 and C4 % 8 == 0 and _FUSED_MLP_BWD != "0"
+        # (dY.W2^T)*gelu'(H) + fc1 bias gradient as ONE hand-written GEMM instead of dgrad + gelu_bwd_colsum, wherever the shape allows.
+        # tools/op_bench.py 512 mlpbwd: 3866 vs 4294 us at C=128, 2084 vs 2369 at C=256, 1284 vs 1394 at C=512 (round 2); since round 4
+        # (both wave groups of the q8 kernel in the epilogue together, +5-12 %) at C=1024 too: 275.1 / 275.6 -> 274.5 / 274.7 ms per step.
+        fused = C % 64 == 0 and C4 % 8 == 0
         fold = fused and dy2.shape[1] % 8 == 0 and droppath_foldable(dy2.shape[0], rowscale, ctx.rs_value)
         rs_arg, rps, mask, scale = None, 0, None, 1.0
         if fold:                                       # DropPath factor rides in the gelu' GEMM epilogue and the wgrad kernel
@@ -837,7 +701,7 @@ class _MLP(torch.autograd.Function):
         if fused:
             dh, _ = gemm_nt(dy2, bf16_weight_t(w2), None, None, 2, False, rs_arg, rps, aux=h)
             db1 = None
-        else:                                         # shapes the DMA kernel does not cover (e.g. Swin-T C=96), or FIBER_FUSED_MLP_BWD=0
+        else:                                         # shapes the DMA kernel does not cover (e.g. Swin-T C=96)
             dh, db1 = gelu_bwd_colsum(_dgrad(dy2, w2), h)
         if db2 is None:
             dw2, db2 = wgrad(dy2, g, want_bias=True, row_mask=mask, scale=scale)
@@ -857,7 +721,6 @@ def mlp(x, w1, b1, w2, b2, residual=None, rowscale=None, rowscale_value=None):
 
 
 # ---- LayerNorm + Mlp + DropPath + residual as one kernel per direction (csrc/mlp_rows.hip; Swin stages with C = 128 / 256) -------------
-_LN_MLP = os.environ.get("FIBER_LN_MLP", "1") != "0"          # A/B switch: 0 = layernorm_res + mlp (separate kernels)
 _fa_perms = {}
 
 
@@ -896,14 +759,14 @@ def _ln_mlp_weights(gamma, beta, w1, b1, w2):
     return val[:5]
 
 
-# widths the fused kernels are USED at (they exist for 128 and 256; FIBER_LN_MLP_WIDTHS=128,256 for A/B runs).  Measured at 512 images,
+# widths the fused kernels are USED at (they exist for 128 and 256).  Measured at 512 images,
 # forward + backward (tools/lnmlp_bench.py, gpurun_out/r06_lnmlp_bench_5.log): C = 128 9.24 ms against 11.11 ms for the separate kernels,
 # C = 256 6.68 against 6.12 (one wave per SIMD at that width: nothing runs under its GELU arithmetic) -- so 128 only.
-_LN_MLP_WIDTHS = tuple(int(v) for v in os.environ.get("FIBER_LN_MLP_WIDTHS", "128").split(",") if v)
+_LN_MLP_WIDTHS = (128,)
 
 
 def ln_mlp_eligible(x, C):
-    return _LN_MLP and C in _LN_MLP_WIDTHS and C in (128, 256) and x.is_cuda and x.dtype == BF16 and f32_of(x) is None
+    return C in _LN_MLP_WIDTHS and C in (128, 256) and x.is_cuda and x.dtype == BF16 and f32_of(x) is None
 
 
 class _LnMlp(torch.autograd.Function):
@@ -945,11 +808,10 @@ class _LnMlp(torch.autograd.Function):
         lib.call("fiber_ln_mlp_bwd_bf16", lib.ptr(x2), lib.ptr(dy2), lib.ptr(w1p), lib.ptr(b1p), lib.ptr(w2tp), lib.ptr(w1tp),
                  lib.ptr(rowscale), lib.ptr(dx), lib.ptr(dh), lib.ptr(xhat), M, C, rps, ctx.eps)
         w1f, gf, bf_ = w1.detach().float(), gamma.detach().float(), beta.detach().float()
-
-        def unfold(dw1p, db1):      # gradients of LayerNorm's gamma / beta and of W1 out of dW1' (xn = xhat gamma + beta feeds fc1)
-            return (dw1p * w1f).sum(0), torch.mv(w1f.t(), db1), torch.addcmul(torch.outer(db1, bf_), dw1p, gf[None, :]), db1
-        dgamma, dbeta, dw1, db1 = wgrad(dh, xhat, want_bias=True, post=unfold)
-        del dh, xhat
+        dw1p, db1 = wgrad(dh, xhat, want_bias=True)
+        # gradients of LayerNorm's gamma / beta and of W1 out of dW1' (xn = xhat gamma + beta feeds fc1)
+        dgamma, dbeta, dw1 = (dw1p * w1f).sum(0), torch.mv(w1f.t(), db1), torch.addcmul(torch.outer(db1, bf_), dw1p, gf[None, :])
+        del dh, xhat, dw1p
         if rowscale is None:
             dw2, db2 = wgrad(dy2, g, want_bias=True)
         elif droppath_foldable(M, rowscale, ctx.rs_value):
@@ -1171,9 +1033,6 @@ def _qkv_perm(C, heads, device):
     return _perm_cache[key]
 
 
-_TN_ROWMAP = os.environ.get("FIBER_TN_ROWMAP", "1") != "0"
-
-
 def _qkv_perm32(C, heads, device):
     key = ("i32", C, heads, str(device))
     if key not in _perm_cache:
@@ -1212,16 +1071,11 @@ class _LinearQKVHeadMajor(torch.autograd.Function):
         perm, inv = _qkv_perm(weight.shape[1], ctx.heads, dy.device)
         wp, _, wpt = _wcache[("HM", id(weight))][1][:3]
         dx = gemm_nt(dy2, wpt)[0].view(ctx.shp)
-        if _TN_ROWMAP:                                      # row r' of the head-major gradient is written at row perm[r'] by the kernel
-            pmap = _qkv_perm32(weight.shape[1], ctx.heads, dy.device)
-            if hint is not None:
-                dw, db = wgrad(dy2, x2, row_map=pmap), hint[inv]
-            else:
-                dw, db = wgrad(dy2, x2, want_bias=True, row_map=pmap)
-        elif hint is not None:                             # (A/B: FIBER_TN_ROWMAP=0 -- index kernels behind the GEMM)
-            dw, db = wgrad(dy2, x2, post=lambda w_, _b: w_[inv]), hint[inv]
+        pmap = _qkv_perm32(weight.shape[1], ctx.heads, dy.device)     # row r' of the head-major gradient is written at row perm[r'] by the kernel
+        if hint is not None:
+            dw, db = wgrad(dy2, x2, row_map=pmap), hint[inv]
         else:
-            dw, db = wgrad(dy2, x2, want_bias=True, post=lambda w_, b_: (w_[inv], b_[inv]))
+            dw, db = wgrad(dy2, x2, want_bias=True, row_map=pmap)
         return dx, dw, db, None
 
 
@@ -1238,7 +1092,6 @@ def linear_qkv_head_major(x, weight, bias, heads):
 # storage) -- no per-step gather of either.  One forward GEMM, one dgrad, one wgrad (+ fold) instead of three each, and no
 # autograd fan-in adds of the three input gradients.
 _packs = {}
-_NO_PACK = os.environ.get("FIBER_NO_PACK", "0") == "1"      # A/B and debugging: separate GEMMs + cat
 
 
 def _pack_views_ok(pk, ws):
@@ -1357,7 +1210,7 @@ def linear_packed(x, linears, fork_sink=None):
     weights = [w for w, _ in linears]
     biases = [b for _, b in linears]
     K = weights[0].shape[1]
-    if (_NO_PACK or any(w.shape[1] != K or w.shape[0] % 8 for w in weights) or K % 8
+    if (any(w.shape[1] != K or w.shape[0] % 8 for w in weights) or K % 8
             or any((b is None) != (biases[0] is None) for b in biases)):
         return torch.cat([linear(x, w, b) for w, b in linears], dim=-1)
     flat = [t for pair in zip(weights, biases) for t in pair]
@@ -1820,11 +1673,9 @@ class _PatchEmbedProj(torch.autograd.Function):
     def backward(ctx, dy):
         (cols,) = ctx.saved_tensors
         dy2 = _c(dy).view(-1, dy.shape[-1])
-        def crop(w_, b_):                                   # a fresh tensor, not a view of a temporary: autograd takes it over as .grad
-            out = torch.empty(ctx.wshape, dtype=w_.dtype, device=w_.device)
-            out.view(w_.shape[0], 48).copy_(w_[:, :48])
-            return out, b_
-        dw, db = wgrad(dy2, cols, want_bias=True, post=crop)
+        w_, db = wgrad(dy2, cols, want_bias=True)
+        dw = torch.empty(ctx.wshape, dtype=w_.dtype, device=w_.device)    # a fresh tensor, not a view of a temporary: autograd takes it over as .grad
+        dw.view(w_.shape[0], 48).copy_(w_[:, :48])
         return None, dw, db, None
 
 
@@ -1920,8 +1771,8 @@ class _DeformConv(torch.autograd.Function):
                 dx = dxf.to(BF16)
         need_db = ctx.has_bias and ctx.needs_input_grad[4]
         if ctx.needs_input_grad[3]:
-            dw, db = wgrad(dy2, cols, want_bias=need_db, post=lambda w_, b_: (
-                w_[:Cout].view(Cout, kh, kw, C).permute(0, 3, 1, 2).contiguous(), b_[:Cout] if b_ is not None else None))
+            w_, b_ = wgrad(dy2, cols, want_bias=True) if need_db else (wgrad(dy2, cols), None)
+            dw, db = w_[:Cout].view(Cout, kh, kw, C).permute(0, 3, 1, 2).contiguous(), b_[:Cout] if b_ is not None else None
         elif need_db:
             db = colsum(dy2)[:Cout]
         return dx, doff, dmask, dw, db, None, None, None
@@ -1959,8 +1810,7 @@ def _ground_operand_grads(ctx, ds, x16, p16):
             lib.call("fiber_gemm_nt_bf16", lib.ptr(ds[b]), lib.ptr(pt[b]), None, None, lib.ptr(dx[b]), None, None, 0, None, 0, None,
                      A, pt.shape[1], T, T, T, pt.shape[1], 0, 0)
     if ctx.needs_input_grad[1]:
-        # dP is an ACTIVATION gradient (it flows on into the text projection), so it stays on the current stream and is folded at once:
-        # wgrad()'s side stream and deferred fold are for parameter gradients that nothing reads before the backward pass ends
+        # dP is an ACTIVATION gradient (it flows on into the text projection); P differs per image, so the TN kernel is called image by image
         C = x16.shape[2]
         dp = torch.empty((B, T, C), dtype=torch.float32, device=ds.device)
         S = lib.plain("fiber_gemm_tn_splits", A, T, C)

@@ -224,35 +224,6 @@ def test_wgrad_tn_path(ops, M, N, K, bias, rps, rowmap):
         assert_elementwise(f"db tile {tile} S {S}", db, refb, 2.0 ** -22 * refb.abs() + C_TN * termb)
 
 
-def test_wgrad_tn_slabs_fold_multi_bitwise(ops):
-    """Slabs + ONE fiber_tn_fold_multi over several weight gradients (fold widths 4, 8, 16, with and without bias sums) give the bits
-    of the immediate fold."""
-    from fiber_amd import lib
-    rows, block0, keep_alive, want = [], 0, [], []
-    for (M, N, K), with_bias in (((3000, 136, 104), True), ((20000, 264, 200), False), ((40000, 136, 104), True)):
-        S = lib.plain("fiber_gemm_tn_splits", M, N, K)
-        assert S > 1
-        dy, x = _tn_inputs(M, N, K, seed=3)
-        ref = ops.wgrad(dy, x, want_bias=with_bias)
-        want.append(ref)
-        dw = torch.empty(N, K, dtype=torch.float32, device=DEV)
-        db = torch.empty(N, dtype=torch.float32, device=DEV) if with_bias else None
-        ws = torch.empty(S * (N * K + N), dtype=torch.float32, device=DEV)
-        lib.call("fiber_gemm_tn_slabs_bf16", lib.ptr(dy), lib.ptr(x), lib.ptr(dw), lib.ptr(db), lib.ptr(ws), M, N, K, dy.stride(0),
-                 x.stride(0), None, 0, 1.0)
-        rows.append((ws.data_ptr(), dw.data_ptr(), db.data_ptr() if with_bias else 0, S | (N << 32), (N * K // 4) | (block0 << 32)))
-        block0 += lib.plain("fiber_tn_fold_blocks", S, N, K, 1 if with_bias else 0)
-        keep_alive.append((dy, x, ws, dw, db))
-    table = torch.tensor(rows, dtype=torch.int64).to(DEV)
-    lib.call("fiber_tn_fold_multi", lib.ptr(table), len(rows), block0)
-    torch.cuda.synchronize()
-    for ref, (_, _, _, dw, db) in zip(want, keep_alive):
-        if db is None:
-            assert torch.equal(dw, ref)
-        else:
-            assert torch.equal(dw, ref[0]) and torch.equal(db, ref[1])
-
-
 # ---- GELU: the whole bf16 grid of [-12, 12] --------------------------------------------------------------------------------------------
 def _bf16_grid():
     v = torch.arange(-32768, 32768, dtype=torch.int32).to(torch.int16).view(torch.bfloat16).float()

@@ -215,105 +215,3 @@ def test_fused_path_forward_gap_fp32_stream(case):
     assert max(g32) < 3e-3 and sum(g32) / len(g32) < 1.5e-3, (g32, l32)
     assert max(g16) < 6e-3 and sum(g16) / len(g16) < 2.5e-3, (g16, l16)
     assert sum(g32) <= sum(g16) + 2e-3, "the fp32 stream must not be further from the oracle than the bf16 stream"
-
-
-# Parameters whose gradients may differ in the last bits between two runs of the same step (compared by value instead).  None: the
-# embedding tables, the embeddings LayerNorm and the alpha_i2t / alpha_t2i gates are all summed in a fixed order now.
-BY_VALUE = ()
-
-
-def _by_value(name):
-    return name.startswith(BY_VALUE)
-
-
-def test_weight_gradients_on_their_own_stream_are_the_same_gradients(monkeypatch):
-    """ops.enable_wgrad_stream(model): the TN weight-gradient GEMMs (and whatever the callers derive from their results) run on a second
-    stream, autograd accumulates every gradient of the model on that stream, and backward() joins it.  Same kernels, same inputs: every parameter gradient must be BITWISE the
-    one of the single-stream run (a consumer that read a gradient before the side stream had written it would show up here), three
-    times in a row, on a path that has every kind of caller (head-major qkv permutation, packed projections, patch embedding,
-    the fused LayerNorm-Mlp unfolding at C = 128)."""
-    from fiber_amd import ops
-    from fiber_amd.config import make_config
-    from fiber_amd.modules import FIBERTransformerSS, fiber_utils
-    from oracle import cases, detgen
-    cfg = dict(cases.SWIN_B)
-    torch.manual_seed(0)
-    model = FIBERTransformerSS(make_config(**cfg)).eval()           # eval: no dropout / DropPath draws, both runs compute the same function
-    for n, p in model.named_parameters():
-        if "alpha_" in n:
-            p.data.fill_(0.5)
-    model.to("cuda")
-    fiber_utils.set_task(model)
-    b = detgen.synth_batch(8, 384, 40, 50265, seed=5, min_len=8)
-    bd = {k: (v.to("cuda") if isinstance(v, torch.Tensor) else [t.to("cuda") for t in v] if isinstance(v, list) and isinstance(v[0], torch.Tensor) else v)
-          for k, v in b.items()}
-    bd["itm_labels_override"] = bd["itm_labels"]
-
-    monkeypatch.setenv("FIBER_WGRAD_STREAM", "1")            # (the switch is an experiment: off unless the variable is set)
-    ops.enable_wgrad_stream(model)                           # accumulator nodes on the weight-gradient stream (before the first forward)
-
-    def grads(on):
-        ops.set_wgrad_stream(on)
-        try:
-            model.zero_grad(set_to_none=True)
-            out = model(bd)
-            sum(v for k, v in out.items() if "loss" in k).backward()
-            torch.cuda.synchronize()
-            return {n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None}
-        finally:
-            ops.set_wgrad_stream(False)
-    ref = grads(False)
-    for rep in range(3):
-        got = grads(True)
-        assert got.keys() == ref.keys()
-        bad = [n for n in ref if not torch.equal(ref[n], got[n])]
-        assert not [n for n in bad if not _by_value(n)], (rep, [n for n in bad if not _by_value(n)][:8])
-        really = [n for n in bad if (ref[n].float() - got[n].float()).abs().max() > 1e-3 * (ref[n].float().abs().max() + 1e-6)]
-        assert not really, (rep, really[:8])
-
-
-def test_deferred_folds_give_the_same_gradients_bitwise(monkeypatch):
-    """ops.set_fold_defer(True): the slabs of the split weight-gradient GEMMs are folded by ONE multi-tensor launch at the end of
-    backward() instead of one small launch per GEMM -- the same per-element summation order, so every gradient must be bitwise the one
-    of the immediate folds (every gradient: BY_VALUE is empty), twice in a row, optimizer step included
-    (the second run starts from weights the first run's deferred gradients produced)."""
-    from fiber_amd import ops, parallel
-    from fiber_amd.config import make_config
-    from fiber_amd.modules import FIBERTransformerSS, fiber_utils
-    from oracle import cases, detgen
-    monkeypatch.setenv("FIBER_TN_FOLD_DEFER", "1")           # (the switch is an experiment: off unless the variable is set)
-    b = detgen.synth_batch(4, 224, 40, 50265, seed=6, min_len=8)
-    bd = {k: (v.to("cuda") if isinstance(v, torch.Tensor) else [t.to("cuda") for t in v] if isinstance(v, list) and isinstance(v[0], torch.Tensor) else v)
-          for k, v in b.items()}
-    bd["itm_labels_override"] = bd["itm_labels"]
-
-    def run(defer):
-        torch.manual_seed(0)
-        model = FIBERTransformerSS(make_config(**dict(cases.SWIN_T), learning_rate=1e-4, warmup_steps=0, max_steps=100)).eval()
-        for n, p in model.named_parameters():
-            if "alpha_" in n:
-                p.data.fill_(0.5)
-        model.to("cuda")
-        fiber_utils.set_task(model)
-        parallel.freeze_unused(model, model.unused_parameter_names())
-        (opt,), _ = model.configure_optimizers()
-        ops.set_fold_defer(defer)
-        try:
-            out = []
-            for _ in range(2):
-                opt.zero_grad(set_to_none=True)
-                o = model(bd)
-                sum(v for k, v in o.items() if "loss" in k).backward()
-                torch.cuda.synchronize()
-                out.append({n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None})
-                opt.step()
-            return out
-        finally:
-            ops.set_fold_defer(False)
-    ref, got = run(False), run(True)
-    for step in range(2):
-        assert ref[step].keys() == got[step].keys()
-        bad = [n for n in ref[step] if not torch.equal(ref[step][n], got[step][n])]
-        assert not [n for n in bad if not _by_value(n)], (step, [n for n in bad if not _by_value(n)][:8])
-        really = [n for n in bad if (ref[step][n].float() - got[step][n].float()).abs().max() > 1e-3 * (ref[step][n].float().abs().max() + 1e-6)]
-        assert not really, (step, really[:8])

@@ -1,8 +1,11 @@
 """Host-side logic of fiber_amd/ops.py that needs no GPU: the one-shot hand-over of column sums from a producing backward
-(window attention: the qkv bias gradient) to the linear backward that follows it."""
+(window attention: the qkv bias gradient) to the linear backward that follows it; the retired entry points the benchmark still calls."""
+import inspect
+
+import pytest
 import torch
 
-from fiber_amd import ops
+from fiber_amd import lib, ops
 
 
 class _Producer(torch.autograd.Function):
@@ -72,3 +75,17 @@ def test_colsum_handover_matches_only_the_offered_tensor():
     res = []
     _Offer.apply(torch.randn(3, requires_grad=True)).sum().backward()
     assert res == [None, None]
+
+
+def test_retired_wgrad_entry_points_do_nothing_and_touch_no_device():
+    """bench.py still calls the switches of the two retired weight-gradient experiments (profiles/wgrad_experiments_retired.md): they
+    return without initialising CUDA, switching the stream experiment ON is an error, and ops.wgrad() has no `post` left."""
+    before = torch.cuda.is_initialized()
+    assert ops.set_fold_defer(True) is None
+    assert ops.enable_wgrad_stream(torch.nn.Linear(8, 8)) is False
+    assert ops.set_wgrad_stream(False) is None
+    assert torch.cuda.is_initialized() == before
+    with pytest.raises(lib.FiberHipError):
+        ops.set_wgrad_stream(True)
+    assert torch.cuda.is_initialized() == before
+    assert "post" not in inspect.signature(ops.wgrad).parameters

@@ -2,7 +2,4 @@ run() { (cd $1 && env $2 timeout 400 python bench.py --steps 30 --warmup 8 --no-
 for i in 1 2; do
 run .ab/r05 X=1
 run . X=1
-run . FIBER_LN_MLP=0
-run . FIBER_TN_ROWMAP=0
-run . FIBER_HM_REFRESH=0
 done
