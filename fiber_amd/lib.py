@@ -55,6 +55,10 @@ SIGNATURES = {
     "fiber_colsum_labelled_bf16": [P, P, P, P, I, I, L],
     "fiber_ce_bwd_bf16": [P, P, P, P, P, I, I, L],
     "fiber_adamw_multi_f32": [P, P, P, I, F, F, F, F, F, I, P],
+    "fiber_grad_sqnorm_multi_f32": [P, P, P, I, P],
+    "fiber_solver_finalize": [P, I, F, P, P, P, I, F, F, P],
+    "fiber_adamw_torch_multi_f32": [P, P, P, I, F, F, F, F, P],
+    "fiber_ema_multi_f32": [P, P, P, I, F],
     "fiber_resize_bicubic_norm_u8": [P, I, P, P, P, I, I, P, P],
     "fiber_mlm_mask_i64": [P, P, P, L, U64, C.c_uint, I, I, I, I],
     "fiber_transpose_multi_bf16": [P, I, I],

@@ -7,7 +7,11 @@ tensors (CPU wiring tests).  Parameter groups, `lr` scheduling through LambdaLR,
 any torch optimizer.
 
 Host side: the pointer / size / chunk tables of a group live on the device and are rebuilt only when something moved (a
-gradient was re-allocated, a bf16 copy appeared); the per-step work is one pass over the parameters comparing addresses."""
+gradient was re-allocated, a bf16 copy appeared); the per-step work is one pass over the parameters comparing addresses.
+
+`FiberTorchAdamW` is torch.optim.AdamW's form of the rule (decay first, eps added to the bias-corrected sqrt(v)) for the grounding
+model, on the kernels of csrc/solver.hip: full-model gradient clipping, the update of every parameter of every group and the model
+EMA in three launches, the step counts and bias corrections kept on the device."""
 import torch
 
 from . import lib, ops
@@ -205,4 +209,187 @@ class FiberAdamW(torch.optim.Optimizer):
         if bumped:
             ops.refresh_transposed_copies()            # every W^T working copy in one launch (233 strided copies per step before)
             ops.refresh_head_major_copies()            # ... and the permuted qkv copies of the window blocks (120 ATen launches per step before)
+        return loss
+
+
+class FiberTorchAdamW(torch.optim.Optimizer):
+    """torch.optim.AdamW with `clip_grad_norm_(all parameters, max_grad_norm)` in front of it and (after `attach_ema`) the model EMA
+    behind it (reference fine_grained/maskrcnn_benchmark/solver/build.py:8-55, utils/ema.py:36-45), in three launches of
+    csrc/solver.hip whatever the grouping: the sum of squares of every gradient, one workgroup that turns it into the norm, the clip
+    coefficient and each tensor's {1 - lr wd, lr / (1 - b1^t), 1 / sqrt(1 - b2^t)}, and the update.  Differences from the composition
+    it replaces, all deliberate: the gradients are left unscaled (the kernel multiplies as it reads), a step whose gradient norm is not
+    finite is skipped (what GradScaler.step does around the reference's optimizer) and counted in `skipped_steps`, and the step counts
+    live in device memory -- a skipped step does not advance them and `step()` never synchronises.  `state_dict()` is torch's layout
+    (`step` a float32 host scalar, `exp_avg`, `exp_avg_sq`); a state dict of torch.optim.AdamW over the same groups loads and
+    continues.  betas and eps are one value for all groups; lr and weight_decay are per group."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, max_grad_norm=None):
+        if max_grad_norm is not None and not max_grad_norm > 0.0:
+            raise ValueError(f"FiberTorchAdamW: max_grad_norm must be positive or None, got {max_grad_norm}")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.max_grad_norm = max_grad_norm
+        self._chunk = None
+        self._tab = None                        # the cached device tables (one set for all groups)
+        self._block = None                      # device int32[4]: {float norm, float clip coefficient, skip, skipped steps}
+        self._ema = None
+        self._ema_done = frozenset()            # ids of the parameters whose EMA the last step() wrote
+        self.rebuilds = 0
+
+    # ---- logging (device tensors: reading them synchronises, step() does not) -----------------------------------------------
+    def _state_block(self):
+        if self._block is None:
+            dev = next(p for g in self.param_groups for p in g["params"]).device
+            self._block = torch.zeros(4, dtype=torch.int32, device=dev)
+        return self._block
+
+    @property
+    def grad_norm(self):
+        return self._state_block()[0:1].view(torch.float32)[0]
+
+    @property
+    def clip_coef(self):
+        return self._state_block()[1:2].view(torch.float32)[0]
+
+    @property
+    def skipped_steps(self):
+        return self._state_block()[3]
+
+    def attach_ema(self, model_ema):
+        """From now on step() also writes `model_ema`'s copy of every parameter it updates (fiber_amd.solver.ModelEma); the rest --
+        parameters without a gradient, frozen ones, buffers -- stays with `model_ema.update()`."""
+        self._ema = model_ema
+        self._tab = None
+        if model_ema is not None:
+            model_ema._attached = self
+
+    def take_ema_done(self):
+        done, self._ema_done = self._ema_done, frozenset()
+        return done
+
+    # ---- state --------------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["state"] = {k: {kk: (torch.tensor(float(vv), dtype=torch.float32) if kk == "step" else vv) for kk, vv in st.items()}
+                       for k, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """Loaded moments and step counts live in NEW tensors: drop the cached device tables.  `step` arrives as torch writes it (a
+        host float32 scalar, or a number) and goes to the device as int32."""
+        super().load_state_dict(state_dict)
+        for p, st in self.state.items():
+            if "step" in st:
+                st["step"] = torch.tensor(int(float(st["step"])), dtype=torch.int32).to(p.device)
+        self._tab = None
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self._tab = None
+
+    def _state_of(self, p):
+        st = self.state[p]
+        if not st:
+            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                raise lib.FiberHipError("FiberTorchAdamW needs contiguous fp32 parameters on a HIP device")
+            st["step"] = None                  # placed in the table's count array by the rebuild
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return st
+
+    @staticmethod
+    def _upload(dev_t, host_t):
+        # a FRESH pageable host tensor per upload (see FiberAdamW.step): staged before copy_() returns, no synchronisation
+        dev_t.copy_(host_t, non_blocking=True)
+        return dev_t
+
+    def _rebuild(self, plist, emas):
+        self.rebuilds += 1
+        dev = plist[0].device
+        states = [self._state_of(p) for p in plist]
+        sizes = [p.numel() for p in plist]
+        n = len(plist)
+        chunks = [(i, c) for i, k in enumerate(sizes) for c in range(-(-k // self._chunk))]
+        # the counts of all members in ONE int32 array the finalize kernel walks; each state's `step` becomes a view of its word
+        zero = torch.zeros((), dtype=torch.int32, device=dev)
+        steps = torch.stack([zero if st["step"] is None else st["step"].to(device=dev, dtype=torch.int32).reshape(()) for st in states])
+        for i, st in enumerate(states):
+            st["step"] = steps[i]
+        coef = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+        fixed = torch.tensor([(p.data_ptr(), 0, st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), 0, 0 if e is None else e.data_ptr(),
+                               coef.data_ptr() + 16 * i) for i, (p, st, e) in enumerate(zip(plist, states, emas))], dtype=torch.int64)
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)      # noqa: E731
+        return {"key": None, "n": n, "nchunks": len(chunks), "states": states, "fixed": fixed, "steps": steps, "coef": coef,
+                "table": new(tuple(fixed.shape), torch.int64), "hyper": None, "lr_wd": new((n, 2), torch.float32),
+                "numel": self._upload(new((n,), torch.int64), torch.tensor(sizes, dtype=torch.int64)),
+                "chunks": self._upload(new((len(chunks), 2), torch.int32), torch.tensor(chunks, dtype=torch.int32)),
+                "partial": new((len(chunks),), torch.float64)}
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if self._chunk is None:
+            self._chunk = lib.plain("fiber_adamw_chunk")
+        plist, hyper = [], []
+        b1, b2 = self.param_groups[0]["betas"]
+        eps = self.param_groups[0]["eps"]
+        for group in self.param_groups:
+            if tuple(group["betas"]) != (b1, b2) or group["eps"] != eps:
+                raise lib.FiberHipError("FiberTorchAdamW keeps one betas / eps for all parameter groups")
+            if group.get("amsgrad") or group.get("maximize"):     # (keys a loaded torch.optim.AdamW state dict brings along)
+                raise lib.FiberHipError("FiberTorchAdamW implements neither amsgrad nor maximize")
+            row = (float(group["lr"]), float(group["weight_decay"]))
+            for p in group["params"]:
+                if p.grad is not None:
+                    plist.append(p)
+                    hyper.append(row)
+        self._ema_done = frozenset()
+        if not plist:
+            return loss
+        grads = []
+        for p in plist:
+            g = p.grad
+            if g.dtype != torch.float32 or not g.is_contiguous() or not g.is_cuda:
+                raise lib.FiberHipError("FiberTorchAdamW needs contiguous fp32 gradients on a HIP device")
+            grads.append(g.data_ptr())
+        cached = ops.bf16_copy_if_cached
+        copies = [cached(p) for p in plist]
+        emas = [None] * len(plist) if self._ema is None else [self._ema.ema_of(p) for p in plist]
+        for p, e in zip(plist, emas):
+            if e is not None and (e.dtype != torch.float32 or not e.is_contiguous() or e.device != p.device or e.shape != p.shape):
+                raise lib.FiberHipError("FiberTorchAdamW: the EMA copy of a parameter must be a contiguous fp32 tensor of its shape and device")
+        # what the cached tables were built from: parameters, their storage, the state dicts, the EMA tensors
+        members = (tuple(map(id, plist)), tuple(p.data_ptr() for p in plist), tuple(id(self.state[p]) for p in plist),
+                   tuple(0 if e is None else e.data_ptr() for e in emas))
+        key = (members, tuple(grads), tuple(0 if c is None else c.data_ptr() for c in copies))
+        tab = self._tab
+        if tab is None or tab["members"] != members:
+            tab = self._tab = self._rebuild(plist, emas)
+            tab["members"] = members
+        if tab["key"] != key:                      # gradients are re-allocated every step under zero_grad(set_to_none=True)
+            host = tab["fixed"].clone()
+            host[:, 1] = torch.tensor(key[1], dtype=torch.int64)
+            host[:, 4] = torch.tensor(key[2], dtype=torch.int64)
+            self._upload(tab["table"], host)
+            tab["key"] = key
+        if tab["hyper"] != hyper:                  # every step during warm-up, at a milestone, when the weight-decay schedule fires
+            self._upload(tab["lr_wd"], torch.tensor(hyper, dtype=torch.float32))
+            tab["hyper"] = hyper
+        block = self._state_block()
+        max_norm = float("inf") if self.max_grad_norm is None else float(self.max_grad_norm)
+        decay = 0.0 if self._ema is None else float(self._ema.decay)
+        P = lib.ptr
+        with torch.cuda.device(plist[0].device):
+            lib.call("fiber_grad_sqnorm_multi_f32", P(tab["table"]), P(tab["numel"]), P(tab["chunks"]), tab["nchunks"], P(tab["partial"]))
+            lib.call("fiber_solver_finalize", P(tab["partial"]), tab["nchunks"], max_norm, P(tab["lr_wd"]), P(tab["steps"]), P(tab["coef"]),
+                     tab["n"], float(b1), float(b2), P(block))
+            lib.call("fiber_adamw_torch_multi_f32", P(tab["table"]), P(tab["numel"]), P(tab["chunks"]), tab["nchunks"], float(b1), float(b2),
+                     float(eps), decay, P(block))
+        self._ema_done = frozenset(id(p) for p, e in zip(plist, emas) if e is not None)
+        # the generation bump makes every other derived copy stale -- the EMA model's own cached bf16 copies among them
+        ops.restamp_bf16_copies(plist, bump=True)
+        ops.refresh_transposed_copies()
+        ops.refresh_head_major_copies()
         return loss

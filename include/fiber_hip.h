@@ -225,6 +225,28 @@ int fiber_adamw_multi_f32(const long long* table, const long long* numel, const 
  * records {const bf16* src [N,K]; bf16* dst [K,N]; int32 N, K, tile0, tiles_k}; tile0 ascending from 0, a weight owns
  * ceil(N/64)*ceil(K/64) tiles, tiles_k = ceil(K/64); ntiles = the total.  N % 8 == K % 8 == 0. */
 int fiber_transpose_multi_bf16(const void* table, int ndesc, int ntiles, fiber_stream_t stream);
+/* The grounding solver's optimizer step in three launches (caller side of the fine-grained path): clip_grad_norm_ over every parameter
+ * around torch.optim.AdamW with one group per parameter (maskrcnn_benchmark/solver/build.py:8-55), the non-finite skip of GradScaler.step
+ * (engine/trainer.py:162-168) and ModelEma.update (utils/ema.py:36-45).  torch's form of the rule: p *= 1 - lr wd first, then
+ * p -= lr/(1-beta1^t) m / (sqrt(v)/sqrt(1-beta2^t) + eps).  Tables in device memory: table int64[n*7] device pointers {param fp32, grad fp32,
+ * exp_avg, exp_avg_sq, bf16 copy or 0, ema fp32 or 0, coefficient row float[4]}; numel int64[n]; chunks int32[nchunks*2] (tensor, chunk)
+ * pairs of fiber_adamw_chunk() elements.
+ * fiber_grad_sqnorm_multi_f32: partial[k] (double[nchunks]) = sum of g^2 over chunk k in fp64, fixed order; reads column 1 of the table.
+ * fiber_solver_finalize (one workgroup): sum of the partials in index order; norm = sqrt(sum), c = min(1, max_norm / (norm + 1e-6)) in fp64
+ * (max_norm = +inf: clipping off).  Non-finite sum: c = 0, skip = 1, skipped_steps += 1, nothing else.  Otherwise steps[i] += 1 (int32[n]) and
+ * coef[4 i ..] = {1 - lr wd, lr/(1-beta1^t), 1/sqrt(1-beta2^t), 0} from lr_wd float[n][2], each entry computed in fp64 and rounded once.
+ * state: {float norm, float c, int32 skip, int32 skipped_steps}, zeroed once by the caller.
+ * fiber_adamw_torch_multi_f32: g' = c g; m' = b1 m + (1-b1) g'; v' = b2 v + (1-b2) g' g'; p' = p decay - s1 m' / (sqrt(v') r2 + eps);
+ * copy = bf16(p'); ema' = ema_decay ema + (1 - ema_decay) p' where an EMA pointer is given.  With skip set only the EMA moves (from the
+ * unchanged p).  Gradients are never written.
+ * fiber_ema_multi_f32: the EMA line alone over table int64[n*2] {src fp32, ema fp32} (entries the optimizer does not step). */
+int fiber_grad_sqnorm_multi_f32(const long long* table, const long long* numel, const int* chunks, int nchunks, double* partial,
+                                fiber_stream_t stream);
+int fiber_solver_finalize(const double* partial, int npartial, float max_norm, const float* lr_wd, int* steps, float* coef, int n,
+                          float beta1, float beta2, void* state, fiber_stream_t stream);
+int fiber_adamw_torch_multi_f32(const long long* table, const long long* numel, const int* chunks, int nchunks, float beta1, float beta2,
+                                float eps, float ema_decay, const void* state, fiber_stream_t stream);
+int fiber_ema_multi_f32(const long long* table, const long long* numel, const int* chunks, int nchunks, float decay, fiber_stream_t stream);
 /* Row-permuted bf16 working copies (+ their transposes, + the permuted fp32 bias) of fp32 weights in one launch after the optimizer step:
  * the head-major qkv projections of the window-attention blocks (ops._LinearQKVHeadMajor; the permutation is this implementation's, the
  * weights are WindowAttention.qkv, swin_transformer.py:197).  table: device array of ndesc 64-byte records {const float* src [N,K];
