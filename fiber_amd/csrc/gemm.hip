@@ -7,8 +7,8 @@
 // swin_transformer.py:325; roberta.py:231-241,337,398,415 query/key/value/dense layers; PatchMerging.reduction
 // swin_transformer.py:431; fiber_module.py:349-350 cross-modal transforms).
 //
-// Kernel family (CDNA4, all NT = both operands K-contiguous, v_mfma_f32_32x32x16_bf16 issued with swapped operands so each
-// lane owns 4 consecutive output columns), in the order gemm_plan() tries them:
+// Kernel family (CDNA4, all NT = both operands K-contiguous, MFMAs issued with swapped operands so each lane owns 4 consecutive
+// output columns: v_mfma_f32_16x16x32_bf16 in gemm_nt_q8_kernel, v_mfma_f32_32x32x16_bf16 in the others), in the order gemm_plan() tries them:
 //   gemm_nt_q8_kernel            256x256 tile, 8 waves in two groups, two 64-KB LDS-DMA stages re-staged a quarter at a time,
 //                                persistent over output tiles (>= 200 tiles, N % 64 == 0), wave-private epilogue with no
 //                                workgroup barrier, bias as accumulator seed                          <- the large shapes
@@ -589,22 +589,29 @@ __global__ __launch_bounds__(512) void gemm_nt_q8_kernel(GemmArgs a) {
   };
 
   // ---- MFMA side
-  f32x16 acc[TM][TN];
-  const int frow = lane & 31, fk = lane >> 5;
-  bf16x8 fa[4][2], fb[2][4];                             // A half: [k step][32-row tile];  both W halves: [half][k step]
+  // v_mfma_f32_16x16x32_bf16 (the same cycles per FLOP as 32x32x16, a higher clock under this load: profiles/mfma_shape.md; the 32x32x16 form:
+  // tools/experiments/gemm_nt_q8_kernel_mfma32.patch): a quadrant is 4 row tiles x 2 column tiles x 2 k-steps of 32 (16 MFMAs of 16 cycles), a
+  // lane holds 8 consecutive k (16-byte chunk ks * 4 + (lane >> 4)) of row lane & 15 and, as a result, columns 4 (lane >> 4) .. + 3 of output
+  // row lane & 15.  swz() stays conflict-free for these reads: a ds_read_b128 lane group {0-3, 12-15, 20-27} takes rows 0-3 and 12-15 at
+  // chunk c and rows 4-11 at chunk c ^ 1, i.e. chunks c ^ {0, 1, 6, 7} and c ^ {3, 2, 5, 4} of both 128-byte halves of the bank row.
+  q8_acc_t acc[8][4];
+  const int frow = lane & 15, fk = lane >> 4;
+  bf16x8 fa[4][2], fb[2][4];                             // A half: [16-row tile][k step];  both W halves: [half][2 * k step + 16-column tile]
   auto readA = [&](const bf16* sb, int h) {
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
+    for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-      for (int ii = 0; ii < 2; ++ii)
-        fa[ks][ii] = *reinterpret_cast<const bf16x8*>(sb + swz(wm * WTM + (2 * h + ii) * 32 + frow, ks * 2 + fk));
+      for (int it = 0; it < 4; ++it)
+        fa[it][ks] = *reinterpret_cast<const bf16x8*>(sb + swz(wm * WTM + h * 64 + it * 16 + frow, ks * 4 + fk));
   };
   auto readW = [&](const bf16* sb, int j) {
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-      fb[j][ks] = *reinterpret_cast<const bf16x8*>(sb + BM * BK + swz(wn * WTN + j * 32 + frow, ks * 2 + fk));
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int jt = 0; jt < 2; ++jt)
+        fb[j][ks * 2 + jt] = *reinterpret_cast<const bf16x8*>(sb + BM * BK + swz(wn * WTN + j * 32 + jt * 16 + frow, ks * 4 + fk));
   };
-  // bias of column block j in accumulator layout (element q*4+e <-> column j*32 + q*8 + 4*(lane>>5) + e): scalar loads, one select each
+  // bias of column block j in accumulator layout (seed_sel below): scalar loads, a one-of-four select each
   // N need only be a multiple of 64 (a wave's 64 columns are then all inside or all outside): the waves of the last tile column
   // whose columns lie past N run the K loop on clamped W rows and store nothing (Swin stage 0: qkv, N = 384 = 1.5 tiles)
   // Two steps: the scalar loads are REQUESTED in the load half of the phase, the selects that consume them sit behind the phase's barrier
@@ -625,33 +632,45 @@ __global__ __launch_bounds__(512) void gemm_nt_q8_kernel(GemmArgs a) {
     }
     return r;
   };
+  // accumulator layout: element e of column tile jt <-> column j*32 + jt*16 + 4*(lane>>4) + e: a one-of-four select (3 v_cndmask) per value;
+  // the four row tiles of a quadrant share the seed
+  struct Seed { f32x4 s[2]; };
   auto seed_sel = [&](const SeedRaw& r) {
-    f32x16 sd;
+    Seed sd;
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
+    for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) sd[q * 4 + e] = fk ? r.v[q * 8 + 4 + e] : r.v[q * 8 + e];
+      for (int e = 0; e < 4; ++e) {
+        const float lo = (fk & 1) ? r.v[jt * 16 + 4 + e] : r.v[jt * 16 + e];
+        const float hi = (fk & 1) ? r.v[jt * 16 + 12 + e] : r.v[jt * 16 + 8 + e];
+        sd.s[jt][e] = (fk & 2) ? hi : lo;
+      }
     return sd;
   };
+  // consecutive MFMAs go to different accumulators (each is met again 8 MFMAs later); only the K = 32 opcode is used
   auto mma = [&](int h, int j) {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
+    for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-      for (int ii = 0; ii < 2; ++ii)
-        acc[2 * h + ii][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[j][ks], fa[ks][ii], acc[2 * h + ii][j], 0, 0, 0);
+      for (int it = 0; it < 4; ++it)
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt)
+          acc[4 * h + it][2 * j + jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j][ks * 2 + jt], fa[it][ks], acc[4 * h + it][2 * j + jt], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
   };
-  auto mma_seeded = [&](int h, int j, const f32x16& sd) {
+  auto mma_seeded = [&](int h, int j, const Seed& sd) {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int ii = 0; ii < 2; ++ii)
-      acc[2 * h + ii][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[j][0], fa[0][ii], sd, 0, 0, 0);
+    for (int it = 0; it < 4; ++it)
 #pragma unroll
-    for (int ks = 1; ks < 4; ++ks)
+      for (int jt = 0; jt < 2; ++jt)
+        acc[4 * h + it][2 * j + jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j][jt], fa[it][0], sd.s[jt], 0, 0, 0);
 #pragma unroll
-      for (int ii = 0; ii < 2; ++ii)
-        acc[2 * h + ii][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[j][ks], fa[ks][ii], acc[2 * h + ii][j], 0, 0, 0);
+    for (int it = 0; it < 4; ++it)
+#pragma unroll
+      for (int jt = 0; jt < 2; ++jt)
+        acc[4 * h + it][2 * j + jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j][2 + jt], fa[it][1], acc[4 * h + it][2 * j + jt], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
   };
   // first barrier of a phase: the requests of this load half are out; `counted`: make everything but the three newest half-tiles
@@ -692,6 +711,7 @@ __global__ __launch_bounds__(512) void gemm_nt_q8_kernel(GemmArgs a) {
   unsigned long long t0 = 0;
   if constexpr (TRACE) t0 = __builtin_amdgcn_s_memtime();
   const unsigned long long tstart = t0;
+  unsigned long long kc = 0, kr = 0, kc0 = 0, kr0 = 0;    // K loops of this wave: shader cycles and 100-MHz ticks (their quotient = the clock held)
   auto mark = [&](int i) {
     if constexpr (TRACE) {
       const unsigned long long t = __builtin_amdgcn_s_memtime();
@@ -704,6 +724,7 @@ __global__ __launch_bounds__(512) void gemm_nt_q8_kernel(GemmArgs a) {
     const int tm0 = (id / tilesN) * BM, tn0 = (id % tilesN) * BN;
     const int n0w = tn0 + wn * WTN;
     if (!keep_stagger && wm == 1) { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
+    if constexpr (TRACE) { kc0 = __builtin_amdgcn_s_memtime(); kr0 = __builtin_amdgcn_s_memrealtime(); }
     for (int kt = 0; kt < nk; ++kt, ++g) {
       const bf16* sb = smem + (g & 1) * STAGE;
       // P1: quadrant (0, 0)
@@ -777,6 +798,7 @@ __global__ __launch_bounds__(512) void gemm_nt_q8_kernel(GemmArgs a) {
       bar_math();
       mark(15);
     }
+    if constexpr (TRACE) { kc += __builtin_amdgcn_s_memtime() - kc0; kr += __builtin_amdgcn_s_memrealtime() - kr0; }
     if (!keep_stagger && wm == 0) { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
     if constexpr (TRACE) t0 = __builtin_amdgcn_s_memtime();
     if (n0w >= a.N) {
@@ -795,6 +817,8 @@ __global__ __launch_bounds__(512) void gemm_nt_q8_kernel(GemmArgs a) {
       o[17] = (float)(__builtin_amdgcn_s_memtime() - tstart);
       o[18] = (float)nk;
       o[19] = (float)T;
+      o[20] = (float)kc;
+      o[21] = (float)kr;
     }
   }
 }

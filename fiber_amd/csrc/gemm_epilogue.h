@@ -6,6 +6,9 @@ namespace {
 
 constexpr int BK = 64;
 
+// gemm_nt_q8_kernel issues v_mfma_f32_16x16x32_bf16 (every other NT kernel 32x32x16): its accumulators as the wave epilogue takes them
+typedef f32x4 q8_acc_t;                                 // acc[8][4]: 16-row tile x 16-column tile of the wave's 128 x 64
+
 struct GemmArgs {
   const bf16* X; const bf16* W; const float* bias; const bf16* R; bf16* Y; bf16* Ypre;
   const float* rowscale;   // optional per-sample scale (timm DropPath): row m uses rowscale[m / rows_per_sample]
@@ -204,43 +207,47 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& a, f32x16 (&acc)[B
 // 4-KB LDS slab.  No workgroup barrier anywhere: the two wave groups keep their half-sub-tile stagger across output tiles, one
 // group's staging / GELU / stores run under the other group's MFMAs, and a wave's stores drain under the next tile's K loop.
 // The bias is already in the accumulators (the tile's first MFMAs are seeded with it), so EPI 0 / 1 start from acc + bias.
-//   slab image: 32 rows x 128 B; 16-byte chunk c of row r lives at chunk c ^ ((r >> 1) & 7) -- the A/B tile swizzle: the 8-byte
-//   MFMA-layout writes of 16 consecutive rows and the 16-byte row-contiguous reads of 8 lanes per row both tile the banks
+//   slab image: 32 rows x 128 B (two 16-row MFMA tiles); 16-byte chunk c of row r lives at chunk c ^ ((r >> 1) & 7) -- the A/B tile
+//   swizzle: the 8-byte MFMA-layout writes of 16 consecutive rows and the 16-byte row-contiguous reads of 8 lanes per row both tile the banks
 //   stores: 8 rows x 128 B per instruction (one whole cache line per row)
 // Column sums (EPI 2) are per 128-row wave sub-tile: `colpart` has two rows per output tile (fiber_gemm_row_tile says 128).
 template <int TM, int EPI, bool HAS_R, bool HAS_RS, bool FULL>
-__device__ __forceinline__ void wave_epilogue(const GemmArgs& a, f32x16 (&acc)[TM][2], bf16* cw, int m0w, int n0w) {
+__device__ __forceinline__ void wave_epilogue(const GemmArgs& a, q8_acc_t (&acc)[2 * TM][4], bf16* cw, int m0w, int n0w) {
   // The lane index is re-derived here (v_mbcnt, made opaque) instead of taken from threadIdx: everything below that depends on it
   // only -- slab addresses, the 16-byte column of the lane -- is otherwise hoisted out of the persistent tile loop and held in
   // registers through the K loop, which at 248+ VGPRs pushed the gelu' variants into scratch (and a scratch reload makes the
   // compiler wait vmcnt(0): a drain of the LDS-DMA stream).
   int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   asm volatile("" : "+v"(lane));
-  const int wr = lane & 31, wh = lane >> 5;              // staging: row of the slab, which 4-column half of an 8-column group
   const int rr = lane >> 3, rc = lane & 7;               // read-back: row inside an 8-row pass, 16-byte chunk of the 128-B row
   constexpr bool E0 = EPI == 0 || EPI == 3;
   constexpr bool SIDE = (HAS_R && EPI != 3) || EPI == 2;
   const bf16* sidep = EPI == 2 ? a.aux : a.R;
   const size_t sideld = EPI == 2 ? a.ldaux : a.ldr;
   const int n_out = n0w + rc * 8;
-  bf16* wbase = cw + wr * 64 + wh * 4;
-  const int wsw = (wr >> 1) & 7;
   const bf16* rbase = cw + rr * 64;
   // The LDS queue of a wave executes in order, so slab i+1 may be written right behind the reads of slab i (they still see
   // slab i) without waiting for their data: stage(i+1) / read(i+1) are issued before slab i is processed and stored, and the
   // write -> read -> return latency of a slab hides behind the previous slab's VALU work and store issue.
+  // 16x16x32 accumulators: slab rows 16 it + (lane & 15) (it = 0, 1: row tiles 2i, 2i + 1), columns 16 jt + 4 (lane >> 4) .. + 3 -- 16-byte
+  // chunk 2 jt + (lane >> 5), its (lane >> 4) & 1 half.  A ds_write_b64 lane group is 16 consecutive rows of one chunk half.
   auto stage = [&](int i) {
-    float rsc = 1.f;
-    if constexpr (E0 && HAS_RS) rsc = a.rowscale[min(m0w + i * 32 + wr, a.M - 1) / a.rows_per_sample];
+    const int g = lane >> 4;
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int it = 0; it < 2; ++it) {
+      const int row = it * 16 + (lane & 15);
+      float rsc = 1.f;
+      if constexpr (E0 && HAS_RS) rsc = a.rowscale[min(m0w + i * 32 + row, a.M - 1) / a.rows_per_sample];
+      bf16* wb16 = cw + row * 64 + (g & 1) * 4;
+      const int sw16 = (row >> 1) & 7;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
+      for (int jt = 0; jt < 4; ++jt) {
         bf16x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = f2bf((E0 && HAS_RS) ? acc[i][j][q * 4 + e] * rsc : acc[i][j][q * 4 + e]);
-        *reinterpret_cast<bf16x4*>(wbase + (((j * 4 + q) ^ wsw) << 3)) = o;
+        for (int e = 0; e < 4; ++e) o[e] = f2bf((E0 && HAS_RS) ? acc[2 * i + it][jt][e] * rsc : acc[2 * i + it][jt][e]);
+        *reinterpret_cast<bf16x4*>(wb16 + (((jt * 2 + (g >> 1)) ^ sw16) << 3)) = o;
       }
+    }
   };
   auto read_pass = [&](int pp) {
     const int row = pp * 8 + rr;

@@ -50,6 +50,10 @@ struct TnArgs {
 
 __device__ __attribute__((aligned(16))) unsigned g_tn_zeros[128];   // 512 zero bytes: the source of dY rows past M
 
+#ifdef FIBER_TN_CLOCK_PROBE   // diagnostic build only (tools/probes/mfma_shape_ab.py --clock): shader cycles and 100-MHz ticks of each workgroup's K loop
+__device__ unsigned long long g_tn_stamp[2 * 1024];
+#endif
+
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -212,6 +216,9 @@ __global__ __launch_bounds__(TS * 2) void gemm_tn_kernel(TnArgs a) {
     __builtin_amdgcn_s_setprio(0);
   };
 
+#ifdef FIBER_TN_CLOCK_PROBE
+  const unsigned long long pc0 = __builtin_amdgcn_s_memtime(), pr0 = __builtin_amdgcn_s_memrealtime();
+#endif
   if constexpr (STAG) {
     auto phase_barrier = [&](bool landed) {
       if (landed) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -261,6 +268,12 @@ __global__ __launch_bounds__(TS * 2) void gemm_tn_kernel(TnArgs a) {
     }
   }
 
+#ifdef FIBER_TN_CLOCK_PROBE
+  if (tid == 0 && blockIdx.x < 1024) {
+    g_tn_stamp[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - pc0;
+    g_tn_stamp[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - pr0;
+  }
+#endif
   // ---- epilogue: fp32 tile -> this split's slab.  Per accumulator register a half-wave writes 128 contiguous bytes.
   float* outp = a.out + (size_t)s * a.N * a.K;
   const int kcol_l = lane & 31;
@@ -388,6 +401,13 @@ TnPlan tn_plan(int M, int N, int K) {
 }  // namespace
 
 // C ABI ---------------------------------------------------------------------------------------------------------
+#ifdef FIBER_TN_CLOCK_PROBE
+// (K-loop shader cycles, 100-MHz ticks) of the first `n` <= 1024 workgroups of the last weight-gradient launch -> host_out[2 n]
+extern "C" int fiber_gemm_tn_clock_probe(unsigned long long* host_out, int n) {
+  if (n < 0 || n > 1024) return FIBER_EINVAL;
+  return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_tn_stamp), sizeof(unsigned long long) * 2 * n) == hipSuccess ? FIBER_OK : FIBER_ELAUNCH;
+}
+#endif
 // Number of M splits the kernel will use for this problem; workspace = S > 1 ? S * (N*K + N) floats : 0.
 extern "C" int fiber_gemm_tn_splits(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;

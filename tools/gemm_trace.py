@@ -14,7 +14,7 @@ def q8(M, N, K, act=0):
     y = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
     pre = torch.empty(M, N, device="cuda", dtype=torch.bfloat16) if act == 1 else None
     dbg = torch.zeros(8 * 8 * 24, device="cuda")
-    for _ in range(3):
+    for _ in range(int(os.environ.get("FIBER_TRACE_LAUNCHES", "3"))):     # (a clock reading wants >= 2 s of back-to-back launches)
         lib.call("fiber_gemm_nt_bf16", lib.ptr(x), lib.ptr(w), lib.ptr(b), None, lib.ptr(y), lib.ptr(pre), None, 0, None, 0, lib.ptr(dbg),
                  M, N, K, K, K, N, 0, 0x1000 | act)
     torch.cuda.synchronize()
@@ -26,6 +26,8 @@ def q8(M, N, K, act=0):
             r = d[wg, wv] / (T * nk)
             ph = " | ".join(f"P{p + 1} {r[4 * p]:5.0f} {r[4 * p + 1]:5.0f} {r[4 * p + 2]:5.0f} {r[4 * p + 3]:5.0f}" for p in range(4))
             print(f"wg{wg} wave{wv} g{wv // 4}: {ph} | epilogue/tile {d[wg, wv, 16] / T:7.0f} | total/Ktile {d[wg, wv, 17] / (T * nk):6.0f}")
+    clk = (d[:, :, 20] / d[:, :, 21].clamp_min(1)).flatten() * 0.1     # s_memtime ticks per 100-MHz s_memrealtime tick over the K loops -> GHz
+    print(f"in-kernel clock over the K loops: median {clk.median():.3f} GHz (min {clk.min():.3f}, max {clk.max():.3f}; 64 waves)")
 
 
 for shp in ((294912, 2048, 512), (294912, 512, 2048), (73728, 1024, 4096)):
