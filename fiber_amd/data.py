@@ -6,6 +6,11 @@ the H2D copy of the RAW sample bytes.
   * `mlm_mask` = the masking rule of `DataCollatorForLanguageModeling(mlm_probability)` used by BaseDataModule
     (datamodules/datamodule_base.py:52) -> `text_ids_mlm`, `text_labels_mlm` of the batch schema (base_dataset.py:223-243).
 
+  * `DeviceDetectionTransform` / `device_collate_grounding` = the fine-grained model's `build_transforms` (Resize(min, max) with PIL
+    BILINEAR -> RandomHorizontalFlip -> ToTensor -> Normalize(format)), `BoxList.resize` / `transpose`, `to_image_list(size_divisible)`
+    and `BatchCollator`, for the configuration every FIBER yaml uses: one ragged batch of raw uint8 images -> the padded
+    [B, 3, Hp, Wp] tensor GeneralizedVLRCNN.forward consumes, its GroundingTargets and its tokenizer_input.
+
 What stays on the host: JPEG decode (`Image.open(...).convert("RGB")`, base_dataset.py:97-103) and tokenisation -- the loader
 workers hand over uint8 [H, W, 3] arrays and int64 token ids; everything after that is stream-ordered device work, so at
 ~800 images/s per GPU the loader no longer resizes and normalises 2 x 384^2 fp32 images per sample on CPU cores.
@@ -21,6 +26,13 @@ IMAGENET_STD = (0.229, 0.224, 0.225)
 _DESC = np.dtype([("src", "<i8"), ("H", "<i4"), ("W", "<i4"), ("src_stride", "<i4"), ("ksize_h", "<i4"), ("ksize_v", "<i4"),
                   ("tmp_off", "<i4"), ("coef_h_off", "<i4"), ("coef_v_off", "<i4")])
 assert _DESC.itemsize == 40
+_DET_DESC = np.dtype([("src", "<i8"), ("H", "<i4"), ("W", "<i4"), ("src_stride", "<i4"), ("oh", "<i4"), ("ow", "<i4"), ("ksize_h", "<i4"),
+                      ("ksize_v", "<i4"), ("tmp_off", "<i4"), ("coef_h_off", "<i4"), ("coef_v_off", "<i4"), ("flip", "<i4"),
+                      ("tmp_pitch", "<i4")])
+assert _DET_DESC.itemsize == 56
+_BOX_PARAM = np.dtype([("ratio_w", "<f4"), ("ratio_h", "<f4"), ("flip", "<i4"), ("new_w", "<f4"), ("num_gt", "<i4")])
+assert _BOX_PARAM.itemsize == 20
+_M64 = (1 << 64) - 1
 
 
 class DeviceImageTransform:
@@ -86,3 +98,206 @@ def device_collate(samples, transform, seed=None, max_text_len=40, pad_id=1, dra
     for k in range(draw_false_image):
         batch[f"false_image_{k}"] = [transform([s[f"false_image_{k}"] for s in samples])]
     return batch
+
+
+# ---- the fine-grained (grounding) model's input ----------------------------------------------------------------------------------------
+def _need(cond, name, why):
+    if not cond:
+        raise NotImplementedError(f"{name}: {why}")
+
+
+def hash_u32(seed, idx):
+    """csrc/common.h hash_u32 on the host (splitmix64 finaliser of seed + idx * golden ratio, high 32 bits)."""
+    z = (seed + idx * 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return (z ^ (z >> 31)) >> 32
+
+
+def det_resize_size(w, h, size, max_size):
+    """Resize.get_size of fine_grained/maskrcnn_benchmark/data/transforms/transforms.py:94-116 for one drawn `size` -> (oh, ow)."""
+    if max_size is not None:
+        min_original_size = float(min((w, h)))
+        max_original_size = float(max((w, h)))
+        if max_original_size / min_original_size * size > max_size:
+            size = int(round(max_size * min_original_size / max_original_size))
+    if (w <= h and w == size) or (h <= w and h == size):
+        return (h, w)
+    if w < h:
+        ow = size
+        oh = int(size * h / w)
+    else:
+        oh = size
+        ow = int(size * w / h)
+    return (oh, ow)
+
+
+def _box_table(rows, dev):
+    """rows: (ratio_w, ratio_h, flip, new_w, num_gt) per image -> the device table of fiber_det_boxes_f32"""
+    t = np.zeros(len(rows), _BOX_PARAM)
+    for i, r in enumerate(rows):
+        t[i] = r
+    return torch.from_numpy(t.view(np.uint8).copy()).to(dev, non_blocking=True)
+
+
+class DetImageList:
+    """What DeviceDetectionTransform returns (the reference's ImageList plus the bookkeeping of its BoxLists): `tensors` fp32
+    [B, 3, Hp, Wp], `image_sizes` [(oh, ow)] and `original` [(orig_h, orig_w, flipped)] per image, all but `tensors` on the host."""
+
+    def __init__(self, tensors, image_sizes, original):
+        self.tensors, self.image_sizes, self.original = tensors, image_sizes, original
+
+    def to(self, device):
+        return DetImageList(self.tensors.to(device), self.image_sizes, self.original)
+
+    def box_params(self, num_gt):
+        """The forward table (original frame -> resized, flipped frame): the ratios of BoxList.resize (bounding_box.py:109), in double,
+        rounded to fp32 as the reference's tensor * python-float products round them."""
+        return [(float(ow) / float(W), float(oh) / float(H), int(f), float(ow), int(n))
+                for (oh, ow), (H, W, f), n in zip(self.image_sizes, self.original, num_gt)]
+
+    def boxes_to_original(self, detections):
+        """Detections (or a [B, D, 4] box tensor) in the resized frame -> boxes fp32 [B, D, 4] in each image's original frame: the
+        `prediction.resize((orig_w, orig_h))` of the reference's inference loop (engine/inference.py:308), with BoxList.resize's ratio rule.
+        No flip is undone: evaluation never flips."""
+        boxes = getattr(detections, "boxes", detections)
+        if boxes.dim() != 3 or boxes.shape[0] != len(self.image_sizes) or boxes.shape[2] != 4:
+            raise ValueError(f"boxes_to_original: boxes {tuple(boxes.shape)} for {len(self.image_sizes)} images")
+        out = boxes.float().clone(memory_format=torch.contiguous_format)
+        D = int(out.shape[1])
+        rows = [(float(W) / float(ow), float(H) / float(oh), 0, float(W), D) for (oh, ow), (H, W, _) in zip(self.image_sizes, self.original)]
+        table = _box_table(rows, out.device)
+        lib.call("fiber_det_boxes_f32", lib.ptr(out), lib.ptr(table), len(rows), D)
+        self._keep = table
+        return out
+
+
+class DeviceDetectionTransform:
+    """`build_transforms(cfg, is_train)` of fine_grained/maskrcnn_benchmark/data/transforms/build.py:5-43 plus `to_image_list(...,
+    DATALOADER.SIZE_DIVISIBILITY)` on the device.  images: list of uint8 [H, W, 3] RGB device tensors (ragged, row-strided views
+    allowed); seed: the 64-bit key of this batch (default ops.collate_seed()).  -> DetImageList.
+
+    The size choice and the flip are drawn on the host (the batch shape depends on them) and are a pure function of (seed, sample
+    index i): hash_u32(seed, 2 i) % len(min_size) picks the size (random.choice in the reference), hash_u32(seed, 2 i + 1) <
+    floor(p 2^32) flips.  Nothing is read back from the device."""
+
+    def __init__(self, cfg, is_train=True):
+        inp, aug = cfg.INPUT, getattr(cfg, "AUGMENT", None)
+        if is_train:
+            mult = tuple(getattr(aug, "MULT_MIN_SIZE_TRAIN", ()))
+            min_size = mult if len(mult) > 0 else inp.MIN_SIZE_TRAIN
+            max_size = inp.MAX_SIZE_TRAIN
+            flip_prob = float(getattr(aug, "FLIP_PROB_TRAIN", 0.5))
+            _need(float(getattr(aug, "VERTICAL_FLIP_PROB_TRAIN", 0.0)) == 0.0, "AUGMENT.VERTICAL_FLIP_PROB_TRAIN",
+                  "the vertical flip is not built (no FIBER yaml sets it)")
+        else:
+            min_size, max_size, flip_prob = inp.MIN_SIZE_TEST, inp.MAX_SIZE_TEST, 0.0
+        _need(not getattr(inp, "FIX_RES", False), "INPUT.FIX_RES", "the fixed (size, max_size) resolution of Resize(restrict=True) is not built")
+        fmt = getattr(inp, "FORMAT", "")
+        if fmt == "":
+            if not getattr(inp, "TO_BGR255", False):
+                raise ValueError("INPUT.FORMAT is empty and INPUT.TO_BGR255 is false: build_transforms defines no input format")
+            fmt = "bgr255"
+        fmt = fmt.lower()
+        self.min_size = tuple(int(v) for v in (min_size if isinstance(min_size, (list, tuple)) else (min_size,)))
+        self.max_size = None if max_size is None else int(max_size)
+        self.flip_threshold = int(flip_prob * 2 ** 32)
+        self.bgr, self.times255 = int("bgr" in fmt), int("255" in fmt)
+        self.mean = (lib.C.c_float * 3)(*inp.PIXEL_MEAN)
+        self.std = (lib.C.c_float * 3)(*inp.PIXEL_STD)
+        self.size_divisible = int(getattr(getattr(cfg, "DATALOADER", None), "SIZE_DIVISIBILITY", 0))
+        self.is_train = bool(is_train)
+
+    def choose(self, seed, index, w, h):
+        """-> ((oh, ow), flipped) of sample `index` of the batch keyed `seed` for a w x h source"""
+        size = self.min_size[hash_u32(seed, 2 * index) % len(self.min_size)]
+        return det_resize_size(w, h, size, self.max_size), hash_u32(seed, 2 * index + 1) < self.flip_threshold
+
+    def plan(self, shapes, seed):
+        """shapes: (H, W) per image -> (image_sizes, flips, (Hp, Wp)): everything the batch shape depends on, host only."""
+        picks = [self.choose(seed, i, W, H) for i, (H, W) in enumerate(shapes)]
+        sizes, flips = [p[0] for p in picks], [bool(p[1]) for p in picks]
+        return sizes, flips, self.padded_shape(sizes)
+
+    def padded_shape(self, sizes):
+        """(Hp, Wp) of to_image_list: the batch maximum, rounded up to DATALOADER.SIZE_DIVISIBILITY (image_list.py:48-60)"""
+        Hp, Wp = max(s[0] for s in sizes), max(s[1] for s in sizes)
+        if self.size_divisible > 0:
+            st = self.size_divisible
+            Hp, Wp = (Hp + st - 1) // st * st, (Wp + st - 1) // st * st
+        return Hp, Wp
+
+    def __call__(self, images, seed=None):
+        if seed is None:
+            seed = ops.collate_seed()
+        sizes, flips, _ = self.plan([(int(im.shape[0]), int(im.shape[1])) for im in images], int(seed) & _M64)
+        return self.apply(images, sizes, flips)
+
+    def apply(self, images, sizes, flips):
+        """The device work for choices already made: image i -> sizes[i] = (oh, ow), flipped when flips[i]."""
+        n, dev = len(images), images[0].device
+        for im in images:
+            if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
+                raise ValueError("DeviceDetectionTransform needs uint8 [H, W, 3] images with packed pixels")
+        shapes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+        sizes, flips = [(int(oh), int(ow)) for oh, ow in sizes], [bool(f) for f in flips]
+        Hp, Wp = self.padded_shape(sizes)
+        desc = np.zeros(n, _DET_DESC)
+        tmp_off = coef_off = 0
+        for i, (im, (H, W), (oh, ow)) in enumerate(zip(images, shapes, sizes)):
+            if oh < 1 or ow < 1:
+                raise ValueError(f"DeviceDetectionTransform: a {H} x {W} image resizes to {oh} x {ow}")
+            kh, kv = lib.plain("fiber_resample_ksize_bilinear", W, ow), lib.plain("fiber_resample_ksize_bilinear", H, oh)
+            pitch = (3 * ow + 3) // 4 * 4                              # rows of the intermediate start on a dword
+            desc[i] = (lib.ptr(im), H, W, int(im.stride(0)), oh, ow, kh, kv, tmp_off, coef_off, coef_off + ow * (2 + kh), int(flips[i]), pitch)
+            tmp_off += (H * pitch + 15) // 16 * 16
+            coef_off += ow * (2 + kh) + oh * (2 + kv)
+        if tmp_off >= 2 ** 31 or coef_off >= 2 ** 31:
+            raise ValueError("batch too large for one call (intermediate images exceed 2 GiB): split it")
+        d_desc = torch.from_numpy(desc.view(np.uint8).copy()).to(dev, non_blocking=True)
+        coef = torch.empty(coef_off, dtype=torch.int32, device=dev)
+        tmp = torch.empty(tmp_off + 16, dtype=torch.uint8, device=dev)      # + the slack the dword reads of pass 2 may touch
+        out = torch.empty((n, 3, Hp, Wp), dtype=torch.float32, device=dev)
+        lib.call("fiber_det_resize_norm_pad_u8", lib.ptr(d_desc), n, lib.ptr(coef), lib.ptr(tmp), lib.ptr(out), Hp, Wp,
+                 int(desc["H"].max()), int(desc["oh"].max()), int(desc["ow"].max()), self.bgr, self.times255, self.mean, self.std)
+        self._keep = (images, d_desc)          # the sources / table must outlive the (asynchronous) kernels of this call
+        return DetImageList(out, sizes, [(H, W, f) for (H, W), f in zip(shapes, flips)])
+
+
+def pad_input_ids(input_ids, max_query_len, pad_max, pad_id=1):
+    """The padding of `batch_encode_plus(padding="max_length" if PAD_MAX else "longest", truncation=True)` (generalized_vl_rcnn.py:268-275)
+    on already tokenised ids: a list of 1-D int64 tensors -> {"input_ids", "attention_mask"} int64 [B, L] on the ids' device, the
+    mask derived from the ids (1 where id != <pad>)."""
+    ids = [torch.as_tensor(t).reshape(-1)[:max_query_len] for t in input_ids]
+    L = int(max_query_len) if pad_max else max(int(t.numel()) for t in ids)
+    out = torch.full((len(ids), L), pad_id, dtype=torch.int64, device=ids[0].device)
+    for i, t in enumerate(ids):
+        out[i, :t.numel()] = t
+    return {"input_ids": out, "attention_mask": (out != pad_id).long()}
+
+
+def device_collate_grounding(samples, transform, cfg, seed=None, pad_id=1):
+    """The device-side half of the fine-grained loader (data/transforms/build.py, structures/bounding_box.py:101-171,
+    structures/image_list.py:30-72, data/collate_batch.py:18-46) for RAW samples.  Each sample is a dict with `image` (uint8 [H, W, 3]
+    RGB device tensor), `boxes` ([G, 4] xyxy in the ORIGINAL frame, already clipped by the dataset), `labels` [G], `positive_map`
+    [G, 256] and `input_ids` (1-D int64, tokenised with <s> ... </s>).  -> (images: DetImageList, targets: GroundingTargets in the
+    resized, flipped frame, tokenizer_input), which GeneralizedVLRCNN.forward(images, targets, tokenizer_input=...) takes as they are.
+
+    JPEG decoding, tokenisation and `create_positive_map` (data/datasets/modulated_coco.py) stay on the host loader and are out of
+    scope here: the workers hand over raw bytes, boxes, token ids and the positive map; resizing, flipping, normalising and padding
+    the ~12.8 MB of fp32 per 800 x 1333 sample is stream-ordered device work."""
+    from .modules.grounding_train import T, pack_targets
+    dev = samples[0]["image"].device
+    if seed is None:
+        seed = ops.collate_seed()
+    images = transform([s["image"] for s in samples], seed)
+    lb = cfg.MODEL.LANGUAGE_BACKBONE
+    tok = pad_input_ids([s["input_ids"] for s in samples], lb.MAX_QUERY_LEN, lb.PAD_MAX, pad_id)
+    tok = {k: v.to(dev) for k, v in tok.items()}
+    boxes = [torch.as_tensor(s["boxes"]).reshape(-1, 4) for s in samples]
+    rows = torch.cat([torch.as_tensor(s["positive_map"]).reshape(b.shape[0], T).cpu() for s, b in zip(samples, boxes)], dim=0)
+    targets = pack_targets(boxes, [torch.as_tensor(s["labels"]).reshape(-1) for s in samples], rows, device=dev)
+    table = _box_table(images.box_params([int(b.shape[0]) for b in boxes]), dev)
+    lib.call("fiber_det_boxes_f32", lib.ptr(targets.boxes), lib.ptr(table), len(samples), int(targets.boxes.shape[1]))
+    images._keep = table
+    return images, targets, tok

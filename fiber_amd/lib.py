@@ -61,6 +61,8 @@ SIGNATURES = {
     "fiber_ema_multi_f32": [P, P, P, I, F],
     "fiber_resize_bicubic_norm_u8": [P, I, P, P, P, I, I, P, P],
     "fiber_mlm_mask_i64": [P, P, P, L, U64, C.c_uint, I, I, I, I],
+    "fiber_det_resize_norm_pad_u8": [P, I, P, P, P, I, I, I, I, I, I, I, P, P],
+    "fiber_det_boxes_f32": [P, P, I, I],
     "fiber_transpose_multi_bf16": [P, I, I],
     "fiber_rowperm_cast_multi_bf16": [P, I, I],
     "fiber_dcn_gather_bf16": [P, P, P, P, I, I, I, I, I, I, I, I, I, I],
@@ -83,7 +85,7 @@ SIGNATURES = {
 }
 # host-side helpers without a stream argument
 PLAIN = {"fiber_layernorm_bwd_grid": [I], "fiber_window_attn_bwd_slices": [I, I], "fiber_window_attn_colsum_rows": [I, I, I], "fiber_colsum_slabs": [I, I], "fiber_colsum_labelled_slabs": [I], "fiber_gemm_row_tile": [I, I, I], "fiber_gemm_tn_splits": [I, I, I],
-         "fiber_adamw_chunk": [], "fiber_resample_ksize": [I, I], "fiber_dcn_dx_workspace": [I, I, I, I, I, I, I],
+         "fiber_adamw_chunk": [], "fiber_resample_ksize": [I, I], "fiber_resample_ksize_bilinear": [I, I], "fiber_dcn_dx_workspace": [I, I, I, I, I, I, I],
          "fiber_roberta_embed_bwd_workspace": [I, I, I], "fiber_ground_workspace": [I, I, I], "fiber_det_max_candidates": [],
          "fiber_atss_num_candidates": [P, I, I], "fiber_atss_loss_rows": [I, I]}
 

@@ -268,6 +268,26 @@ int fiber_resize_bicubic_norm_u8(const void* descs, int n, int* coef, void* tmp,
                                  const float* std, fiber_stream_t stream);
 int fiber_mlm_mask_i64(const long long* ids, long long* ids_mlm, long long* labels, long n, unsigned long long seed,
                        unsigned p_select, int mask_id, int vocab, int special_lo, int special_hi, fiber_stream_t stream);
+/* Detection (grounding) input pipeline: the per-sample CPU transforms of the fine-grained model, after the H2D copy of raw bytes.
+ * fiber_det_resize_norm_pad_u8 replaces fine_grained/maskrcnn_benchmark/data/transforms/build.py:5-43 `build_transforms` (transforms.py:85-129
+ * Resize = PIL Image.resize(BILINEAR) to the per-image Resize.get_size, :131-143 RandomHorizontalFlip, :160-162 ToTensor, :165-177
+ * Normalize(format)) and structures/image_list.py:30-72 `to_image_list` (zero padding AFTER normalising), as BatchCollator calls it
+ * (data/collate_batch.py:18-21).  Same Pillow ImagingResample as above with the triangle filter (support 1 x max(scale, 1)), bit-identical
+ * to PIL.  descs: device array of n records {int64 src; int32 H, W, src_stride, oh, ow, ksize_h, ksize_v, tmp_off, coef_h_off, coef_v_off,
+ * flip, tmp_pitch} (56 bytes; ksize_h = fiber_resample_ksize_bilinear(W, ow), ksize_v = (H, oh); `coef` holds ow*(2+ksize_h) +
+ * oh*(2+ksize_v) ints per image; `tmp`, 16-byte aligned, holds H*tmp_pitch bytes per image at tmp_off (a multiple of 16), tmp_pitch = 3*ow
+ * rounded up to a multiple of 4, plus 16 bytes of slack at its end).  out: fp32 [n,3,Hp,Wp], every element written once: inside (oh, ow)
+ * ((v/255 [*255 if times255]) - mean[c]) / std[c] in fp32, each operation rounded, with v read at column ow-1-x when flip and from source
+ * channel 2-c when bgr; 0.0f outside.  max_h / max_oh / max_ow: the largest H, oh, ow (oh <= Hp, ow <= Wp).  mean / std: HOST pointers
+ * to 3 floats, indexed by output channel.
+ * fiber_det_boxes_f32 replaces structures/bounding_box.py:101-135 `BoxList.resize` and :137-171 `BoxList.transpose(FLIP_LEFT_RIGHT)` on the
+ * packed targets: boxes fp32 [B,G,4] xyxy in place; params: device array of B records {float ratio_w, ratio_h; int32 flip; float new_w;
+ * int32 num_gt} (20 bytes): x *= ratio_w, y *= ratio_h (fp32), then, when flip, (x0, x1) = (new_w - x1 - 1, new_w - x0 - 1); rows
+ * g >= num_gt are written as zero. */
+int fiber_resample_ksize_bilinear(int in_size, int out_size);
+int fiber_det_resize_norm_pad_u8(const void* descs, int n, int* coef, void* tmp, float* out, int Hp, int Wp, int max_h, int max_oh,
+                                 int max_ow, int bgr, int times255, const float* mean, const float* std, fiber_stream_t stream);
+int fiber_det_boxes_f32(float* boxes, const void* params, int B, int G, fiber_stream_t stream);
 
 /* Modulated deformable convolution (DCNv2) of the fine-grained model's DyHead: the sampling half of
  * layers/deform_conv.py:300-353 `ModulatedDeformConv` (csrc/cuda/deform_conv_kernel_cuda.cu:578-640 im2col, :643-700 col2im,
