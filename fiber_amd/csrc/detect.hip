@@ -23,13 +23,16 @@ __device__ __forceinline__ float sigmoid1(float z) {
 }
 
 // One wave per anchor: the 256 token probabilities go through LDS, lane c (+64, ...) folds its class's tokens in CSR order.
+// Sample b reads the C + 1 offsets at class_ptr + b * ptr_stride (absolute offsets into the one tok_idx); ptr_stride 0 = one map for all.
 __global__ __launch_bounds__(256) void det_scores_kernel(const float* __restrict__ logits, const float* __restrict__ ctr,
-                                                         const int* __restrict__ class_ptr, const int* __restrict__ tok_idx,
-                                                         float* __restrict__ out, int A, int C, float thresh, int use_max) {
+                                                         const int* __restrict__ class_ptr_all, const int* __restrict__ tok_idx,
+                                                         float* __restrict__ out, int A, int C, float thresh, int use_max,
+                                                         int ptr_stride) {
   __shared__ __attribute__((aligned(16))) float prob[4][DT];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, b = blockIdx.y;
   const int a = blockIdx.x * 4 + wave;
   if (a >= A) return;                                      // whole wave; no workgroup barrier below
+  const int* __restrict__ class_ptr = class_ptr_all + (size_t)b * ptr_stride;
   const size_t row = (size_t)b * A + a;
   const f32x4 z = *reinterpret_cast<const f32x4*>(logits + row * DT + lane * 4);
   f32x4 p;
@@ -211,16 +214,25 @@ __global__ __launch_bounds__(64) void det_nms_select_kernel(const float* __restr
 // Largest N (candidates per image after the per-level top-k) the select kernel's register bitmap holds
 extern "C" int fiber_det_max_candidates(void) { return SEL_MAX_N; }
 
-extern "C" int fiber_det_scores_f32(const float* logits, const float* centerness, const int* class_ptr, const int* tok_idx, float* out,
-                                    int B, int A, int T, int C, float pre_nms_thresh, int agg_max, hipStream_t stream) {
+// ptr_stride: elements between the class_ptr rows of consecutive samples (per-sample positive maps: phrase grounding, referring
+// expressions); 0 = every sample reads the same C + 1 offsets.
+extern "C" int fiber_det_scores_rows_f32(const float* logits, const float* centerness, const int* class_ptr, const int* tok_idx,
+                                         float* out, int B, int A, int T, int C, float pre_nms_thresh, int agg_max, int ptr_stride,
+                                         hipStream_t stream) {
   if (T != DT || C <= 0 || B < 0 || A < 0) return FIBER_EINVAL;
+  if (ptr_stride != 0 && ptr_stride < C + 1) return FIBER_EINVAL;
   if (B == 0 || A == 0) return FIBER_OK;
   if (!logits || !centerness || !class_ptr || !tok_idx || !out) return FIBER_EINVAL;
   if (fiber_misaligned(16, logits) || fiber_misaligned(4, centerness, class_ptr, tok_idx, out)) return FIBER_EINVAL;
   hipLaunchKernelGGL(det_scores_kernel, dim3(cdiv(A, 4), B), dim3(256), 0, stream, logits, centerness, class_ptr, tok_idx, out, A, C,
-                     pre_nms_thresh, agg_max);
+                     pre_nms_thresh, agg_max, ptr_stride);
   FIBER_CHECK_LAUNCH();
   return FIBER_OK;
+}
+
+extern "C" int fiber_det_scores_f32(const float* logits, const float* centerness, const int* class_ptr, const int* tok_idx, float* out,
+                                    int B, int A, int T, int C, float pre_nms_thresh, int agg_max, hipStream_t stream) {
+  return fiber_det_scores_rows_f32(logits, centerness, class_ptr, tok_idx, out, B, A, T, C, pre_nms_thresh, agg_max, 0, stream);
 }
 
 extern "C" int fiber_det_decode_f32(const float* topk_val, const long long* topk_idx, const float* bbox_reg, const float* anchors,

@@ -11,7 +11,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FIBER_HIP_LIB") or os.path.join(_HERE, "libfiber_hip.so")   # env: A/B builds (tools/)
 
-P, I, F, L, U64 = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_uint64
+P, I, F, L, U64, DBL = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_uint64, C.c_double
 
 # name -> argtypes (stream appended automatically)
 SIGNATURES = {
@@ -71,9 +71,11 @@ SIGNATURES = {
     "fiber_ground_fwd_bf16": [P, P, P, P, P, P, P, P, P, I, I, I, I, F, F],
     "fiber_ground_bwd_bf16": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, F],
     "fiber_det_scores_f32": [P, P, P, P, P, I, I, I, I, F, I],
+    "fiber_det_scores_rows_f32": [P, P, P, P, P, I, I, I, I, F, I, I],
     "fiber_det_decode_f32": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F],
     "fiber_det_nms_mask": [P, P, P, P, I, I, F],
     "fiber_det_nms_select": [P, P, P, P, P, P, P, P, P, P, I, I, I],
+    "fiber_ground_recall": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, DBL, I],
     "fiber_atss_candidates_f32": [P, P, I, P, P, P, P, I, I, I, I],
     "fiber_atss_resolve_f32": [P, P, P, P, P, P, I, I, I, I],
     "fiber_atss_finalize_f32": [P, P, P, P, P, P, P, P, P, P, I, I, I, I],

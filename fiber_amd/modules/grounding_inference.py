@@ -171,6 +171,48 @@ def positive_map_to_csr(positive_map, num_classes, v2=False):
     return torch.from_numpy(ptr), torch.from_numpy(idx if idx.size else np.zeros(1, dtype=np.int32))
 
 
+class PackedPositiveMaps:
+    """One positive map per sample: class_ptr int32 [B, C + 1] (row b: absolute offsets of sample b's classes into tok_idx) and the
+    samples' token lists concatenated in tok_idx int32 [nnz].  What ATSSPostProcessor.forward takes in place of a dict when every
+    image has its own caption; already on the device, it costs no copy, so the call can be captured in a graph."""
+
+    def __init__(self, class_ptr, tok_idx):
+        self.class_ptr, self.tok_idx = class_ptr, tok_idx
+
+    @property
+    def num_classes(self):
+        return int(self.class_ptr.shape[1]) - 1
+
+    def __len__(self):
+        return int(self.class_ptr.shape[0])
+
+    def to(self, device):
+        """Both tensors travel in ONE copy (class_ptr padded to a multiple of 16 bytes, then tok_idx)."""
+        have, want = self.class_ptr.device, torch.device(device)
+        if have.type == want.type and want.index in (None, have.index):
+            return self
+        n = self.class_ptr.numel()
+        pad = -n % 4
+        flat = torch.cat([self.class_ptr.reshape(-1), self.class_ptr.new_zeros(pad), self.tok_idx.reshape(-1)]).to(device)
+        return PackedPositiveMaps(flat[:n].view(self.class_ptr.shape), flat[n + pad:])
+
+
+def pack_positive_maps(maps, num_classes, v2=False):
+    """A list of B reference-form dicts (positive_map_to_csr's validation applies to each) -> PackedPositiveMaps on the host.  Classes a
+    sample does not use have empty rows, which score -1: top-k, decode and `source` keep their meaning with the padded num_classes."""
+    if isinstance(maps, dict) or len(maps) == 0:
+        raise ValueError("pack_positive_maps: a non-empty list of positive maps, one per sample")
+    ptrs, idxs, off = [], [], 0
+    for m in maps:
+        ptr, idx = positive_map_to_csr(m, num_classes, v2)
+        nnz = int(ptr[-1])
+        ptrs.append(ptr + off)
+        idxs.append(idx[:nnz])
+        off += nnz
+    idx = torch.cat(idxs)
+    return PackedPositiveMaps(torch.stack(ptrs).contiguous(), idx if idx.numel() else torch.zeros(1, dtype=torch.int32))
+
+
 class Detections:
     """Fixed-size result: boxes fp32 [B, D, 4] (xyxy, +1 convention), scores fp32 [B, D] (-1 past count), labels int32 [B, D],
     source int32 [B, D] (level << 28 | anchor << 10 | class; -1 past count), count int32 [B]; descending score per image."""
@@ -243,7 +285,9 @@ class ATSSPostProcessor(nn.Module):
                 token_logits=None):
         """box_regression / centerness / dot_product_logits: per level, as VLDyHead.forward returns them; image_sizes fp32 [B, 2] device
         tensor of (w, h) per image; anchors: one [A_l, 4] tensor per level (AnchorGenerator.grid_anchors of the feature shapes: the
-        reference's per-image BoxList copies differ in nothing but the size field).  -> Detections"""
+        reference's per-image BoxList copies differ in nothing but the size field).  positive_map: the reference's dict (one map for the
+        batch, cached by csr()), a list of B dicts (one per sample: packed here with one host-to-device copy per call, not cached), or a
+        PackedPositiveMaps already on the device (no copy).  -> Detections"""
         if token_logits is not None:
             raise NotImplementedError(f"ATSSPostProcessor token_logits: {_UNSUPPORTED['token_logits']}")
         if dot_product_logits is None:
@@ -255,7 +299,17 @@ class ATSSPostProcessor(nn.Module):
         dev = dot_product_logits[0].device
         B = dot_product_logits[0].shape[0]
         C = self.num_score_classes(box_cls)
-        ptr, idx = self.csr(positive_map, C, dev)
+        if isinstance(positive_map, (list, tuple)):
+            if len(positive_map) != B:
+                raise ValueError(f"ATSSPostProcessor: {len(positive_map)} positive maps for a batch of {B}")
+            positive_map = pack_positive_maps(positive_map, C, self.mdetr_style_aggregate_class_num != -1).to(dev)
+        if isinstance(positive_map, PackedPositiveMaps):
+            if len(positive_map) != B or positive_map.num_classes != C or positive_map.class_ptr.device != dev:
+                raise ValueError(f"ATSSPostProcessor: packed positive maps {tuple(positive_map.class_ptr.shape)} on "
+                                 f"{positive_map.class_ptr.device} for a batch of {B} with {C} classes on {dev}")
+            ptr, idx = positive_map.class_ptr, positive_map.tok_idx
+        else:
+            ptr, idx = self.csr(positive_map, C, dev)
         ks = [self.level_k(d.shape[1], C) for d in dot_product_logits]
         N = sum(ks)
         if N > lib.plain("fiber_det_max_candidates"):
@@ -315,7 +369,8 @@ class VLDyHeadModule(nn.Module):
     def forward(self, image_sizes, features, language_dict_features, positive_map=None, targets=None):
         """Training mode with `targets`: -> {"loss_reg", "loss_centerness", "loss_cls", "loss_dot_product_token"} (image_sizes and
         positive_map are not read: the anchors do not depend on the image and the targets carry their positive map).  Eval: image_sizes: [(h, w)] per image as ImageList.image_sizes, or a [B, 2] tensor of (w, h); features: the FPN levels
-        [B, C, H, W]; language_dict_features["embedded"]: [B, 256, LANG_DIM].  -> Detections.  A list of sizes is copied to the device
+        [B, C, H, W]; language_dict_features["embedded"]: [B, 256, LANG_DIM]; positive_map: one dict for the batch, a list of B dicts or a
+        PackedPositiveMaps (one map per sample: see ATSSPostProcessor.forward).  -> Detections.  A list of sizes is copied to the device
         here (a host-to-device copy per call); pass the tensor, already on the device, to avoid it or to capture the call in a graph."""
         if self.training:
             if targets is None:

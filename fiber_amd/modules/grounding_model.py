@@ -97,7 +97,8 @@ class GeneralizedVLRCNN(nn.Module):
 
     def forward(self, images, targets=None, captions=None, positive_map=None, greenlight_map=None, tokenizer_input=None):
         """Training (with targets: GroundingTargets) -> {"loss_reg", "loss_centerness", "loss_cls", "loss_dot_product_token"}; eval ->
-        Detections.  greenlight_map is read by the MLM branch only and is accepted for signature parity."""
+        Detections; positive_map: the reference's dict, or one map per sample as a list of B dicts or a PackedPositiveMaps on the device
+        (phrase grounding, referring expressions).  greenlight_map is read by the MLM branch only and is accepted for signature parity."""
         if self.training and targets is None:
             raise ValueError("In training mode, targets should be passed")
         sizes = None

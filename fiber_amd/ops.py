@@ -1907,18 +1907,25 @@ def _det_f32(t):
 
 def det_scores(logits, centerness, class_ptr, tok_idx, pre_nms_thresh, score_agg="MEAN"):
     """Dense class scores of one level (inference.py:620-650, :741-795): logits fp32 [B, A, 256] and centerness [B, 1, H, W] as
-    VLDyHead.forward returns them, the positive map as CSR (int32 class_ptr [C + 1], tok_idx [nnz]).  -> fp32 [B, A, C]:
+    VLDyHead.forward returns them, the positive map as CSR (int32 class_ptr [C + 1], tok_idx [nnz]), or one map per sample as class_ptr
+    [B, C + 1] holding absolute offsets into the one tok_idx (grounding_inference.pack_positive_maps).  -> fp32 [B, A, C]:
     agg * sigmoid(centerness) where agg > pre_nms_thresh, -1 elsewhere."""
     if score_agg not in ("MEAN", "MAX"):
         raise NotImplementedError(f"det_scores: score_agg {score_agg!r} (MEAN and MAX are built)")
     B, A, T = logits.shape
-    C = class_ptr.numel() - 1
+    C = class_ptr.shape[-1] - 1
     if centerness.numel() != B * A or class_ptr.dtype != torch.int32 or tok_idx.dtype != torch.int32:
         raise ValueError(f"det_scores: logits {tuple(logits.shape)}, centerness {tuple(centerness.shape)}, CSR {class_ptr.dtype} / {tok_idx.dtype}")
     lg, ct = _det_f32(logits), _det_f32(centerness)
     out = torch.empty((B, A, C), dtype=torch.float32, device=logits.device)
-    lib.call("fiber_det_scores_f32", lib.ptr(lg), lib.ptr(ct), lib.ptr(_c(class_ptr)), lib.ptr(_c(tok_idx)), lib.ptr(out), B, A, T, C,
-             float(pre_nms_thresh), int(score_agg == "MAX"))
+    if class_ptr.dim() == 1:
+        lib.call("fiber_det_scores_f32", lib.ptr(lg), lib.ptr(ct), lib.ptr(_c(class_ptr)), lib.ptr(_c(tok_idx)), lib.ptr(out), B, A, T, C,
+                 float(pre_nms_thresh), int(score_agg == "MAX"))
+        return out
+    if class_ptr.dim() != 2 or class_ptr.shape[0] != B:
+        raise ValueError(f"det_scores: class_ptr {tuple(class_ptr.shape)} for {B} samples (one row of C + 1 offsets per sample)")
+    lib.call("fiber_det_scores_rows_f32", lib.ptr(lg), lib.ptr(ct), lib.ptr(_c(class_ptr)), lib.ptr(_c(tok_idx)), lib.ptr(out), B, A, T, C,
+             float(pre_nms_thresh), int(score_agg == "MAX"), C + 1)
     return out
 
 
@@ -1962,6 +1969,33 @@ def nms_ml(boxes, scores, labels, source, nms_thresh, detections_per_img):
     lib.call("fiber_det_nms_select", lib.ptr(bx), lib.ptr(sc), lib.ptr(lb), lib.ptr(sr), lib.ptr(mask), lib.ptr(ob), lib.ptr(osc),
              lib.ptr(ol), lib.ptr(osr), lib.ptr(cnt), B, N, D)
     return ob, osc, ol, osr, cnt
+
+
+# ---- grounding evaluation: recall@k of Detections against per-phrase ground truth (csrc/geval.hip) -----------------------------------
+def ground_recall(boxes, labels, count, gt, gt_count, cat_mask, topk, positives, totals, thresh, mode, num_categories=64):
+    """One launch of fiber_ground_recall, no host synchronisation.  boxes fp32 [B, D, 4] in the original frame, labels int32 [B, D]
+    (None in mode 1), count int32 [B], gt fp64 [B, P, G, 4], gt_count int32 [B, P], cat_mask int64 [B, P] (bit 0 = "all"), topk int32
+    [K]; positives / totals int64 [K, 64] are accumulated IN PLACE.  mode 0 = Flickr recall, 1 = RefExp precision.
+    -> (hit int32 [B, P, K], best fp64 [B, P, K])."""
+    B, D = boxes.shape[:2]
+    P, G = gt.shape[1:3]
+    K = topk.numel()
+    if boxes.shape != (B, D, 4) or gt.shape != (B, P, G, 4) or gt_count.shape != (B, P) or cat_mask.shape != (B, P) or count.shape != (B,):
+        raise ValueError(f"ground_recall: boxes {tuple(boxes.shape)}, gt {tuple(gt.shape)}, gt_count {tuple(gt_count.shape)}, "
+                         f"cat_mask {tuple(cat_mask.shape)}, count {tuple(count.shape)}")
+    if gt.dtype != torch.float64 or gt_count.dtype != torch.int32 or cat_mask.dtype != torch.int64 or topk.dtype != torch.int32 or \
+            count.dtype != torch.int32 or (labels is not None and (labels.dtype != torch.int32 or labels.shape != (B, D))):
+        raise ValueError("ground_recall: gt fp64, gt_count / topk / count / labels int32, cat_mask int64")
+    for t in (positives, totals):
+        if t.dtype != torch.int64 or t.shape != (K, 64) or not t.is_contiguous():
+            raise ValueError("ground_recall: positives / totals are contiguous int64 [K, 64]")
+    dev = boxes.device
+    hit = torch.empty((B, P, K), dtype=torch.int32, device=dev)
+    best = torch.empty((B, P, K), dtype=torch.float64, device=dev)
+    lib.call("fiber_ground_recall", lib.ptr(_det_f32(boxes)), lib.ptr(None if labels is None else _c(labels)), lib.ptr(_c(count)),
+             lib.ptr(_c(gt)), lib.ptr(_c(gt_count)), lib.ptr(_c(cat_mask)), lib.ptr(_c(topk)), lib.ptr(hit), lib.ptr(best),
+             lib.ptr(positives), lib.ptr(totals), B, D, P, G, K, int(num_categories), float(thresh), int(mode))
+    return hit, best
 
 
 # ---- grounding training: ATSS assignment + GIoU / centerness losses (csrc/atss.hip) --------------------------------------------------

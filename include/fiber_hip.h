@@ -338,6 +338,10 @@ int fiber_ground_bwd_bf16(const void* X, const void* P, const float* tbias, cons
  * candidate test, the centerness product): logits fp32 [B,A,T] and centerness fp32 [B,1,H,W] (= [B,A]) as the head returns them, the positive
  * map as CSR (class_ptr int32 [C+1], tok_idx int32 [nnz], token sets may overlap, an empty class scores 0); out fp32 [B,A,C] =
  * agg * sigmoid(ctr) where agg > pre_nms_thresh (tested BEFORE the centerness product) and -1 elsewhere; agg_max 0 = MEAN, 1 = MAX.
+ * fiber_det_scores_rows_f32 is the same with one positive map PER SAMPLE (phrase grounding, referring expressions: a caption per image, which
+ * the reference evaluates at batch size 1, engine/inference.py:531): sample b reads its C+1 offsets at class_ptr + b * ptr_stride, absolute
+ * offsets into the one shared tok_idx; ptr_stride 0 = fiber_det_scores_f32; 0 < ptr_stride < C+1 -> 1.  A class a sample does not use has an
+ * empty row and scores -1.
  * fiber_det_decode_f32 replaces inference.py:657-676, modeling/box_coder.py:52-95 (weights 10,10,5,5, log(1000/16) clamp, TO_REMOVE 1),
  * structures/bounding_box.py:214-225 (clip_to_image) and structures/boxlist_ops.py:77-91 (remove_small_boxes): one level's top-k
  * (topk_val fp32 [B,k], topk_idx int64 [B,k] into [A*C], val < 0 = padding), bbox_reg fp32 [B,4,H,W] read in place, anchors fp32 [A,4],
@@ -352,6 +356,8 @@ int fiber_ground_bwd_bf16(const void* X, const void* P, const float* tbias, cons
 int fiber_det_max_candidates(void);
 int fiber_det_scores_f32(const float* logits, const float* centerness, const int* class_ptr, const int* tok_idx, float* out, int B, int A,
                          int T, int C, float pre_nms_thresh, int agg_max, fiber_stream_t stream);
+int fiber_det_scores_rows_f32(const float* logits, const float* centerness, const int* class_ptr, const int* tok_idx, float* out, int B,
+                              int A, int T, int C, float pre_nms_thresh, int agg_max, int ptr_stride, fiber_stream_t stream);
 int fiber_det_decode_f32(const float* topk_val, const long long* topk_idx, const float* bbox_reg, const float* anchors,
                          const float* image_sizes, float* boxes, float* scores, int* labels, int* source, int B, int k, int A, int C, int N,
                          int offset, int level, float min_size, fiber_stream_t stream);
@@ -360,6 +366,26 @@ int fiber_det_nms_mask(const float* boxes, const float* scores, const int* label
 int fiber_det_nms_select(const float* boxes, const float* scores, const int* labels, const int* source, const unsigned long long* mask,
                          float* out_boxes, float* out_scores, int* out_labels, int* out_source, int* out_count, int B, int N, int D,
                          fiber_stream_t stream);
+
+/* Phrase-grounding evaluation (csrc/geval.hip); file:line relative to the reference's fine_grained/maskrcnn_benchmark/.  One wave per
+ * (image, phrase); nothing crosses to the host.  fiber_ground_recall replaces engine/inference.py:311-327 (flickr_post_process),
+ * data/datasets/evaluation/flickr/flickr_eval.py:173-204 and :365-383 (box_iou, the recall@k tally), data/datasets/refexp.py:58-74
+ * (RefExpEvaluator.summarize) and layers/set_loss.py:15-52 (generalized_box_iou).
+ * boxes fp32 [B,D,4] in the ORIGINAL image frame, labels int32 [B,D], count int32 [B] (device): the first count[b] rows are read, in their
+ * stored descending-score order.  gt fp64 [B,P,G,4]; gt_count int32 [B,P] (0 = no such phrase: hit 0, best 0.0, counted nowhere);
+ * cat_mask uint64 [B,P]: the categories the phrase counts towards (bit 0 = "all"), bits >= ncat ignored; topk int32 [K] (device), -1 =
+ * every box.  hit int32 [B,P,K], best fp64 [B,P,K]: every element written.  positives / totals int64 [K,64]: ACCUMULATED in place with
+ * integer atomic adds (order-independent: two runs give the same bits).
+ * mode 0 (Flickr): a detection belongs to phrase p when label == p + 1; its rank is its position among that phrase's detections; one
+ * sentinel box [0,0,0,0] follows at the next rank; best[k] = max IoU over ranks < topk[k] and the phrase's gt boxes, IoU in fp64 as
+ * inter / (area1 + area2 - inter), no +1; hit = best >= thresh.
+ * mode 1 (RefExp): P = 1, labels not read (may be NULL), rank = position, no sentinel; generalized IoU in fp32 of boxes rounded to fp32,
+ * compared with thresh rounded to fp32; count[b] == 0: a miss with best = -1 (the reference raises on the empty zip).
+ * K > 8, ncat > 64, negative sizes, mode outside {0,1}, mode 1 with P > 1, NULL or misaligned pointers -> 1; B, P or K == 0 -> 0 without
+ * a launch. */
+int fiber_ground_recall(const float* boxes, const int* labels, const int* count, const double* gt, const int* gt_count,
+                        const unsigned long long* cat_mask, const int* topk, int* hit, double* best, long long* positives, long long* totals,
+                        int B, int D, int P, int G, int K, int ncat, double thresh, int mode, fiber_stream_t stream);
 
 /* Grounding training: ATSS target assignment and the box / centerness losses with fixed shapes and no host synchronisation
  * (csrc/atss.hip); file:line relative to the reference's fine_grained/maskrcnn_benchmark/.  Targets: gt_boxes fp32 [B,Gmax,4] (xyxy),
