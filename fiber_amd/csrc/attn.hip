@@ -45,7 +45,7 @@ struct AttnP {
   const float* bias_table;   // [(2ws-1)^2, H] fp32
   float* dbias_part;         // [gridDim.z, H, N, N] fp32 partial bias gradients (pass A, WINDOW)
   int groups_per_block;      // pass A: windows visited by one workgroup
-  // LDS chunk geometry of this launch (host-chosen, launch_geometry()): tiles per chunk cap, rows of the row-major images
+  // LDS chunk geometry of this launch (host-chosen, attn_plan()): tiles per chunk cap, rows of the row-major images
   int tpc_cap, chrows;
   // attention-probability dropout
   float p_drop; uint64_t seed; const uint64_t* seed_base;   // key = seed + *seed_base (seed_base nullable: hipGraph replay)
@@ -157,8 +157,7 @@ __device__ __forceinline__ Lds carve(char* base, int nbias, int n_rm, int chrows
   L.rm1 = img; img += (n_rm > 1) * chrows * (D + 16);
   return L;
 }
-template <int D>
-size_t lds_bytes(int nbias, int n_rm, int chrows) {
+size_t lds_bytes(int D, int nbias, int n_rm, int chrows) {
   return (size_t)(5 * CH + ((nbias + 3) & ~3)) * 4 + (size_t)n_rm * chrows * (D + 16) * 2;
 }
 
@@ -675,145 +674,163 @@ __global__ __launch_bounds__(256) void dbias_scatter_kernel(const float* __restr
   }
 }
 
-// waves (16-row strips) per workgroup.  `staged` = rows of the OTHER operand every workgroup stages into LDS: when that is a
-// short text sequence (i2t cross-attention: 40-50 keys) small workgroups win -- three or four of them share a CU and overlap
-// each other's staging / softmax phases (op_bench, 576 queries x 40 keys: forward 812 -> 543 us) -- while a long staged side
-// (t2i backward: 576 keys per 40 queries) wants few, large workgroups so it is staged fewer times.
-int pick_waves(int nstrips, int staged) {
-  static const int force = getenv("FIBER_ATTN_WAVES") ? atoi(getenv("FIBER_ATTN_WAVES")) : 0;
-  if (force > 0) return nstrips < force ? nstrips : force;
-  if (staged <= 64 && nstrips > 4) return nstrips % 3 == 0 ? 3 : 4;
-  return nstrips <= 12 ? nstrips : (nstrips % 9 == 0 ? 9 : 8);
+// ===================================================== dispatch ================================================
+// A pass WALKS one axis in strips of 16 rows, one wave per strip (forward and dQ: the queries; dK/dV: the keys), and STAGES the other axis in
+// LDS, in chunks of whole 16-row tiles that the waves of a workgroup share.  attn_plan() decides everything about one pass' launch, each
+// quantity once; launch_fwd / launch_dq / launch_dkv map a plan to the template it describes.  Plain arithmetic: no HIP call, no environment.
+enum AttnPass { ATTN_FWD, ATTN_DQ, ATTN_DKV };
+struct AttnPlan {
+  int slots;               // tile slots of the kernel form (template parameter NT): 4, 6 or 10
+  int nw;                  // waves per workgroup
+  int tpc_cap, chrows;     // AttnP: cap on the tiles per chunk, rows of the row-major LDS images
+  int gx, gy, gz;          // grid: workgroups per (head, group), heads, groups (dQ pass of WINDOW mode: runs of groups_per_block windows)
+  int groups_per_block;    // AttnP (1 outside the dQ pass of WINDOW mode)
+  size_t lds;              // dynamic LDS bytes
+};
+
+// waves the form may be launched with: its __launch_bounds__ / 64 (strips beyond them go to further workgroups)
+int max_waves(AttnPass pass, int D, bool window, int slots) {
+  if (pass == ATTN_DQ) return (window || slots > 6) ? 8 : 12;
+  if (pass == ATTN_DKV) return (!window && slots > 6 && D == 64) ? 8 : 12;
+  return 12;
 }
 
-// LDS chunk geometry for a launch that stages `staged_len` rows per group with `nw` waves per workgroup.  The images are
-// sized to the chunk actually used (a 40-token text sequence needs 48 rows, not 160), and small workgroups take chunks of at
-// most 5 tiles: with the full 160-row layout a 3-wave workgroup of the D = 64 kernels owned 47-91 KB of LDS, i.e. one or two
-// workgroups (3-6 waves) per CU.
-void launch_geometry(AttnP& p, int staged_len, int nw, bool backward) {
-  const int ntiles = cdiv(staged_len, 16);
-  // small workgroups want chunks short enough for three or four of them to share a CU's LDS: two row-major images of
-  // chrows x (D+16) plus 3.2 KB of tables.  Forward: 8 tiles (128 rows, 44 KB at D = 64 -> 3 workgroups; the full 160-row chunk
-  // leaves 2 and measured 386 -> 486 us on the t2i shape, 5-tile chunks add barriers: 422 us); backward: 5 tiles.
-  p.tpc_cap = (nw <= 4 && !p.window && ntiles > (backward ? 5 : 8)) ? (backward ? 5 : 8) : NKT;
-  const int nchunk = cdiv(ntiles, p.tpc_cap), tpc = cdiv(ntiles, nchunk);
-  p.chrows = (tpc * 16 + 31) & ~31;
+// ws: window size (0: PLAIN mode); nz: partial-gradient slices of the WINDOW dQ pass (fiber_window_attn_bwd_slices).  CAUSAL is a flag of the
+// 4-slot forms and changes nothing here: L <= 64 is one chunk of at most 4 tiles.
+AttnPlan attn_plan(AttnPass pass, int D, int walked, int staged, int H, int G, int ws, int nz) {
+  const bool window = ws > 0, backward = pass != ATTN_FWD;
+  const int nstrips = cdiv(walked, 16), ntiles = cdiv(staged, 16);
+  AttnPlan a{};
+  // waves: when the staged side is a short text sequence (i2t cross-attention: 40-50 keys) small workgroups win -- three or four of them
+  // share a CU and overlap each other's staging / softmax phases (op_bench, 576 queries x 40 keys: forward 812 -> 543 us) -- while a long
+  // staged side (t2i backward: 576 keys per 40 queries) wants few, large workgroups so it is staged fewer times.  The key-strip pass
+  // measured worse with small workgroups.
+  if (pass != ATTN_DKV && staged <= 64 && nstrips > 4) a.nw = nstrips % 3 == 0 ? 3 : 4;
+  else a.nw = nstrips <= 12 ? nstrips : (nstrips % 9 == 0 ? 9 : 8);
+  // chunks: the images are sized to the chunk actually used (a 40-token text sequence needs 48 rows, not 160), and small workgroups take
+  // chunks short enough for three or four of them to share a CU's LDS: two row-major images of chrows x (D+16) plus 3.2 KB of tables.
+  // Forward: 8 tiles (128 rows, 44 KB at D = 64 -> 3 workgroups; the full 160-row chunk leaves 2 and measured 386 -> 486 us on the t2i
+  // shape, 5-tile chunks add barriers: 422 us); backward: 5 tiles.
+  const int small_cap = backward ? 5 : 8;
+  a.tpc_cap = (a.nw <= 4 && !window && ntiles > small_cap) ? small_cap : NKT;
+  const int nchunk = cdiv(ntiles, a.tpc_cap), tpc = cdiv(ntiles, nchunk);
+  a.chrows = (tpc * 16 + 31) & ~31;
+  a.lds = lds_bytes(D, window ? (2 * ws - 1) * (2 * ws - 1) : 0, 2, a.chrows);
+  // form: chunks of at most 4 tiles (a 40-token text side: 3) take the kernels instantiated with 4 tile slots instead of 10, which hold 24
+  // fewer score registers per array and fit more waves per SIMD (the strip-walking kernels are bound by the latency of their per-strip
+  // loads); the dQ pass has a 6-slot form as well (t2i: 5-tile chunks; the 10-slot form spills)
+  a.slots = window ? NKT : tpc <= 4 ? 4 : (pass == ATTN_DQ && tpc <= 6) ? 6 : NKT;
+  const int cap = max_waves(pass, D, window, a.slots);     // (below 9 only for 10-slot forms; the chunking above depends on nw only up to 4)
+  if (a.nw > cap) a.nw = cap;
+  // grid: when the staged side is one chunk the PLAIN kernels (and the WINDOW forward) stage it once per workgroup and loop over strips, so
+  // only as many workgroups per (head, group) are launched as it takes to fill the chip (~8 per CU overall)
+  a.groups_per_block = (window && pass == ATTN_DQ) ? cdiv(G, nz) : 1;
+  a.gy = H;
+  a.gz = cdiv(G, a.groups_per_block);
+  const bool once = nchunk == 1 && (!window || pass == ATTN_FWD);
+  a.gx = cdiv(nstrips, a.nw);
+  if (once && cdiv(2048, H * a.gz) < a.gx) a.gx = cdiv(2048, H * a.gz);
+  return a;
 }
 
-// grid.x of the query-strip kernels.  When the staged side fits one chunk the kernels stage it once per workgroup and loop over
-// strips, so only as many workgroups per (head, group) are launched as it takes to fill the chip (~8 per CU overall).
-int strip_blocks(const AttnP& p, int staged_len, int nstrips, int nw, int hg, bool window_ok) {
-  const int full = cdiv(nstrips, nw);
-  const bool once = cdiv(cdiv(staged_len, 16), p.tpc_cap) == 1 && (window_ok || !p.window);
-  if (!once) return full;
-  const int want = cdiv(2048, hg);
-  return want < 1 ? 1 : (want < full ? want : full);
-}
-
-// chunks of at most 4 tiles (a 40-token text side: 3): the kernels instantiated with 4 tile slots instead of 10 hold 24 fewer score
-// registers per array and fit more waves per SIMD (the strip-walking kernels are bound by the latency of their per-strip loads)
-int chunk_tiles(const AttnP& p, int staged_len) {
-  const int ntiles = cdiv(staged_len, 16), nchunk = cdiv(ntiles, p.tpc_cap);
-  return cdiv(ntiles, nchunk);
-}
-bool small_chunk(const AttnP& p, int staged_len) {
-  static const int off = getenv("FIBER_ATTN_NOSMALL") ? 1 : 0;
-  const int ntiles = cdiv(staged_len, 16), nchunk = cdiv(ntiles, p.tpc_cap);
-  return !off && cdiv(ntiles, nchunk) <= 4;
-}
-
-template <int D>
-int launch_fwd(AttnP& p, hipStream_t st, bool causal = false) {
-  const int nstrips = cdiv(p.Lq, 16), nw = pick_waves(nstrips, p.Lk);
-  const int nb = p.window ? (2 * p.ws - 1) * (2 * p.ws - 1) : 0;
-  launch_geometry(p, p.Lk, nw, false);
-  const size_t sh = lds_bytes<D>(nb, 2, p.chrows);
-  const int gx = strip_blocks(p, p.Lk, nstrips, nw, p.H * p.G, true);
-  if (p.window) hipLaunchKernelGGL((attn_fwd_kernel<D, true>), dim3(gx, p.H, p.G), dim3(64 * nw), sh, st, p);
-  else if (causal) hipLaunchKernelGGL((attn_fwd_kernel<D, false, 4, true>), dim3(gx, p.H, p.G), dim3(64 * nw), sh, st, p);   // (L <= 64: one 4-tile chunk)
-  else if (small_chunk(p, p.Lk)) hipLaunchKernelGGL((attn_fwd_kernel<D, false, 4>), dim3(gx, p.H, p.G), dim3(64 * nw), sh, st, p);
-  else hipLaunchKernelGGL((attn_fwd_kernel<D, false>), dim3(gx, p.H, p.G), dim3(64 * nw), sh, st, p);
+// Launch K as the plan says.  A form's dynamic-LDS limit is raised here, on the function that is about to be launched, the first time a
+// device launches it with more than the default limit (only the WINDOW forms can ask for that much: the bias table of a large window).
+using AttnKernel = void (*)(AttnP);
+template <AttnKernel K>
+int launch_as(AttnP& p, const AttnPlan& a, hipStream_t st) {
+  static bool raised[16] = {};
+  if (a.lds > 64 * 1024 && fiber_first_on_device(raised))
+    hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  p.tpc_cap = a.tpc_cap; p.chrows = a.chrows;
+  hipLaunchKernelGGL(K, dim3(a.gx, a.gy, a.gz), dim3(64 * a.nw), a.lds, st, p);
   FIBER_CHECK_LAUNCH();
   return FIBER_OK;
 }
 
+// (mode, slots) -> template, one launcher per kernel family.  WINDOW mode is head_dim 32 and the 10-slot form; CAUSAL the 4-slot form; a
+// combination attn_plan() does not produce is refused, not served by another template.
 template <int D>
-int launch_bwd(AttnP& p, float* delta, float* dbias_table, float* dbias_ws, int nz, hipStream_t st, bool causal = false) {
-  const int rows_q = p.G * p.Lq;
-  {
-    const size_t total = (size_t)rows_q * p.H * (D / 8);
-    int grid = (int)((total + 255) / 256);
-    grid = grid > 2048 ? 2048 : grid;
-    hipLaunchKernelGGL((attn_delta_kernel<D>), dim3(grid), dim3(256), 0, st, (const bf16*)p.o, p.dout, delta, rows_q, p.H, p.ldo, p.lddo);
-    FIBER_CHECK_LAUNCH();
-  }
-  p.delta = delta;
-  const int nb = p.window ? (2 * p.ws - 1) * (2 * p.ws - 1) : 0;
-  {
-    const int nstrips = cdiv(p.Lq, 16);
-    int nw = pick_waves(nstrips, p.Lk);
-    launch_geometry(p, p.Lk, nw, true);                  // (the chunking only changes at nw <= 4, the cap below only acts on nw > 8)
-    const bool wide_form = p.window || (!small_chunk(p, p.Lk) && chunk_tiles(p, p.Lk) > 6);
-    if (wide_form && nw > 8) nw = 8;                     // launch bound of those instantiations (strips beyond 8 go to further workgroups)
-    int gz = p.G;
-    p.groups_per_block = 1;
-    p.dbias_part = nullptr;
-    if (p.window) {
-      gz = nz;
-      p.groups_per_block = cdiv(p.G, nz);
-      gz = cdiv(p.G, p.groups_per_block);
-      p.dbias_part = dbias_ws;
-    }
-    launch_geometry(p, p.Lk, nw, true);
-    const size_t sh = lds_bytes<D>(nb, 2, p.chrows);
-    if (p.window) hipLaunchKernelGGL((attn_bwd_dq_kernel<D, true>), dim3(cdiv(nstrips, nw), p.H, gz), dim3(64 * nw), sh, st, p);
-    else if (causal) hipLaunchKernelGGL((attn_bwd_dq_kernel<D, false, 4, true>), dim3(strip_blocks(p, p.Lk, nstrips, nw, p.H * gz, false), p.H, gz), dim3(64 * nw), sh, st, p);
-    else if (small_chunk(p, p.Lk)) hipLaunchKernelGGL((attn_bwd_dq_kernel<D, false, 4>), dim3(strip_blocks(p, p.Lk, nstrips, nw, p.H * gz, false), p.H, gz), dim3(64 * nw), sh, st, p);
-    else if (chunk_tiles(p, p.Lk) <= 6) hipLaunchKernelGGL((attn_bwd_dq_kernel<D, false, 6>), dim3(strip_blocks(p, p.Lk, nstrips, nw, p.H * gz, false), p.H, gz), dim3(64 * nw), sh, st, p);   // (t2i: 5-tile chunks; the 10-slot form spills)
-    else hipLaunchKernelGGL((attn_bwd_dq_kernel<D, false>), dim3(strip_blocks(p, p.Lk, nstrips, nw, p.H * gz, false), p.H, gz), dim3(64 * nw), sh, st, p);
-    FIBER_CHECK_LAUNCH();
-    if (p.window) {
-      if (hipMemsetAsync(dbias_table, 0, (size_t)nb * p.H * sizeof(float), st) != hipSuccess) return FIBER_ELAUNCH;
-      hipLaunchKernelGGL(dbias_scatter_kernel, dim3(p.Lq, p.H), dim3(256), 0, st, dbias_ws, dbias_table, gz, p.H, p.ws);
-      FIBER_CHECK_LAUNCH();
-    }
-  }
-  {
-    const int nstrips = cdiv(p.Lk, 16);
-    int nw = pick_waves(nstrips, 1 << 20);               // key-strip pass: measured worse with small workgroups
-    launch_geometry(p, p.Lq, nw, true);
-    if (!p.window && D == 64 && !small_chunk(p, p.Lq) && nw > 8) nw = 8;   // launch bound of that instantiation (the chunking only changes at nw <= 4)
-    const size_t sh = lds_bytes<D>(nb, 2, p.chrows);
-    // query side in one staged chunk: the kernel stages it once and walks key strips, so only as many workgroups per (head, sample) as it
-    // takes to fill the chip (strip_blocks); otherwise one workgroup per nw strips
-    static const int once_env = getenv("FIBER_ATTN_DKV_ONCE") ? atoi(getenv("FIBER_ATTN_DKV_ONCE")) : 1;   // 0: one strip per wave (A/B runs)
-    const int gx = once_env ? strip_blocks(p, p.Lq, nstrips, nw, p.H * p.G, false) : cdiv(nstrips, nw);
-    if (p.window) hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, true>), dim3(cdiv(nstrips, nw), p.H, p.G), dim3(64 * nw), sh, st, p);
-    else if (causal) hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, false, 4, true>), dim3(gx, p.H, p.G), dim3(64 * nw), sh, st, p);
-    else if (small_chunk(p, p.Lq)) hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, false, 4>), dim3(gx, p.H, p.G), dim3(64 * nw), sh, st, p);
-    else hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, false>), dim3(gx, p.H, p.G), dim3(64 * nw), sh, st, p);
-    FIBER_CHECK_LAUNCH();
-  }
-  return FIBER_OK;
+int launch_fwd(AttnP& p, const AttnPlan& a, bool causal, hipStream_t st) {
+  if (p.window) return (D == 32 && !causal && a.slots == 10) ? launch_as<attn_fwd_kernel<32, true>>(p, a, st) : FIBER_EINVAL;
+  if (causal) return a.slots == 4 ? launch_as<attn_fwd_kernel<D, false, 4, true>>(p, a, st) : FIBER_EINVAL;
+  if (a.slots == 4) return launch_as<attn_fwd_kernel<D, false, 4>>(p, a, st);
+  if (a.slots == 10) return launch_as<attn_fwd_kernel<D, false>>(p, a, st);
+  return FIBER_EINVAL;
+}
+template <int D>
+int launch_dq(AttnP& p, const AttnPlan& a, bool causal, hipStream_t st) {
+  if (p.window) return (D == 32 && !causal && a.slots == 10) ? launch_as<attn_bwd_dq_kernel<32, true>>(p, a, st) : FIBER_EINVAL;
+  if (causal) return a.slots == 4 ? launch_as<attn_bwd_dq_kernel<D, false, 4, true>>(p, a, st) : FIBER_EINVAL;
+  if (a.slots == 4) return launch_as<attn_bwd_dq_kernel<D, false, 4>>(p, a, st);
+  if (a.slots == 6) return launch_as<attn_bwd_dq_kernel<D, false, 6>>(p, a, st);
+  if (a.slots == 10) return launch_as<attn_bwd_dq_kernel<D, false>>(p, a, st);
+  return FIBER_EINVAL;
+}
+template <int D>
+int launch_dkv(AttnP& p, const AttnPlan& a, bool causal, hipStream_t st) {
+  if (p.window) return (D == 32 && !causal && a.slots == 10) ? launch_as<attn_bwd_dkv_kernel<32, true>>(p, a, st) : FIBER_EINVAL;
+  if (causal) return a.slots == 4 ? launch_as<attn_bwd_dkv_kernel<D, false, 4, true>>(p, a, st) : FIBER_EINVAL;
+  if (a.slots == 4) return launch_as<attn_bwd_dkv_kernel<D, false, 4>>(p, a, st);
+  if (a.slots == 10) return launch_as<attn_bwd_dkv_kernel<D, false>>(p, a, st);
+  return FIBER_EINVAL;
 }
 
-bool attr_done[16] = {};
-void ensure_attrs() {
-  if (!fiber_first_on_device(attr_done)) return;
-  const int big = 160 * 1024;
-  hipFuncSetAttribute((const void*)attn_fwd_kernel<32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)attn_fwd_kernel<32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)attn_fwd_kernel<64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)attn_fwd_kernel<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+template <int D>
+int run_fwd(AttnP& p, bool causal, hipStream_t st) {
+  return launch_fwd<D>(p, attn_plan(ATTN_FWD, D, p.Lq, p.Lk, p.H, p.G, p.window ? p.ws : 0, 1), causal, st);
 }
+
+// delta, then pass A (dQ; WINDOW: the bias gradient in nz slices of dbias_ws, folded into dbias_table), then pass B (dK, dV)
+template <int D>
+int run_bwd(AttnP& p, bool causal, float* delta, float* dbias_table, float* dbias_ws, int nz, hipStream_t st) {
+  const int rows_q = p.G * p.Lq, ws = p.window ? p.ws : 0;
+  const size_t total = (size_t)rows_q * p.H * (D / 8);
+  const int grid = total > 2048 * (size_t)256 ? 2048 : (int)((total + 255) / 256);
+  hipLaunchKernelGGL((attn_delta_kernel<D>), dim3(grid), dim3(256), 0, st, (const bf16*)p.o, p.dout, delta, rows_q, p.H, p.ldo, p.lddo);
+  FIBER_CHECK_LAUNCH();
+  p.delta = delta;
+  const AttnPlan dq = attn_plan(ATTN_DQ, D, p.Lq, p.Lk, p.H, p.G, ws, nz);
+  p.groups_per_block = dq.groups_per_block;
+  p.dbias_part = p.window ? dbias_ws : nullptr;
+  if (const int rc = launch_dq<D>(p, dq, causal, st)) return rc;
+  if (p.window) {
+    const int nb = (2 * ws - 1) * (2 * ws - 1);
+    if (hipMemsetAsync(dbias_table, 0, (size_t)nb * p.H * sizeof(float), st) != hipSuccess) return FIBER_ELAUNCH;
+    hipLaunchKernelGGL(dbias_scatter_kernel, dim3(p.Lq, p.H), dim3(256), 0, st, dbias_ws, dbias_table, dq.gz, p.H, p.ws);
+    FIBER_CHECK_LAUNCH();
+  }
+  return launch_dkv<D>(p, attn_plan(ATTN_DKV, D, p.Lk, p.Lq, p.H, p.G, ws, nz), causal, st);
+}
+
+// AttnP from the arguments of the C ABI (G groups of Lq queries and Lk keys); a forward passes null gradient pointers and zero leading
+// dimensions.  The WINDOW entry points add their geometry.
+AttnP attn_params(const void* q, const void* k, const void* v, const float* kmask, const void* o, const float* lse, const void* dout, void* dq,
+                  void* dk, void* dv, int G, int heads, int Lq, int Lk, int ldq, int ldk, int ldv, int ldo, int lddo, int lddq, int lddk,
+                  int lddv, float scale, float p_drop, uint64_t seed, const uint64_t* seed_base) {
+  AttnP p{};
+  p.q = (const bf16*)q; p.k = (const bf16*)k; p.v = (const bf16*)v; p.o = (bf16*)o; p.lse = (float*)lse;
+  p.dout = (const bf16*)dout; p.dq = (bf16*)dq; p.dk = (bf16*)dk; p.dv = (bf16*)dv;
+  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
+  p.H = heads; p.Lq = Lq; p.Lk = Lk; p.G = G; p.scale = scale; p.kmask = kmask; p.p_drop = p_drop; p.seed = seed; p.seed_base = seed_base;
+  return p;
+}
+// qkv [B*Hres*Wres, 3C] in the reference layout [3][heads][32] (dqkv likewise, or null), scale 32^-0.5
+AttnP window_params(const void* qkv, const float* bias_table, const void* o, const float* lse, const void* dout, void* dqkv, int B, int Hres,
+                    int Wres, int C, int heads, int ws, int shift) {
+  const bf16* base = (const bf16*)qkv;
+  bf16* dbase = (bf16*)dqkv;
+  const int ldg = dqkv ? 3 * C : 0, nWw = Wres / ws, nW = (Hres / ws) * nWw;
+  AttnP p = attn_params(base, base + C, base + 2 * C, nullptr, o, lse, dout, dbase, dqkv ? dbase + C : nullptr, dqkv ? dbase + 2 * C : nullptr,
+                        B * nW, heads, ws * ws, ws * ws, 3 * C, 3 * C, 3 * C, C, dout ? C : 0, ldg, ldg, ldg, 0.17677669529663687f, 0.f, 0, nullptr);
+  p.window = 1; p.Hres = Hres; p.Wres = Wres; p.ws = ws; p.shift = shift; p.nWw = nWw; p.nW = nW; p.bias_table = bias_table;
+  return p;
+}
+
+// FIBER_ATTN_T2I_ONEPASS / FIBER_ATTN_I2T_ONEPASS = 0: the generic kernels where fiber_mha_* would take the one-pass kernels of attn_x.hip
+// (tools/probes/mha_precision.py compares the two selections)
+int env_int(const char* name, int dflt) { const char* s = getenv(name); return s ? atoi(s) : dflt; }
+bool t2i_onepass() { static const bool on = env_int("FIBER_ATTN_T2I_ONEPASS", 1) != 0; return on; }
+bool i2t_onepass() { static const bool on = env_int("FIBER_ATTN_I2T_ONEPASS", 1) != 0; return on; }
 
 }  // namespace
 
@@ -825,11 +842,15 @@ int fiber_win_bwd_launch(const void* qkv, const float* bias_table, const void* o
                          void* dqkv, float* dbias_table, float* delta_ws, float* dbias_ws, float* dqkv_colsum, float* colsum_ws,
                          int B, int Hres, int Wres, int C, int heads, int ws, int shift, int hmajor, hipStream_t st);
 int fiber_win_colsum_rows(int n_windows, int heads, int N);
-// one-pass backward of image -> text cross attention (attn_x.hip); FIBER_EINVAL = shape not served
+// One-pass kernels of attn_x.hip.  Each launcher decides by itself whether it serves a call and returns FIBER_EINVAL when it does not (the
+// generic passes then run); the callers below test only what a launcher is not told: the head_dim, and for i2t that there is no dropout.
+// image -> text cross attention (head_dim 32, few keys)
 int fiber_i2t_bwd_launch(const void* q, const void* k, const void* v, const float* kmask, const void* o, const void* dout, const float* lse,
                          void* dq, void* dk, void* dv, int B, int heads, int Lq, int Lk, int ldq, int ldk, int ldv, int ldo, int lddo,
                          int lddq, int lddk, int lddv, float scale, hipStream_t st);
-// the same for head_dim 64 and at most 48 queries (text -> image cross attention, text self attention), dropout included
+int fiber_i2t_fwd_launch(const void* q, const void* k, const void* v, const float* kmask, void* o, float* lse, int B, int heads, int Lq, int Lk,
+                         int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t st);
+// head_dim 64 and few queries (text -> image cross attention, text self attention), dropout included
 int fiber_t2i_bwd_launch(const void* q, const void* k, const void* v, const float* kmask, const void* o, const void* dout, const float* lse,
                          void* dq, void* dk, void* dv, int B, int heads, int Lq, int Lk, int ldq, int ldk, int ldv, int ldo, int lddo,
                          int lddq, int lddk, int lddv, float scale, float p_drop, uint64_t seed, const uint64_t* seed_base, bool causal,
@@ -837,8 +858,42 @@ int fiber_t2i_bwd_launch(const void* q, const void* k, const void* v, const floa
 int fiber_t2i_fwd_launch(const void* q, const void* k, const void* v, const float* kmask, void* o, float* lse, int B, int heads, int Lq, int Lk,
                          int ldq, int ldk, int ldv, int ldo, float scale, float p_drop, uint64_t seed, const uint64_t* seed_base, bool causal,
                          hipStream_t st);
-int fiber_i2t_fwd_launch(const void* q, const void* k, const void* v, const float* kmask, void* o, float* lse, int B, int heads, int Lq, int Lk,
-                         int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t st);
+
+namespace {
+
+// Forward of fiber_mha_fwd_bf16 / fiber_mha_causal_fwd_bf16 (arguments validated by the entry point): the one-pass kernels where they serve
+// the call, else the generic kernel.  The causal entry points take the t2i kernels whatever FIBER_ATTN_T2I_ONEPASS says.
+int mha_fwd(bool causal, const void* q, const void* k, const void* v, const float* kmask, void* o, float* lse, int B, int heads, int Lq,
+            int Lk, int D, int ldq, int ldk, int ldv, int ldo, float scale, float p_drop, uint64_t seed, const uint64_t* seed_base,
+            hipStream_t stream) {
+  int rc = FIBER_EINVAL;
+  if (D == 32 && !causal && p_drop == 0.f && i2t_onepass())
+    rc = fiber_i2t_fwd_launch(q, k, v, kmask, o, lse, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, scale, stream);
+  if (D == 64 && (causal || t2i_onepass()))
+    rc = fiber_t2i_fwd_launch(q, k, v, kmask, o, lse, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, scale, p_drop, seed, seed_base, causal, stream);
+  if (rc != FIBER_EINVAL) return rc;
+  AttnP p = attn_params(q, k, v, kmask, o, lse, nullptr, nullptr, nullptr, nullptr, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, 0, 0, 0, 0, scale,
+                        p_drop, seed, seed_base);
+  return D == 32 ? run_fwd<32>(p, causal, stream) : run_fwd<64>(p, causal, stream);
+}
+
+// Backward of the same (the one-pass kernels leave delta_ws unused)
+int mha_bwd(bool causal, const void* q, const void* k, const void* v, const float* kmask, const void* o, const void* dout, const float* lse,
+            void* dq, void* dk, void* dv, float* delta_ws, int B, int heads, int Lq, int Lk, int D, int ldq, int ldk, int ldv, int ldo,
+            int lddo, int lddq, int lddk, int lddv, float scale, float p_drop, uint64_t seed, const uint64_t* seed_base, hipStream_t stream) {
+  int rc = FIBER_EINVAL;
+  if (D == 32 && !causal && p_drop == 0.f && i2t_onepass())
+    rc = fiber_i2t_bwd_launch(q, k, v, kmask, o, dout, lse, dq, dk, dv, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, scale, stream);
+  if (D == 64 && (causal || t2i_onepass()))
+    rc = fiber_t2i_bwd_launch(q, k, v, kmask, o, dout, lse, dq, dk, dv, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, scale,
+                              p_drop, seed, seed_base, causal, stream);
+  if (rc != FIBER_EINVAL) return rc;
+  AttnP p = attn_params(q, k, v, kmask, o, lse, dout, dq, dk, dv, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, scale, p_drop,
+                        seed, seed_base);
+  return D == 32 ? run_bwd<32>(p, causal, delta_ws, nullptr, nullptr, 1, stream) : run_bwd<64>(p, causal, delta_ws, nullptr, nullptr, 1, stream);
+}
+
+}  // namespace
 
 // --------------------------------------------------------------------------------------------------- C ABI
 // Window attention in image-token order.  qkv: [B*Hres*Wres, 3C] bf16 with channel layout [3][heads][32]
@@ -850,15 +905,8 @@ extern "C" int fiber_window_attn_fwd_bf16(const void* qkv, const float* bias_tab
   if (C != heads * 32 || Hres % ws || Wres % ws || shift < 0 || shift >= ws) return FIBER_EINVAL;
   if (ws * ws <= 336) return fiber_win_fwd_launch(qkv, bias_table, o, lse, B, Hres, Wres, C, heads, ws, shift, head_major, stream);
   if (head_major) return FIBER_EINVAL;                 // the generic (N > 336) path reads the reference layout only
-  ensure_attrs();
-  AttnP p{};
-  const bf16* base = (const bf16*)qkv;
-  p.q = base; p.k = base + C; p.v = base + 2 * C; p.o = (bf16*)o; p.lse = lse;
-  p.ldq = p.ldk = p.ldv = 3 * C; p.ldo = C;
-  p.H = heads; p.Lq = p.Lk = ws * ws; p.nWw = Wres / ws; p.nW = (Hres / ws) * p.nWw; p.G = B * p.nW;
-  p.scale = 0.17677669529663687f;  // 32^-0.5
-  p.window = 1; p.Hres = Hres; p.Wres = Wres; p.ws = ws; p.shift = shift; p.bias_table = bias_table;
-  return launch_fwd<32>(p, stream);
+  AttnP p = window_params(qkv, bias_table, o, lse, nullptr, nullptr, B, Hres, Wres, C, heads, ws, shift);
+  return run_fwd<32>(p, false, stream);
 }
 
 // Number of partial-gradient slices pass A uses for B*nW windows; workspace = slices * heads * N * N floats.
@@ -881,17 +929,8 @@ extern "C" int fiber_window_attn_bwd_bf16(const void* qkv, const float* bias_tab
     return fiber_win_bwd_launch(qkv, bias_table, o, dout, lse, dqkv, dbias_table, delta_ws, dbias_ws, dqkv_colsum, colsum_ws, B,
                                 Hres, Wres, C, heads, ws, shift, head_major, stream);
   if (head_major || dqkv_colsum || colsum_ws) return FIBER_EINVAL;   // (fiber_window_attn_colsum_rows() returns 0 for this path)
-  ensure_attrs();
-  AttnP p{};
-  const bf16* base = (const bf16*)qkv;
-  bf16* dbase = (bf16*)dqkv;
-  p.q = base; p.k = base + C; p.v = base + 2 * C; p.o = (bf16*)o; p.lse = (float*)lse; p.dout = (const bf16*)dout;
-  p.dq = dbase; p.dk = dbase + C; p.dv = dbase + 2 * C;
-  p.ldq = p.ldk = p.ldv = p.lddq = p.lddk = p.lddv = 3 * C; p.ldo = p.lddo = C;
-  p.H = heads; p.Lq = p.Lk = ws * ws; p.nWw = Wres / ws; p.nW = (Hres / ws) * p.nWw; p.G = B * p.nW;
-  p.scale = 0.17677669529663687f;
-  p.window = 1; p.Hres = Hres; p.Wres = Wres; p.ws = ws; p.shift = shift; p.bias_table = bias_table;
-  return launch_bwd<32>(p, delta_ws, dbias_table, dbias_ws, fiber_window_attn_bwd_slices(p.G, heads), stream);
+  AttnP p = window_params(qkv, bias_table, o, lse, dout, dqkv, B, Hres, Wres, C, heads, ws, shift);
+  return run_bwd<32>(p, false, delta_ws, dbias_table, dbias_ws, fiber_window_attn_bwd_slices(p.G, heads), stream);
 }
 
 // Generic multi-head attention: q [B*Lq, ldq], k/v [B*Lk, ldk/ldv], o [B*Lq, ldo]; head h occupies columns
@@ -901,23 +940,7 @@ extern "C" int fiber_mha_fwd_bf16(const void* q, const void* k, const void* v, c
                                   int B, int heads, int Lq, int Lk, int D, int ldq, int ldk, int ldv, int ldo,
                                   float scale, float p_drop, uint64_t seed, const uint64_t* seed_base, hipStream_t stream) {
   if ((D != 32 && D != 64) || (ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 3) || Lq <= 0 || Lk <= 0) return FIBER_EINVAL;
-  // few queries, head_dim 64 (text -> image cross attention, text self attention): streaming forward with Q in registers (attn_x.hip)
-  static const int onepass_t = getenv("FIBER_ATTN_T2I_ONEPASS") ? atoi(getenv("FIBER_ATTN_T2I_ONEPASS")) : 1;   // 0: the generic kernel (A/B runs)
-  static const int onepass_i = getenv("FIBER_ATTN_I2T_ONEPASS") ? atoi(getenv("FIBER_ATTN_I2T_ONEPASS")) : 1;
-  if (onepass_i && D == 32 && Lk <= 48 && p_drop == 0.f) {   // few keys, head_dim 32 (image -> text cross attention): K / V in registers
-    const int rc = fiber_i2t_fwd_launch(q, k, v, kmask, o, lse, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, scale, stream);
-    if (rc != FIBER_EINVAL) return rc;
-  }
-  if (onepass_t && D == 64 && Lq <= 48) {
-    const int rc = fiber_t2i_fwd_launch(q, k, v, kmask, o, lse, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, scale, p_drop, seed, seed_base, false, stream);
-    if (rc != FIBER_EINVAL) return rc;
-  }
-  ensure_attrs();
-  AttnP p{};
-  p.q = (const bf16*)q; p.k = (const bf16*)k; p.v = (const bf16*)v; p.o = (bf16*)o; p.lse = lse;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-  p.H = heads; p.Lq = Lq; p.Lk = Lk; p.G = B; p.scale = scale; p.kmask = kmask; p.p_drop = p_drop; p.seed = seed; p.seed_base = seed_base;
-  return D == 32 ? launch_fwd<32>(p, stream) : launch_fwd<64>(p, stream);
+  return mha_fwd(false, q, k, v, kmask, o, lse, B, heads, Lq, Lk, D, ldq, ldk, ldv, ldo, scale, p_drop, seed, seed_base, stream);
 }
 
 // Backward: dq/dk/dv have the same row layout as q/k/v with leading dims lddq/lddk/lddv; delta_ws fp32 [B*Lq*heads].
@@ -929,27 +952,8 @@ extern "C" int fiber_mha_bwd_bf16(const void* q, const void* k, const void* v, c
   if ((D != 32 && D != 64) || (ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 7) || (lddo & 7) || (lddq & 3) || (lddk & 3) ||
       (lddv & 3) || Lq <= 0 || Lk <= 0)
     return FIBER_EINVAL;
-  // few keys, head_dim 32, no dropout (image -> text cross attention): one pass with K / V in registers (delta_ws stays unused)
-  static const int onepass = getenv("FIBER_ATTN_I2T_ONEPASS") ? atoi(getenv("FIBER_ATTN_I2T_ONEPASS")) : 1;   // 0: the generic three kernels (A/B runs)
-  if (onepass && D == 32 && Lk <= 48 && p_drop == 0.f && (Lq & 15) == 0 && (heads & 3) == 0 && !(lddq & 7)) {
-    const int rc = fiber_i2t_bwd_launch(q, k, v, kmask, o, dout, lse, dq, dk, dv, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv,
-                                        scale, stream);
-    if (rc != FIBER_EINVAL) return rc;
-  }
-  // few queries, head_dim 64 (text -> image cross attention, text self attention): one pass with Q / dO in registers
-  static const int onepass_t = getenv("FIBER_ATTN_T2I_ONEPASS") ? atoi(getenv("FIBER_ATTN_T2I_ONEPASS")) : 1;
-  if (onepass_t && D == 64 && Lq <= 48) {
-    const int rc = fiber_t2i_bwd_launch(q, k, v, kmask, o, dout, lse, dq, dk, dv, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv,
-                                        scale, p_drop, seed, seed_base, false, stream);
-    if (rc != FIBER_EINVAL) return rc;
-  }
-  ensure_attrs();
-  AttnP p{};
-  p.q = (const bf16*)q; p.k = (const bf16*)k; p.v = (const bf16*)v; p.o = (bf16*)o; p.lse = (float*)lse;
-  p.dout = (const bf16*)dout; p.dq = (bf16*)dq; p.dk = (bf16*)dk; p.dv = (bf16*)dv;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
-  p.H = heads; p.Lq = Lq; p.Lk = Lk; p.G = B; p.scale = scale; p.kmask = kmask; p.p_drop = p_drop; p.seed = seed; p.seed_base = seed_base;
-  return D == 32 ? launch_bwd<32>(p, delta_ws, nullptr, nullptr, 1, stream) : launch_bwd<64>(p, delta_ws, nullptr, nullptr, 1, stream);
+  return mha_bwd(false, q, k, v, kmask, o, dout, lse, dq, dk, dv, delta_ws, B, heads, Lq, Lk, D, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv,
+                 scale, p_drop, seed, seed_base, stream);
 }
 
 // Causal self-attention (text decoder, roberta.py _prepare_decoder_attention_mask): softmax(q.k^T*scale + kmask[b, j] + (j > i ? -inf : 0)).v.
@@ -962,15 +966,7 @@ extern "C" int fiber_mha_causal_fwd_bf16(const void* q, const void* k, const voi
   if ((D != 32 && D != 64) || Lq != Lk || Lq <= 0 || Lq > 64 || B <= 0 || heads <= 0 || (ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 7) ||
       p_drop < 0.f || p_drop >= 1.f)
     return FIBER_EINVAL;
-  if (D == 64 && Lq <= 48) {
-    const int rc = fiber_t2i_fwd_launch(q, k, v, kmask, o, lse, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, scale, p_drop, seed, seed_base, true, stream);
-    if (rc != FIBER_EINVAL) return rc;
-  }
-  AttnP p{};
-  p.q = (const bf16*)q; p.k = (const bf16*)k; p.v = (const bf16*)v; p.o = (bf16*)o; p.lse = lse;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-  p.H = heads; p.Lq = Lq; p.Lk = Lk; p.G = B; p.scale = scale; p.kmask = kmask; p.p_drop = p_drop; p.seed = seed; p.seed_base = seed_base;
-  return D == 32 ? launch_fwd<32>(p, stream, true) : launch_fwd<64>(p, stream, true);
+  return mha_fwd(true, q, k, v, kmask, o, lse, B, heads, Lq, Lk, D, ldq, ldk, ldv, ldo, scale, p_drop, seed, seed_base, stream);
 }
 
 extern "C" int fiber_mha_causal_bwd_bf16(const void* q, const void* k, const void* v, const float* kmask, const void* o,
@@ -981,15 +977,7 @@ extern "C" int fiber_mha_causal_bwd_bf16(const void* q, const void* k, const voi
   if ((D != 32 && D != 64) || Lq != Lk || Lq <= 0 || Lq > 64 || B <= 0 || heads <= 0 || (ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 7) ||
       (lddo & 7) || (lddq & 7) || (lddk & 7) || (lddv & 7) || p_drop < 0.f || p_drop >= 1.f)
     return FIBER_EINVAL;
-  if (D == 64 && Lq <= 48) {
-    const int rc = fiber_t2i_bwd_launch(q, k, v, kmask, o, dout, lse, dq, dk, dv, B, heads, Lq, Lk, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv,
-                                        scale, p_drop, seed, seed_base, true, stream);
-    if (rc != FIBER_EINVAL) return rc;
-  }
-  AttnP p{};
-  p.q = (const bf16*)q; p.k = (const bf16*)k; p.v = (const bf16*)v; p.o = (bf16*)o; p.lse = (float*)lse;
-  p.dout = (const bf16*)dout; p.dq = (bf16*)dq; p.dk = (bf16*)dk; p.dv = (bf16*)dv;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
-  p.H = heads; p.Lq = Lq; p.Lk = Lk; p.G = B; p.scale = scale; p.kmask = kmask; p.p_drop = p_drop; p.seed = seed; p.seed_base = seed_base;
-  return D == 32 ? launch_bwd<32>(p, delta_ws, nullptr, nullptr, 1, stream, true) : launch_bwd<64>(p, delta_ws, nullptr, nullptr, 1, stream, true);
+  return mha_bwd(true, q, k, v, kmask, o, dout, lse, dq, dk, dv, delta_ws, B, heads, Lq, Lk, D, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv,
+                 scale, p_drop, seed, seed_base, stream);
 }
+

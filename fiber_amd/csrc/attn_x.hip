@@ -5,8 +5,9 @@
 // The generic kernels of attn.hip treat both sides alike (key chunks staged in LDS per workgroup behind barriers; a delta kernel, a query-strip
 // pass and a key-strip pass in the backward, K / V read twice): these sites ran at 1.5-2.7 TB/s of their bytes (0.19-0.34 of the HBM floor).
 // Here the small side of a (sample, head) lives in REGISTERS as MFMA operands (in both orientations where needed) and the large side is streamed
-// through once, 16 rows per step, with no workgroup barrier inside the stream; fiber_mha_fwd_bf16 / fiber_mha_bwd_bf16 dispatch here when the
-// shape fits (FIBER_ATTN_I2T_ONEPASS / FIBER_ATTN_T2I_ONEPASS = 0: the generic kernels, for A/B runs) and fall back otherwise.
+// through once, 16 rows per step, with no workgroup barrier inside the stream; fiber_mha_fwd_bf16 / fiber_mha_bwd_bf16 try the fiber_*_launch
+// functions at the end of this file on head_dim alone (FIBER_ATTN_I2T_ONEPASS / FIBER_ATTN_T2I_ONEPASS = 0: not at all, for A/B runs); those
+// functions are the only statement of which calls are served, and on their FIBER_EINVAL the generic kernels run.
 //
 // ---- image -> text, backward ---------------------------------------------------------------------------------------------------------
 // The text side is tiny -- K and V of one (sample, head) are

@@ -1226,32 +1226,41 @@ def _ld(t):
     return t.stride(0)
 
 
+def _mha_fwd(q, k, v, kmask, B, heads, scale, p_drop, seed, base, causal=False):
+    """fiber_mha_fwd_bf16 (causal: fiber_mha_causal_fwd_bf16) on q [B*Lq, heads*D], k / v [B*Lk, heads*D], possibly column views of a
+    packed projection -> (o, lse)"""
+    o = torch.empty(q.shape, dtype=BF16, device=q.device)
+    lse = torch.empty((q.shape[0], heads), dtype=torch.float32, device=q.device)
+    lib.call("fiber_mha_causal_fwd_bf16" if causal else "fiber_mha_fwd_bf16", lib.ptr(q), lib.ptr(k), lib.ptr(v), lib.ptr(kmask), lib.ptr(o),
+             lib.ptr(lse), B, heads, q.shape[0] // B, k.shape[0] // B, q.shape[1] // heads, _ld(q), _ld(k), _ld(v), _ld(o), scale, p_drop,
+             seed, base)
+    return o, lse
+
+
+def _mha_bwd(q, k, v, kmask, o, lse, do, dq, dk, dv, B, heads, scale, p_drop, seed, base, causal=False):
+    """the backward of _mha_fwd into dq / dk / dv (possibly column views of a packed gradient)"""
+    do = _c(do)
+    delta = torch.empty((q.shape[0], heads), dtype=torch.float32, device=q.device)
+    lib.call("fiber_mha_causal_bwd_bf16" if causal else "fiber_mha_bwd_bf16", lib.ptr(q), lib.ptr(k), lib.ptr(v), lib.ptr(kmask), lib.ptr(o),
+             lib.ptr(do), lib.ptr(lse), lib.ptr(dq), lib.ptr(dk), lib.ptr(dv), lib.ptr(delta), B, heads, q.shape[0] // B, k.shape[0] // B,
+             q.shape[1] // heads, _ld(q), _ld(k), _ld(v), _ld(o), _ld(do), _ld(dq), _ld(dk), _ld(dv), scale, p_drop, seed, base)
+
+
 class _MHA(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, kmask, B, heads, scale, p_drop, seed):
-        # q [B*Lq, heads*D], k/v [B*Lk, heads*D] (possibly column views of a packed projection)
-        D = q.shape[1] // heads
-        Lq, Lk = q.shape[0] // B, k.shape[0] // B
-        o = torch.empty((q.shape[0], heads * D), dtype=BF16, device=q.device)
-        lse = torch.empty((q.shape[0], heads), dtype=torch.float32, device=q.device)
-        lib.call("fiber_mha_fwd_bf16", lib.ptr(q), lib.ptr(k), lib.ptr(v), lib.ptr(kmask), lib.ptr(o), lib.ptr(lse), B, heads, Lq, Lk, D,
-                 _ld(q), _ld(k), _ld(v), _ld(o), scale, p_drop, seed, seed_base_ptr())
+        ctx.cfg = (B, heads, scale, p_drop, seed, seed_base_ptr())
+        o, lse = _mha_fwd(q, k, v, kmask, *ctx.cfg)
         ctx.save_for_backward(q, k, v, kmask, o, lse)
-        ctx.cfg = (B, heads, Lq, Lk, D, scale, p_drop, seed, seed_base_ptr())
         return o
 
     @staticmethod
     def backward(ctx, do):
         q, k, v, kmask, o, lse = ctx.saved_tensors
-        B, heads, Lq, Lk, D, scale, p_drop, seed, base = ctx.cfg
-        do = _c(do)
-        dq = torch.empty((q.shape[0], heads * D), dtype=BF16, device=q.device)
-        dk = torch.empty((k.shape[0], heads * D), dtype=BF16, device=q.device)
+        dq = torch.empty_like(o)
+        dk = torch.empty((k.shape[0], o.shape[1]), dtype=BF16, device=q.device)
         dv = torch.empty_like(dk)
-        delta = torch.empty((q.shape[0], heads), dtype=torch.float32, device=q.device)
-        lib.call("fiber_mha_bwd_bf16", lib.ptr(q), lib.ptr(k), lib.ptr(v), lib.ptr(kmask), lib.ptr(o), lib.ptr(do), lib.ptr(lse),
-                 lib.ptr(dq), lib.ptr(dk), lib.ptr(dv), lib.ptr(delta), B, heads, Lq, Lk, D, _ld(q), _ld(k), _ld(v), _ld(o), _ld(do),
-                 _ld(dq), _ld(dk), _ld(dv), scale, p_drop, seed, base)
+        _mha_bwd(q, k, v, kmask, o, lse, do, dq, dk, dv, *ctx.cfg)
         return dq, dk, dv, None, None, None, None, None, None
 
 
@@ -1268,43 +1277,26 @@ class _MHAPacked(torch.autograd.Function):
     backward is one dgrad + one wgrad and autograd never assembles slices."""
 
     @staticmethod
+    def _views(a, b, mode):
+        """the q, k, v column blocks of a packed input (or of its gradient)"""
+        C = a.shape[1] // 3
+        return (a[:, :C], a[:, C:2 * C], a[:, 2 * C:]) if mode == 0 else (a, b[:, :a.shape[1]], b[:, a.shape[1]:])
+
+    @staticmethod
     def forward(ctx, a, b, kmask, mode, B, heads, scale, p_drop, seed, causal=False):
         a = _c(a)
         b = _c(b) if b is not None else None
-        if mode == 0:
-            C = a.shape[1] // 3
-            q, k, v = a[:, :C], a[:, C:2 * C], a[:, 2 * C:]
-        else:
-            C = a.shape[1]
-            q, k, v = a, b[:, :C], b[:, C:]
-        D = C // heads
-        Lq, Lk = q.shape[0] // B, k.shape[0] // B
-        o = torch.empty((q.shape[0], C), dtype=BF16, device=a.device)
-        lse = torch.empty((q.shape[0], heads), dtype=torch.float32, device=a.device)
-        base = seed_base_ptr()
-        lib.call("fiber_mha_causal_fwd_bf16" if causal else "fiber_mha_fwd_bf16", lib.ptr(q), lib.ptr(k), lib.ptr(v), lib.ptr(kmask),
-                 lib.ptr(o), lib.ptr(lse), B, heads, Lq, Lk, D, _ld(q), _ld(k), _ld(v), _ld(o), scale, p_drop, seed, base)
+        ctx.mode, ctx.cfg = mode, (B, heads, scale, p_drop, seed, seed_base_ptr(), causal)
+        o, lse = _mha_fwd(*_MHAPacked._views(a, b, mode), kmask, *ctx.cfg)
         ctx.save_for_backward(a, b, kmask, o, lse)
-        ctx.cfg = (mode, B, heads, Lq, Lk, D, C, scale, p_drop, seed, base, causal)
         return o
 
     @staticmethod
     def backward(ctx, do):
         a, b, kmask, o, lse = ctx.saved_tensors
-        mode, B, heads, Lq, Lk, D, C, scale, p_drop, seed, base, causal = ctx.cfg
-        do = _c(do)
         da = torch.empty_like(a)
         db = torch.empty_like(b) if b is not None else None
-        if mode == 0:
-            q, k, v = a[:, :C], a[:, C:2 * C], a[:, 2 * C:]
-            dq, dk, dv = da[:, :C], da[:, C:2 * C], da[:, 2 * C:]
-        else:
-            q, k, v = a, b[:, :C], b[:, C:]
-            dq, dk, dv = da, db[:, :C], db[:, C:]
-        delta = torch.empty((q.shape[0], heads), dtype=torch.float32, device=a.device)
-        lib.call("fiber_mha_causal_bwd_bf16" if causal else "fiber_mha_bwd_bf16", lib.ptr(q), lib.ptr(k), lib.ptr(v), lib.ptr(kmask),
-                 lib.ptr(o), lib.ptr(do), lib.ptr(lse), lib.ptr(dq), lib.ptr(dk), lib.ptr(dv), lib.ptr(delta), B, heads, Lq, Lk, D,
-                 _ld(q), _ld(k), _ld(v), _ld(o), _ld(do), _ld(dq), _ld(dk), _ld(dv), scale, p_drop, seed, base)
+        _mha_bwd(*_MHAPacked._views(a, b, ctx.mode), kmask, o, lse, do, *_MHAPacked._views(da, db, ctx.mode), *ctx.cfg)
         return da, db, None, None, None, None, None, None, None, None
 
 

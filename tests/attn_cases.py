@@ -4,19 +4,23 @@ the forward and the backward must launch.  Shared by tests/test_hip_attn_paths.p
 tools/probes/attn_paths.py (which kernels each case actually launched).  Also: the fp64 reference and its per-element bounds,
 used on the GPU by the path tests and on the host by tests/test_attn_compare_host.py.
 
-Selection, as read from the dispatch (attn.hip C ABI, win_attn.hip fiber_win_*_launch, attn_x.hip fiber_*_launch):
+Selection, as read from the dispatch (win_attn.hip fiber_win_*_launch; attn_x.hip fiber_*_launch, which alone decide whether a one-pass
+kernel serves a call -- attn.hip's mha_fwd / mha_bwd add only the head_dim and, for i2t, "no dropout"; attn.hip attn_plan() and
+launch_fwd / launch_dq / launch_dkv for the generic kernels):
   window, N = ws*ws <= 160, N != 144   win_fwd_kernel<1, 0>, win_bwd_dq / dkv_kernel<1, 0>; dbias fold (fold1 when heads*N*N is odd)
   window, N == 144                      win_fwd_kernel<1, 9>, win_bwd_fused_kernel<shift > 0>
   window, 160 < N <= 336                win_fwd_kernel<3, 0, 21, false>, win_bwd_dq / dkv_kernel<3, 0, 21, false>
   window, N > 336                       attn_fwd_kernel<32, true>, attn_delta_kernel, attn_bwd_dq / dkv_kernel<32, true>, dbias_scatter
   mha, D = 32, Lk <= 48, no dropout     i2t_fwd_kernel if Lq % 16 == 0 and heads % 4 == 0; i2t_bwd_kernel if also lddq % 8 == 0
   mha, D = 64, Lq <= 48, Lk <= 1024     t2i_fwd_kernel<DROP>, t2i_bwd_kernel<DROP> (all leading dimensions % 8 == 0)
-  mha otherwise                         attn_fwd_kernel<D, false, 4> when the key side is one chunk of <= 4 tiles, else <D, false>;
-                                        attn_bwd_dq_kernel<D, false, 4 | 6 | 10> by the key chunk's tiles, dkv <D, false, 4 | 10> by the
-                                        query chunk's
-  causal, D = 64, L <= 48               t2i_*_kernel<DROP, true>;  otherwise attn_*_kernel<D, false, 4, true>
-Not reached by default: win_bwd_fused_kernel<*, 11> (FIBER_WIN_BWD_WAVES=11), attn_*_kernel<64, true> (window head_dim is 32;
-instantiated for the attribute table only).
+  mha otherwise                         one attn_plan() per pass: the staged side (forward, dQ: keys; dK/dV: queries) is cut into equal
+                                        chunks of at most 10 tiles of 16 rows (8 forward / 5 backward for workgroups of <= 4 waves), and the
+                                        chunk's tiles pick the slot form: attn_fwd_kernel<D, false, 4 | 10> (<= 4 tiles or more),
+                                        attn_bwd_dq_kernel<D, false, 4 | 6 | 10> (<= 4, <= 6, more), attn_bwd_dkv_kernel<D, false, 4 | 10>
+  causal, D = 64, L <= 48               t2i_*_kernel<DROP, true>;  otherwise attn_*_kernel<D, false, 4, true> (L <= 64: one chunk of <= 4 tiles)
+A (mode, slots) pair outside this list is refused by the launchers (FIBER_EINVAL), not served by another template; the window mode of the
+generic kernels exists for head_dim 32 only.
+Not reached by default: win_bwd_fused_kernel<*, 11> (FIBER_WIN_BWD_WAVES=11).
 A sample whose every key is masked with finfo(fp32).min ("allmin") is the uniform average, as the reference's fp32 softmax gives it
 (finfo.min absorbs the scores); the kernels replace such scores by KMASK_SCORE (common.h), so its lse is private to the kernels."""
 import math
@@ -169,6 +173,13 @@ MHA_CASES = [
     _mha("g64-200x200-drop", 1, 2, 200, 200, 64, [_GF(64, 10)], _GB(64, 10, 10), p=0.1, packed=True),
     _mha("g64-lk1", 2, 3, 60, 1, 64, [_GF(64, 4)], _GB(64, 4, 4)),
     _mha("g64-allmin", 2, 3, 64, 50, 64, [_GF(64, 4)], _GB(64, 4, 4), mask="allmin"),
+    # launch geometry (attn_plan; profiles/attn_dispatch.md lists the branches): a capped grid whose 3-wave workgroups loop over query
+    # strips (forward, dQ: heads * B * 12 > 2048) or whose 8-wave workgroups loop over key strips (dK/dV: heads * B * 3 > 2048); 9 waves cut
+    # to the 8 that the 10-slot dQ form (18 strips) and the 10-slot D = 64 dQ and dK/dV forms (9 strips) are built for
+    _mha("g32-gridcap", 32, 6, 576, 40, 32, [_GF(32, 4)], _GB(32, 4, 10)),
+    _mha("g32-dkv-gridcap", 64, 16, 16, 257, 32, [_GF(32, 10)], _GB(32, 6, 4)),
+    _mha("g32-288x200", 2, 2, 288, 200, 32, [_GF(32, 10)], _GB(32, 10, 10)),
+    _mha("g64-144x144", 2, 2, 144, 144, 64, [_GF(64, 10)], _GB(64, 10, 10)),
 ]
 
 CAUSAL_CASES = []
