@@ -27,6 +27,10 @@ DEFAULTS = dict(
     # not a reference key: True = MLM head only on the rows that carry a label (objectives._mlm_head): same loss, gradients and accuracy,
     # but ret["mlm_logits"] is then [n_labelled, V]; the default keeps the reference's full [B, S, V] head
     mlm_compact_rows=False,
+    # not a reference key: True = compute_caption_cider runs the image tower ONCE with gradient and shares its tokens between sampling
+    # (detached), the RL pass (repeated per beam; autograd sums the beams) and the MLE term, instead of the reference's 1 + beam + 1 samples
+    # per image.  Each image then gets one DropPath draw instead of seven (beam 5), so the default keeps the reference's passes
+    caption_cider_share_image=False,
 )
 
 
@@ -41,7 +45,7 @@ def make_config(**over):
 
 
 # Named task configs of the path built here (reference config.py:95-110 pre-training with / without ITC, :134-150 VQAv2,
-# :235-250 COCO caption fine-tuning).
+# :235-250 COCO caption fine-tuning, :273-291 its CIDEr-optimisation stage).
 NAMED = {
     "task_pretrain_mlm_itm": dict(
         exp_name="mlm_itm", loss_names={"itm": 1, "mlm": 1}, draw_false_image=1, batch_size=4096, max_steps=100000,
@@ -58,6 +62,11 @@ NAMED = {
         exp_name="finetune_caption_mle_coco", datasets=["coco"], loss_names={"caption_mle": 1}, batch_size=512, max_epoch=10,
         max_steps=None, warmup_steps=0.1, learning_rate=5e-5, lr_mult_cross_modal=5, lr_mult_head=5, max_text_len=50,
         train_transform_keys=["albef_randaug"], val_transform_keys=["albef"], image_size=576, pretrained_vit=False),
+    "task_finetune_caption_cider_coco": dict(                             # reference config.py:273-291
+        exp_name="finetune_caption_cider_coco", datasets=["coco"], loss_names={"caption_cider": 1}, batch_size=512, max_epoch=10,
+        max_steps=None, warmup_steps=0.1, learning_rate=1e-6, lr_mult_cross_modal=5, lr_mult_head=5, max_text_len=50,
+        train_transform_keys=["albef_randaug"], val_transform_keys=["albef"], image_size=576, resolution_before=576,
+        pretrained_vit=False, cider_path="coco-train-words.p"),
 }
 
 

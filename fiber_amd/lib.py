@@ -54,6 +54,9 @@ SIGNATURES = {
     "fiber_ce_fwd_bf16": [P, P, P, P, P, I, I, L],
     "fiber_colsum_labelled_bf16": [P, P, P, P, I, I, L],
     "fiber_ce_bwd_bf16": [P, P, P, P, P, I, I, L],
+    "fiber_sample_rows_bf16": [P, P, P, P, P, I, I, I, I, U64, P, L, L],
+    "fiber_seqlogp_fwd_bf16": [P, P, P, P, I, I, L],
+    "fiber_seqlogp_bwd_bf16": [P, P, P, P, P, I, I, L],
     "fiber_adamw_multi_f32": [P, P, P, I, F, F, F, F, F, I, P],
     "fiber_grad_sqnorm_multi_f32": [P, P, P, I, P],
     "fiber_solver_finalize": [P, I, F, P, P, P, I, F, F, P],

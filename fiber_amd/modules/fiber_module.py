@@ -3,8 +3,10 @@
 Mirrors coarse_grained/fiber/modules/fiber_module.py: constructor wiring (:27-179), infer() (:224-367, fused branch
 :310-367, image-only :279-308, text-only :247-277), forward() (:431-471), training_step (:473-478),
 configure_optimizers (:522).  Parameter names / shapes equal the reference's so a `fiber_pretrain.ckpt` state dict loads
-(`load_path`, ITC queue keys dropped as at :141-146).  Captioning: caption_mle training and beam-search decoding (infer_caption
-:369-429, on the causal attention kernels); caption_gold / caption_cider (host-side CIDEr scoring) and NLVR2 raise if requested.
+(`load_path`, ITC queue keys dropped as at :141-146).  Captioning: caption_mle training, beam-search decoding (infer_caption
+:369-429, on the causal attention kernels) and caption_cider, the CIDEr-optimisation stage (sampled decoding and the sequence
+log-probability loss on HIP, CIDEr-D scored on the host: modules/cider.py; it needs config["cider_path"]); caption_gold and NLVR2 raise if
+requested.
 """
 import os
 import types
@@ -36,9 +38,15 @@ class FIBERTransformerSS(LightningModule):
         self.save_hyperparameters()
         self.config = config
         ln = config["loss_names"]
-        for k in ("caption_gold", "caption_cider", "nlvr2"):
+        for k in ("caption_gold", "nlvr2"):
             if ln.get(k, 0) > 0:
                 raise NotImplementedError(f"loss '{k}' is outside the fused-backbone hot path built here")
+        # caption_cider needs its document-frequency table (the named config's cider_path; the reference's CiderD(df=None) fails on open(None)).
+        # Scoring against the references of each training batch alone is not built as a default: with one image per batch every idf is
+        # log(beam) - log(beam) = 0 and every reward the same.  cider_path="corpus" asks for exactly that by name (benchmarks, tests).
+        if ln.get("caption_cider", 0) > 0 and not config.get("cider_path"):
+            raise NotImplementedError("loss 'caption_cider' without config['cider_path'] (the CIDEr-D document-frequency pickle, or \"corpus\") "
+                                      "is not built")
 
         bert_config = types.SimpleNamespace(        # RobertaConfig defaults: layer_norm_eps = 1e-12
             vocab_size=config["vocab_size"], hidden_size=config["hidden_size"], layer_norm_eps=1e-12)
@@ -103,7 +111,7 @@ class FIBERTransformerSS(LightningModule):
             self.cross_modal_image_pooler_itc.apply(objectives.init_weights)
             self.cross_modal_text_pooler_itc.apply(objectives.init_weights)
 
-        caption = ln.get("caption_mle", 0) > 0
+        caption = ln.get("caption_mle", 0) > 0 or ln.get("caption_cider", 0) > 0
         if ln.get("mlm", 0) > 0 or caption:                               # fiber_module.py:100-106
             self.mlm_score = heads.MLMHead(bert_config)
             self.mlm_score.apply(objectives.init_weights)
@@ -131,6 +139,10 @@ class FIBERTransformerSS(LightningModule):
             vs = config["vqav2_label_size"]
             self.vqa_classifier = heads.VQAClassifier(hs * 2, vs)
             self.vqa_classifier.apply(objectives.init_weights)
+
+        if ln.get("caption_cider", 0) > 0:                               # fiber_module.py:130-133
+            from .cider import CiderD
+            self.cider_scorer = CiderD(df=config["cider_path"])
 
         fiber_utils.set_metrics(self)
         self.current_tasks = list()
@@ -167,8 +179,8 @@ class FIBERTransformerSS(LightningModule):
     # with ITC the image-only / text-only passes also exercise vit_model.norm, the *_itc transforms / poolers and layer 11's
     # output LayerNorm
     def unused_parameter_names(self):
-        if self.config["loss_names"].get("caption_mle", 0) > 0:
-            return self._unused_caption()
+        if self.config["loss_names"].get("caption_mle", 0) > 0 or self.config["loss_names"].get("caption_cider", 0) > 0:
+            return self._unused_caption()                   # (compute_caption_cider reaches the parameters compute_caption_mle does)
         itc = self.config["loss_names"].get("itc", 0) > 0
         names = []
         for n, _ in self.named_parameters():
@@ -409,6 +421,8 @@ class FIBERTransformerSS(LightningModule):
             ret.update(objectives.compute_vqa(self, batch))
         if "caption_mle" in self.current_tasks:
             ret.update(objectives.compute_caption_mle(self, batch))
+        if "caption_cider" in self.current_tasks:
+            ret.update(objectives.compute_caption_cider(self, batch))
         return ret
 
     def training_step(self, batch, batch_idx):
@@ -434,7 +448,7 @@ class FIBERTransformerSS(LightningModule):
         ret = dict()
         if self.hparams.config["loss_names"].get("vqa", 0) > 0:
             ret.update(objectives.vqa_test_step(self, batch, output))
-        if self.hparams.config["loss_names"].get("caption_mle", 0) > 0:
+        if self.hparams.config["loss_names"].get("caption_mle", 0) > 0 or self.hparams.config["loss_names"].get("caption_cider", 0) > 0:
             ret.update(objectives.caption_test_step(self, batch, output))
         return ret
 
@@ -443,7 +457,7 @@ class FIBERTransformerSS(LightningModule):
         model_name = self.hparams.config["load_path"].split("/")[-1][:-5]
         if self.hparams.config["loss_names"].get("vqa", 0) > 0:
             objectives.vqa_test_wrapup(outs, model_name)
-        if self.hparams.config["loss_names"].get("caption_mle", 0) > 0:
+        if self.hparams.config["loss_names"].get("caption_mle", 0) > 0 or self.hparams.config["loss_names"].get("caption_cider", 0) > 0:
             objectives.caption_test_wrapup(outs, model_name)
         fiber_utils.epoch_wrapup(self)
 

@@ -1,6 +1,6 @@
 """Loss functions on the metric path: compute_mlm / compute_itm / compute_itm_hardneg / compute_itc / compute_vqa /
-compute_caption_mle + caption_test_step / caption_test_wrapup / init_weights (reference coarse_grained/fiber/modules/objectives.py:17-213,
-502-510, 560-710).  Same call signatures and return keys."""
+compute_caption_mle / compute_caption_cider + caption_test_step / caption_test_wrapup / init_weights (reference
+coarse_grained/fiber/modules/objectives.py:17-213, 502-510, 560-896).  Same call signatures and return keys."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -299,6 +299,126 @@ def compute_caption_mle(pl_module, batch):
     acc = getattr(pl_module, f"{phase}_caption_mle_accuracy")(ret["caption_mle_logits"], ret["caption_mle_labels"])
     pl_module.log(f"caption_mle/{phase}/loss", loss)
     pl_module.log(f"caption_mle/{phase}/accuracy", acc)
+    return ret
+
+
+def _wrap_sentence(s):
+    """objectives.py:720-728 (after VinVL): no trailing full stop, and an <eos> word, as the cached CIDEr document frequencies have it."""
+    r = s.strip()
+    if r.endswith("."):
+        r = r[:-1]
+    return r + " <eos>"
+
+
+def _head_logits_2d(pl_module, feats):
+    """mlm_score over [N, L, H] features as [N * L, V] rows, bf16 on the device (what the loss.hip kernels read)."""
+    logits = pl_module.mlm_score(feats)
+    flat = logits.reshape(-1, logits.shape[-1])
+    return flat.to(torch.bfloat16) if flat.is_cuda else flat
+
+
+def _caption_cider_scores(scorer, tok, text_ids, gt_txt, beam_size):
+    """objectives.py:830-856: CIDEr-D of every sampled caption (tokenizer.decode without the cls / sep / pad strings, _wrap_sentence) against
+    the references of its image (gt_txt[image], the same list for each of its beams): np.ndarray [bs * beam]."""
+    strip = (tok.cls_token, tok.sep_token, tok.pad_token)
+    res, gts = [], {}
+    for i, ids in enumerate(text_ids.tolist()):
+        s = tok.decode(ids)
+        for t in strip:
+            s = s.replace(t, "")
+        res.append({"image_id": i, "caption": [_wrap_sentence(s)]})
+        gts[i] = [_wrap_sentence(g) for g in gt_txt[i // beam_size]]
+    return scorer.compute_score(gts, res)[1]
+
+
+@torch.no_grad()
+def _caption_sample(pl_module, tok, image, image_embeds, beam_size, max_len):
+    """objectives.py:730-796: beam_size sampled continuations per image, [bs * beam, max_len] ids laid out image-major.  Step 0 runs on the
+    two-token prefix [cls, pad] (with the image tower unless image_embeds is handed in) and draws beam_size tokens per image with replacement;
+    every later step re-runs the causal text stack on the ids so far and draws one token per beam, ended beams are padded, and the loop stops
+    once all have ended.  The draws are ops.sample_rows (Gumbel-max on the dropout key stream) instead of softmax + torch.multinomial."""
+    bs, dev = image.size(0), image.device
+    pad, sep, mask_id = tok.pad_token_id, tok.sep_token_id, tok.mask_token_id
+    text_ids = torch.full((bs, max_len), pad, device=dev, dtype=torch.long)
+    text_ids[:, 0] = tok.cls_token_id
+    b = {"image": [image], "text_ids": text_ids[:, :2], "text_labels": None, "text_masks": text_ids[:, :2] != pad}
+    first = pl_module.infer_caption(b, mask_text=False, mask_image=False, image_embeds=image_embeds)
+    image_embeds = first["image_embeds"].repeat_interleave(beam_size, 0)
+    b["text_masks"] = None
+    end_seq = None
+    for i in range(max_len - 1):
+        b["text_ids"] = text_ids
+        infer = first if i == 0 else pl_module.infer_caption(b, mask_text=False, mask_image=False, image_embeds=image_embeds)
+        logits = _head_logits_2d(pl_module, infer["text_feats"][:, i:i + 1])
+        if i == 0:
+            tokens, _, end_seq = ops.sample_rows(logits, beam_size, mask_id, pad_id=pad, sep_id=sep)      # [bs, beam]
+            text_ids = text_ids.repeat_interleave(beam_size, 0)
+        else:
+            tokens, _, end_seq = ops.sample_rows(logits, 1, mask_id, ended=end_seq, pad_id=pad, sep_id=sep)
+        text_ids[:, i + 1] = tokens.reshape(-1)
+        end_seq = end_seq.reshape(-1)
+        if i > 0 and bool(end_seq.all()):
+            break
+    return text_ids.contiguous()
+
+
+def compute_caption_cider(pl_module, batch, beam_size=5, alpha=0.3, sampled_ids=None):
+    """objectives.py:712-896, self-critical sequence training on CIDEr-D: alpha * caption_loss + (1 - alpha) * rl_loss.  In training, beam_size
+    captions per image are sampled without gradient (_caption_sample), scored on the host against batch["gt_txt"] (modules/cider.py), and
+    re-scored WITH gradient: rl_loss = sum_seq mean_t log(p(token_t) + 1e-9) * (100 - 100 cider) / bs, the per-token term on ops.seq_logprob
+    (csrc/loss.hip) instead of softmax / + 1e-9 / log / gather over [bs * beam * L, V] fp32 tensors; a sequence without any non-pad label adds 0.
+    Outside training rl_loss = 0.  caption_loss is compute_caption_mle's term on the batch's own text.  The caller's batch is not modified.
+
+    `sampled_ids` (int64 [bs * beam, max_text_len]) pins the sampled captions for parity tests, like compute_itc's neg_override.
+    config["caption_cider_share_image"]: the image tower runs once with gradient (on the batch's images) and its tokens serve the sampling
+    (detached), the RL pass (repeated per beam: autograd sums the beams' gradients) and the MLE term, instead of the reference's 1 + beam + 1
+    tower samples per image.  Same function of the weights; in training mode each image then gets ONE DropPath draw instead of seven."""
+    cfg = pl_module.hparams.config
+    tok = pl_module.trainer.datamodule.dms[0].tokenizer
+    pad = tok.pad_token_id
+    share = bool(cfg.get("caption_cider_share_image", False))
+    caption_infer = pl_module.infer_caption(batch, mask_text=False, mask_image=False) if share else None
+    rl_loss = 0
+    if pl_module.training:
+        image = batch["image"][0]
+        bs = image.size(0)
+        shared = caption_infer["image_embeds"] if share else None
+        if sampled_ids is None:
+            text_ids = _caption_sample(pl_module, tok, image, shared.detach() if share else None, beam_size, cfg["max_text_len"])
+        else:
+            text_ids = sampled_ids.to(image.device).contiguous()
+        n = text_ids.size(0)
+        assert n == bs * beam_size, (n, bs, beam_size)
+        batch_rl = {"image": [None if share else image.repeat_interleave(beam_size, 0)], "text_ids": text_ids, "text_labels": None,
+                    "text_masks": text_ids != pad}
+        infer_rl = pl_module.infer_caption(batch_rl, mask_text=False, mask_image=False,
+                                           image_embeds=shared.repeat_interleave(beam_size, 0) if share else None)
+        rl_labels = torch.cat([text_ids[:, 1:], torch.full_like(text_ids[:, :1], pad)], 1)
+        lp = ops.seq_logprob(_head_logits_2d(pl_module, infer_rl["text_feats"]), rl_labels.reshape(-1), pad).view(n, -1)
+        rl_len = (rl_labels != pad).sum(-1).float()
+        seq_logp = lp.sum(-1) / (rl_len + 1e-9)                                     # [bs * beam]; 0 for a sequence of pads only
+
+        scores = _caption_cider_scores(pl_module.cider_scorer, tok, text_ids, batch["gt_txt"], beam_size)
+        weight = torch.as_tensor(100.0 - 100.0 * scores, dtype=torch.float32).to(seq_logp.device)
+        rl_loss = (seq_logp * weight).sum() / bs
+
+    if caption_infer is None:
+        caption_infer = pl_module.infer_caption(batch, mask_text=False, mask_image=False)
+    ids = caption_infer["text_ids"]
+    labels = torch.cat([ids[:, 1:], torch.full_like(ids[:, :1], pad)], 1)
+    labels = labels.masked_fill(labels == pad, -100)
+    if caption_infer["text_feats"].is_cuda:
+        caption_loss, logits, labels = _mlm_head(pl_module, caption_infer["text_feats"], labels)
+    else:                                                    # host tests: the same cross entropy in torch
+        logits = pl_module.mlm_score(caption_infer["text_feats"])
+        caption_loss = F.cross_entropy(logits.reshape(-1, logits.shape[-1]).float(), labels.reshape(-1), ignore_index=-100)
+    loss = alpha * caption_loss + (1 - alpha) * rl_loss
+    ret = {"caption_cider_loss": loss, "caption_cider_logits": logits, "caption_cider_labels": labels, "caption_cider_ids": ids}
+    phase = "train" if pl_module.training else "val"
+    loss = getattr(pl_module, f"{phase}_caption_cider_loss")(ret["caption_cider_loss"])
+    acc = getattr(pl_module, f"{phase}_caption_cider_accuracy")(ret["caption_cider_logits"], ret["caption_cider_labels"])
+    pl_module.log(f"caption_cider/{phase}/loss", loss)
+    pl_module.log(f"caption_cider/{phase}/accuracy", acc)
     return ret
 
 

@@ -455,6 +455,98 @@ def cross_entropy(logits, labels, ignore_index=-100):
     return _CrossEntropy.apply(logits, labels, ignore_index)
 
 
+class _SeqLogProb(torch.autograd.Function):
+    """lp[r] = log(softmax(x[r])[labels[r]] + 1e-9), 0 where labels[r] == pad_id (objectives.py:818-824), for bf16 logits [rows, V] on
+    csrc/loss.hip: one read of the logits forward, one read and one bf16 write backward, the per-row upstream gradient read on the device."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, pad_id):
+        rows, V = logits.shape
+        x = _c(logits)
+        lab = labels.contiguous()
+        lp = torch.empty(rows, dtype=torch.float32, device=x.device)
+        lse = torch.empty_like(lp)
+        lib.call("fiber_seqlogp_fwd_bf16", lib.ptr(x), lib.ptr(lab), lib.ptr(lp), lib.ptr(lse), rows, V, int(pad_id))
+        ctx.save_for_backward(x, lab, lse)
+        ctx.pad = int(pad_id)
+        return lp
+
+    @staticmethod
+    def backward(ctx, g):
+        x, lab, lse = ctx.saved_tensors
+        rowscale = g.float().contiguous()
+        dx = torch.empty_like(x)
+        lib.call("fiber_seqlogp_bwd_bf16", lib.ptr(x), lib.ptr(lab), lib.ptr(lse), lib.ptr(rowscale), lib.ptr(dx), x.shape[0], x.shape[1], ctx.pad)
+        _offer_labelled_rows(dx, lab, ctx.pad)               # pad rows are exact zeros: the decoder-bias column sum skips them
+        return dx, None, None
+
+
+def seq_logprob(logits, labels, pad_id):
+    """log(softmax(logits)[labels] + 1e-9) per row, 0 on rows whose label is pad_id: fp32 [rows].  bf16 device logits run on the HIP kernels;
+    CPU tensors on the same formulas in torch (host tests)."""
+    assert logits.dim() == 2 and labels.dtype == torch.int64 and labels.shape == logits.shape[:1]
+    if not logits.is_cuda:
+        x = logits.float()
+        pad = labels == pad_id
+        lab = labels.clamp(0, x.shape[1] - 1)
+        p = torch.exp(x.gather(1, lab[:, None])[:, 0] - torch.logsumexp(x, 1))
+        return torch.where(pad, torch.zeros_like(p), torch.log(p + 1e-9))
+    assert logits.dtype == BF16
+    return _SeqLogProb.apply(logits, labels, pad_id)
+
+
+def _hash_u32_torch(key, idx):
+    """hash_u32 of csrc/common.h on int64 tensors (two's-complement products are the uint64 ones; the shifts are made logical)."""
+    def i64(v):
+        v &= _M64
+        return v - (1 << 64) if v >= (1 << 63) else v
+
+    def shr(z, n):
+        return (z >> n) & ((1 << (64 - n)) - 1)
+    z = idx * i64(0x9E3779B97F4A7C15) + i64(int(key))
+    z = (z ^ shr(z, 30)) * i64(0xBF58476D1CE4E5B9)
+    z = (z ^ shr(z, 27)) * i64(0x94D049BB133111EB)
+    z = z ^ shr(z, 31)
+    return shr(z, 32)
+
+
+SAMPLE_FORCED_LOGIT = -10000.0
+
+
+def sample_rows(logits, K, forced_id, key=None, ended=None, pad_id=1, sep_id=2):
+    """K tokens per row of `logits` [rows, V] drawn with replacement from softmax(logits) (column forced_id read as -10000) by Gumbel-max
+    on a counter-based key: (tokens int64 [rows, K], logp fp32 [rows, K] = z_tok - logsumexp(z), ended uint8 [rows, K] = tok in {pad, sep}).
+    Replaces log_softmax / exp_ / torch.multinomial(replacement=True) / gather of objectives.py:756-766, 781-786.  Rows with ended[r] != 0
+    give pad_id / 0 / 1.  key=None draws a fresh key from the dropout key stream.  CPU tensors run the same formulas in torch (fp64)."""
+    assert logits.dim() == 2
+    rows, V = logits.shape
+    if key is None:
+        key = next_seed()
+    if ended is not None:
+        ended = ended.reshape(rows).to(torch.uint8).contiguous()
+    if not logits.is_cuda:
+        z = logits.double().clone()
+        if forced_id >= 0:
+            z[:, forced_id] = SAMPLE_FORCED_LOGIT
+        idx = ((torch.arange(rows)[:, None, None] * K + torch.arange(K)[None, :, None]) * V + torch.arange(V)[None, None, :])
+        u = (_hash_u32_torch(key, idx).double() + 0.5) * 2.0 ** -32
+        tokens = (z[:, None, :] - torch.log(-torch.log(u))).argmax(-1)
+        logp = (z.gather(1, tokens) - torch.logsumexp(z, 1, keepdim=True)).float()
+        if ended is not None:
+            e = ended.bool()[:, None]
+            tokens = torch.where(e, torch.full_like(tokens, pad_id), tokens)
+            logp = torch.where(e, torch.zeros_like(logp), logp)
+        return tokens, logp, ((tokens == pad_id) | (tokens == sep_id)).to(torch.uint8)
+    assert logits.dtype == BF16
+    x = _c(logits)
+    tokens = torch.empty(rows, K, dtype=torch.int64, device=x.device)
+    logp = torch.empty(rows, K, dtype=torch.float32, device=x.device)
+    ended_out = torch.empty(rows, K, dtype=torch.uint8, device=x.device)
+    lib.call("fiber_sample_rows_bf16", lib.ptr(x), lib.ptr(ended), lib.ptr(tokens), lib.ptr(logp), lib.ptr(ended_out), rows, V, int(K),
+             int(forced_id), int(key) & _M64, seed_base_ptr(), int(pad_id), int(sep_id))
+    return tokens, logp, ended_out
+
+
 # Call sites of the library GEMM (file names), recorded when a test switches it on: the library is allowed for the caller-side heads
 # (SURVEY.md 8a-15) and the ITC similarity matrices only -- tests/test_hip_modules.py::test_library_gemm_only_from_heads.
 lib_gemm_sites = None

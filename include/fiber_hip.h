@@ -211,6 +211,23 @@ int fiber_colsum_labelled_slabs(int rows);
 int fiber_colsum_labelled_bf16(const void* x, const long long* labels, float* out, float* workspace, int rows, int V,
                                long long ignore_index, fiber_stream_t stream);
 
+/* CIDEr-optimised caption training (caller side: compute_caption_cider, objectives.py:712-896), bf16 logits [rows, V] contiguous, V > 16.
+ * fiber_sample_rows_bf16 = objectives.py:756-766 / 781-786 (log_softmax, exp_, torch.multinomial(probs, K, replacement=True), gather): K
+ * Gumbel-max draws per row in one read of the row.  tokens[r, k] (int64) = arg max_j (z_j - log(-log(u))), smallest index among equal maxima,
+ * u = (hash_u32(seed + *seed_base, (r K + k) V + j) + 0.5) 2^-32, z = the row with column forced_id read as -10000 (:757; forced_id < 0: none);
+ * logp[r, k] (fp32) = z_tok - logsumexp(z); ended_out[r, k] (uint8) = tok in {pad_id, sep_id}.  ended (nullable, uint8 [rows]): such a row is not
+ * read, its tokens are pad_id, its logp 0, its ended_out 1 (:792).  1 <= K <= 8. */
+int fiber_sample_rows_bf16(const void* logits, const unsigned char* ended, long long* tokens, float* logp, unsigned char* ended_out, int rows,
+                           int V, int K, int forced_id, uint64_t seed, const uint64_t* seed_base, long long pad_id, long long sep_id,
+                           fiber_stream_t stream);
+/* objectives.py:818-827 and its autograd (softmax, + 1e-9, log, gather, zero on pad): lp[r] = log(exp(x[r, l] - lse[r]) + 1e-9), l = labels[r];
+ * lp = lse = 0 where l == pad_id.  bwd: dlogits[r, j] = rowscale[r] (p_l / (p_l + 1e-9)) ([j == l] - p_j), p = exp(x - lse), rowscale fp32 [rows]
+ * in device memory (d loss / d lp[r]); exact zero rows where l == pad_id, so fiber_colsum_labelled_bf16(ignore_index = pad_id) sums the rest. */
+int fiber_seqlogp_fwd_bf16(const void* logits, const long long* labels, float* lp, float* lse, int rows, int V, long long pad_id,
+                           fiber_stream_t stream);
+int fiber_seqlogp_bwd_bf16(const void* logits, const long long* labels, const float* lse, const float* rowscale, void* dlogits, int rows,
+                           int V, long long pad_id, fiber_stream_t stream);
+
 /* AdamW step of one parameter group in one launch (caller side of the path: transformers 4.6.0 AdamW(correct_bias=True) as
  * configured by fiber_utils.set_schedule, fiber_utils.py:248-252), also refreshing the bf16 working copies of the weights.
  * table: int64[n*5] device pointers (param fp32, grad fp32, exp_avg, exp_avg_sq, bf16 copy or 0); numel: int64[n];
