@@ -12,7 +12,7 @@
 //  * the M reduction is split INSIDE the launch: workgroup = (output tile, M range); every split writes its fp32 tile into
 //    its own slab and one small fold kernel sums the slabs (no atomics, deterministic, no [S,N,K] batched-GEMM temporary
 //    in front of a library reduction);
-//  * K tiles are 64 rows of dY and X, brought HBM -> LDS by global_load_lds_dwordx4 exactly as they lie in memory
+//  * K tiles are 32 rows of dY and X, brought HBM -> LDS by global_load_lds_dwordx4 exactly as they lie in memory
 //    (row-major, 512-byte rows: fully coalesced), and BOTH MFMA operands are read transposed out of those row-major images
 //    with ds_read_b64_tr_b16 (two reads = the 8 consecutive-m values a lane needs for its column) -- no transposed copy of
 //    dY or X is ever made, in HBM or in LDS;
@@ -20,9 +20,12 @@
 //    rows would sit on the same banks, so 32-byte chunk c of row r is stored at chunk c ^ ((r & 3) << 1) -- applied on the
 //    per-lane SOURCE address of the DMA (which writes lane-linear) and on the read address.  The eight 32-byte pieces of a
 //    half-wave then tile the 256-byte bank row exactly;
-//  * 256x256 output tile, 8 waves as 2 x 4 (128 x 64 per wave = 4 x 2 MFMA 32x32x16 tiles), two 64-KB stages, and the same
-//    two-wave-group schedule as the forward GEMM (gemm.hip): the groups run the K loop half a sub-tile apart so that on every
-//    SIMD one wave feeds the matrix pipe while its partner reads fragments.  A 128x128 / 4-wave instance covers the narrow
+//  * 256x256 output tile, 8 waves as 2 x 4 (128 x 64 per wave = 4 x 2 MFMA 32x32x16 tiles), a ring of five 32-KB stages (the whole
+//    LDS: four K tiles requested ahead, every wait a counted vmcnt) under the two-wave-group schedule of the forward GEMM (gemm.hip):
+//    the groups run the K loop one phase apart so that on every SIMD one wave feeds the matrix pipe while its partner reads
+//    fragments and requests a tile.  The host's plan still counts 64-row units, so every split adds the same products in the same
+//    order as the two-stage 64-row loop this replaced (profiles/tn_ring.md: -6.4 % of the kernel's time per step; what decided it
+//    was the instruction count of the steady-state loop, not the depth alone).  A 128x128 / 4-wave instance covers the narrow
 //    weights (stage-0 / stage-1 linears, patch embedding, test configurations);
 //  * the bias gradient: in the workgroups of the first K-column tile every wave adds ONE of its dY fragment tiles up with
 //    v_dot2_f32_bf16 against (1, 1) -- four VALU issues per MFMA k-step behind a scalar branch -- so no separate pass ever streams dY
@@ -31,6 +34,8 @@
 //    s_b in {0, 1/keep}.  Instead of a pass that writes s_b dY, the kernel skips the K tiles of dropped samples (row_mask)
 //    and multiplies the result by 1/keep (scale): dW = (1/keep) sum over kept samples of dY^T X.
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -67,9 +72,15 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* p, int hi_off) {
   return __builtin_bit_cast(bf16x8, o);
 }
 
+// lds_dma16 (common.h) with the LDS address of the wave's 1 KB given as a number: no generic -> LDS pointer conversion (a null test and a select
+// per request) in a loop that issues four of them per 32-row tile
+__device__ __forceinline__ void lds_dma16_at(const void* base, unsigned lane_byte_off, unsigned lds_addr) {
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(lane_byte_off), "s"(base) : "memory");
+}
+
 // TS: output tile edge (256: 8 waves, 128: 4 waves).  BKM: rows of dY / X per K tile.  NS: LDS stages.
-// STAG (TS = 256, BKM = 64, NS = 2): two wave groups half a sub-tile apart, one workgroup per CU.
-// ring (TS = 128, BKM = 32, NS = 4): the narrow weights are pure streaming problems (2 x 256 B per row of M against 128 x 128
+// STAG (TS = 256, BKM = 32, NS = 5): two wave groups one phase apart over the ring, one workgroup per CU (see the loop).
+// plain ring (TS = 128, BKM = 32, NS = 4): the narrow weights are pure streaming problems (2 x 256 B per row of M against 128 x 128
 // MACs), so what matters is bytes in flight: three K tiles per workgroup stay requested across the (raw) barrier behind a
 // COUNTED vmcnt, 64 KB of LDS per workgroup so that two workgroups share a CU and cover each other's fragment reads.
 template <int TS, int BKM, int NS, bool STAG>
@@ -85,8 +96,8 @@ __global__ __launch_bounds__(TS * 2) void gemm_tn_kernel(TnArgs a) {
   constexpr int NDI = BKM / RPI / NW;           // DMA instructions per wave, operand and K tile
   constexpr int OPB = BKM * RB;                 // bytes per operand per stage
   constexpr int STAGEB = 2 * OPB;
-  constexpr int NSUB = BKM / 32;                // 32-row sub-tiles (two MFMA k-steps each) per K tile
-  static_assert(NDI * RPI * NW == BKM && (!STAG || (NW == 8 && BKM == 64 && NS == 2)) && (BKM == 32 || BKM == 64), "geometry");
+  constexpr int TPU = (TS == 256 ? 64 : 32) / BKM;   // K tiles per unit of the host's plan (tn_plan counts 64 rows at TS = 256, 32 at TS = 128)
+  static_assert(NDI * RPI * NW == BKM && BKM == 32 && NS * STAGEB <= 160 * 1024 && (!STAG || (NW == 8 && NS >= 3 && NS <= 5)), "geometry");
   __shared__ __attribute__((aligned(16))) char smem[NS * STAGEB];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -101,8 +112,8 @@ __global__ __launch_bounds__(TS * 2) void gemm_tn_kernel(TnArgs a) {
   const int s = bid / tiles, tile = bid - s * tiles;
   const int tn = tile / a.tiles_k, tk = tile - tn * a.tiles_k;
   const int n0 = tn * TS, k0 = tk * TS;
-  const int kt0 = s * a.kt_per_split;
-  const int nk = min(a.kt_per_split, a.nk_total - kt0);
+  const int kt0 = s * a.kt_per_split * TPU;
+  const int nk = min(a.kt_per_split, a.nk_total - s * a.kt_per_split) * TPU;
   const int m0 = kt0 * BKM;
 
   // ---- DMA addressing: instruction p of this wave covers tile rows (p*NW + wave)*RPI .. +RPI-1, lane -> (row, 16-B chunk).
@@ -117,18 +128,18 @@ __global__ __launch_bounds__(TS * 2) void gemm_tn_kernel(TnArgs a) {
     aoff[p] = (unsigned)(r * a.lda + min(n0 + gc * 8, a.N - 8)) * 2u;
     boff[p] = (unsigned)(r * a.ldb + min(k0 + gc * 8, a.K - 8)) * 2u;
   }
-  auto dma = [&](int kt) {
-    char* st = smem + (kt % NS) * STAGEB;
+  auto dma = [&](int kt, int stage) {
+    char* st = smem + stage * STAGEB;
     const int mt = m0 + kt * BKM;                                 // first row of this K tile (scalar)
     const bf16* abase = a.A + (size_t)mt * a.lda;
-    const bf16* bbase = a.B + (size_t)mt * a.ldb;
+    const bf16* bbase = a.B + (size_t)min(mt, a.M - 1) * a.ldb;   // (TPU = 2: the second half of the last unit may lie wholly past M)
     if (mt + BKM <= a.M) {
 #pragma unroll
       for (int p = 0; p < NDI; ++p) {
         lds_dma16(abase, aoff[p], st + (p * NW + wave) * RPI * RB);
         lds_dma16(bbase, boff[p], st + OPB + (p * NW + wave) * RPI * RB);
       }
-    } else {                                                      // the very last K tile of the problem: rows past M
+    } else {                                                      // the very last unit of the problem: rows past M
 #pragma unroll
       for (int p = 0; p < NDI; ++p) {
         const int r = (p * NW + wave) * RPI + drow;
@@ -168,8 +179,8 @@ __global__ __launch_bounds__(TS * 2) void gemm_tn_kernel(TnArgs a) {
   // K tile kt belongs to sample (m0 + kt*BKM) / rows_per_sample; its MFMAs are skipped when that sample was dropped.  The factors of the
   // next 64 samples are fetched with ONE vector load and kept as a ballot in an SGPR pair: a load in front of every K tile's branch cost
   // the masked form 18 % of its rate (and any vector load inside the loop makes hipcc wait with vmcnt(0), which also drains the LDS-DMA
-  // requests of the next K tile -- the compiler does not count what inline asm issued).  The reload every 64 samples sits at the top of
-  // an iteration, where no DMA is outstanding.
+  // requests of the next K tiles -- the compiler does not count what inline asm issued).  The reload every 64 samples sits at the top of
+  // an iteration and empties the ring once per 64 samples of one split.
   const int tps = a.row_mask ? a.rows_per_sample / BKM : 1;       // K tiles per sample
   const int nsamp = a.row_mask ? (a.M + a.rows_per_sample - 1) / a.rows_per_sample : 1;
   int samp0 = a.row_mask ? (m0 / BKM) / tps : 0, srem = a.row_mask ? (m0 / BKM) % tps : 0, sbit = 0;
@@ -186,8 +197,8 @@ __global__ __launch_bounds__(TS * 2) void gemm_tn_kernel(TnArgs a) {
   reload_mask();
 
   bf16x8 fa[2][TA], fb[2][TB];
-  auto load_phase = [&](int kt, int sub) {
-    const char* st = smem + (kt % NS) * STAGEB + sub * 32 * RB;
+  auto load_phase = [&](int stage) {                               // one K tile = two MFMA k-steps: 24 | 16 transposed reads
+    const char* st = smem + stage * STAGEB;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
@@ -220,33 +231,78 @@ __global__ __launch_bounds__(TS * 2) void gemm_tn_kernel(TnArgs a) {
   const unsigned long long pc0 = __builtin_amdgcn_s_memtime(), pr0 = __builtin_amdgcn_s_memrealtime();
 #endif
   if constexpr (STAG) {
-    auto phase_barrier = [&](bool landed) {
-      if (landed) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    // Two wave groups (waves 0-3 and 4-7: the two waves of every SIMD), one phase apart, over NS stages of 32 rows.  Tile j is one load phase
+    // (24 transposed reads) and one math phase (16 MFMAs); the load phase of tile j requests tile j + NS - 1 (4 DMA instructions per wave), so
+    // NS - 1 tiles are in flight per CU and each group's requests go out under the partner group's math phase.
+    // Barriers are numbered over the workgroup: barrier 0 ends the prologue; phase p of group 0 (p = 2j: load of tile j, 2j + 1: its math) ends
+    // at barrier p + 1, phase p of group 1 at barrier p + 2 (group 1 passes one barrier more before the loop, group 0 one more behind it).
+    //  RAW: group 0 reads tile j after barrier 2j, group 1 after barrier 2j + 1.  Every wave arrives at barrier 2j -- group 0 from the math
+    //       phase of tile j - 1, group 1 from its load phase -- having requested the tiles up to min(j + NS - 2, nk - 1) and having waited with
+    //       vmcnt(4 * tiles requested after tile j): loads return in order, so its own share of tile j (and of every older tile) has landed.
+    //  WAR: tile j + NS - 1 overwrites the stage of tile j - 1.  Group 0 requests it after barrier 2j, group 1 after barrier 2j + 1.  The last
+    //       reads of tile j - 1 are those of group 1's load phase, which ends at barrier 2j behind lgkmcnt(0); group 0's ended at barrier 2j - 1.
+    // Nothing in the loop waits with vmcnt(0) while newer tiles are requested, except the 64-sample mask reload (a vector load: once per 64
+    // samples of ONE split; the splits of the training shapes hold 1-16 samples, so it never runs there).
+    static_assert(NDI == 2, "counted vmcnt below: 4 DMA instructions per wave and K tile");
+    auto phase_barrier = [&](int newer) {                  // newer < 0: fragment reads only; else: at most `newer` younger K tiles still in flight
+      if (newer < 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      else if (newer >= 3) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
+      else if (newer == 2) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+      else if (newer == 1) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
     };
-    dma(0);
-    phase_barrier(true);
-    if (wa == 1) phase_barrier(false);                   // group 1 runs one phase behind (see gemm.hip, wide kernel)
-    for (int kt = 0; kt < nk; ++kt) {
-      const bool inc = kept_then_advance();
-      load_phase(kt, 0);
-      if (kt + 1 < nk) dma(kt + 1);
-      phase_barrier(false);
-      if (inc) math_phase();
-      phase_barrier(false);
-      load_phase(kt, 1);
-      phase_barrier(wa == 1);
-      if (inc) math_phase();
-      phase_barrier(wa == 0);
-    }
-    if (wa == 0) phase_barrier(false);
+    for (int pre = 0; pre < NS - 1 && pre < nk; ++pre) dma(pre, pre);
+    phase_barrier(min(nk - 1, NS - 2));                    // barrier 0: tile 0 resident
+    // The first n_steady tiles request a whole tile inside M: constant waits, running source pointers, one copy of the loop per group.
+    const int n_steady = max(min(nk, (a.M - m0) / BKM) - (NS - 1), 0);
+    const bool masked = a.row_mask != nullptr;
+    auto run = [&](auto G) __attribute__((always_inline)) {
+      constexpr int g = decltype(G)::value;
+      if (g == 1) phase_barrier(-1);
+      int rs = 0, ws = NS - 1;                             // stage of tile j, stage of tile j + NS - 1 (= that of tile j - 1)
+      const char* pa = reinterpret_cast<const char*>(a.A + (size_t)(m0 + (NS - 1) * BKM) * a.lda);
+      const char* pb = reinterpret_cast<const char*>(a.B + (size_t)(m0 + (NS - 1) * BKM) * a.ldb);
+      const size_t sa = (size_t)BKM * a.lda * 2, sb = (size_t)BKM * a.ldb * 2;
+      const unsigned lbase = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem + wave * (RPI * RB);
+      int kt = 0;
+      for (; kt < n_steady; ++kt) {
+        const bool inc = masked ? kept_then_advance() : true;
+        load_phase(rs);
+        const unsigned st = lbase + ws * STAGEB;
+#pragma unroll
+        for (int p = 0; p < NDI; ++p) {
+          lds_dma16_at(pa, aoff[p], st + p * NW * RPI * RB);
+          lds_dma16_at(pb, boff[p], st + OPB + p * NW * RPI * RB);
+        }
+        pa += sa; pb += sb;
+        phase_barrier(g == 1 ? NS - 2 : -1);
+        if (inc) math_phase();
+        phase_barrier(g == 0 ? NS - 2 : -1);
+        ws = rs;
+        rs = rs + 1 == NS ? 0 : rs + 1;
+      }
+      for (; kt < nk; ++kt) {                              // the last NS - 1 tiles and the unit that reaches past M
+        const bool inc = masked ? kept_then_advance() : true;
+        load_phase(rs);
+        if (kt + NS - 1 < nk) dma(kt + NS - 1, ws);
+        const int newer = max(min(nk - 2 - kt, NS - 2), 0);  // K tiles requested after tile kt + 1
+        phase_barrier(g == 1 ? newer : -1);
+        if (inc) math_phase();
+        phase_barrier(g == 0 ? newer : -1);
+        ws = rs;
+        rs = rs + 1 == NS ? 0 : rs + 1;
+      }
+      if (g == 0) phase_barrier(-1);
+    };
+    if (wa == 0) run(std::integral_constant<int, 0>{});
+    else run(std::integral_constant<int, 1>{});
   } else {
     static_assert(STAG || (NS == 4 && NDI == 2), "counted vmcnt below: 3 tiles x 4 DMA instructions per wave in flight");
-    for (int pre = 0; pre < NS - 1 && pre < nk; ++pre) dma(pre);
+    for (int pre = 0; pre < NS - 1 && pre < nk; ++pre) dma(pre, pre);
     for (int kt = 0; kt < nk; ++kt) {
       const bool inc = kept_then_advance();
       const int newer = min(nk - 1 - kt, NS - 2);          // K tiles requested after tile kt (2 NDI instructions per wave each)
@@ -257,13 +313,10 @@ __global__ __launch_bounds__(TS * 2) void gemm_tn_kernel(TnArgs a) {
       __builtin_amdgcn_s_barrier();                       // tile kt resident for every wave; tile kt-1 fully consumed
       asm volatile("" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
-      if (kt + NS - 1 < nk) dma(kt + NS - 1);             // into the stage tile kt-1 just vacated
+      if (kt + NS - 1 < nk) dma(kt + NS - 1, (kt + NS - 1) % NS);   // into the stage tile kt-1 just vacated
       if (inc) {
-#pragma unroll
-        for (int sub = 0; sub < NSUB; ++sub) {
-          load_phase(kt, sub);
-          math_phase();
-        }
+        load_phase(kt % NS);
+        math_phase();
       }
     }
   }
@@ -381,7 +434,7 @@ TnPlan tn_plan(int M, int N, int K) {
   TnPlan p;
   p.ts = (N >= 192 && K >= 192) ? 256 : 128;
   if (force_ts == 128 || force_ts == 256) p.ts = force_ts;
-  p.bkm = p.ts == 256 ? 64 : 32;
+  p.bkm = p.ts == 256 ? 64 : 32;                           // rows per plan unit (the 256 kernel walks a unit as two 32-row K tiles)
   p.tiles_n = cdiv(N, p.ts);
   p.tiles_k = cdiv(K, p.ts);
   p.nk_total = cdiv(M, p.bkm);
@@ -437,7 +490,7 @@ static int tn_launch(const void* dY, const void* X, float* dW, float* dbias, flo
   a.S = p.S; a.tiles_n = p.tiles_n; a.tiles_k = p.tiles_k; a.kt_per_split = p.kt_per_split; a.nk_total = p.nk_total;
   a.row_mask = row_mask; a.rows_per_sample = rows_per_sample; a.scale = scale;
   const unsigned grid = (unsigned)(p.tiles_n * p.tiles_k * p.S);
-  if (p.ts == 256) hipLaunchKernelGGL((gemm_tn_kernel<256, 64, 2, true>), dim3(grid), dim3(512), 0, stream, a);
+  if (p.ts == 256) hipLaunchKernelGGL((gemm_tn_kernel<256, 32, 5, true>), dim3(grid), dim3(512), 0, stream, a);
   else hipLaunchKernelGGL((gemm_tn_kernel<128, 32, 4, false>), dim3(grid), dim3(256), 0, stream, a);
   FIBER_CHECK_LAUNCH();
   if (via_ws) {

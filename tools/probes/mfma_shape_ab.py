@@ -42,7 +42,7 @@ def table_rows(path):
 
 
 def served(entry, M, N, K):
-    """Does the call reach gemm_nt_q8_kernel / gemm_tn_kernel<256, 64, 2, true>?  (gemm_plan / tn_plan of the csrc files, default environment;
+    """Does the call reach gemm_nt_q8_kernel / the 256-tile gemm_tn_kernel?  (gemm_plan / tn_plan of the csrc files, default environment;
     every NT kind of the table is an epilogue q8 is built for.)"""
     if entry == "gemm_nt":
         tiles = -(-M // 256) * -(-N // 256)
