@@ -1,0 +1,401 @@
+"""Box average precision of the fine-grained model by the LVIS protocol, on the device.
+
+Mirrors fine_grained/maskrcnn_benchmark/data/datasets/evaluation/lvis/lvis_eval.py: Params (:52-76), LVISResults.limit_dets_per_image
+(:137-148), LVISEval._prepare / compute_iou / evaluate_img / accumulate / _summarize / summarize (:201-586), LvisEvaluator (:637-750) and
+LvisEvaluatorFixedAP (:767-872).
+
+The reference copies every prediction to the host and walks images x categories x four area ranges x ten IoU thresholds in Python.  Here
+the Detections stay where they are:
+  pack_detection_targets  the batch's annotations as fixed-shape tensors (DetectionTargets)
+  evaluator.update        ONE launch of ops.ap_match (csrc/apeval.hip, one wave per (image, area range, threshold)): per detection slot a
+                          64-bit match word, a 64-bit ignore word (bit a * T + t) and a valid byte; num_gt is added to.  No synchronisation.
+  evaluator.tables        the records of all updates ranked by two stable sorts (score, then category), ONE launch of ops.ap_accumulate
+  evaluator.summarize     the one device-to-host copy (the two tables), then the reference's means with numpy
+On CPU tensors the same bookkeeping runs with the two launches replaced by numpy (_match_host, _accumulate_host), which the `not gpu`
+tests hold against fixtures the reference's own LVISEval produced.
+
+Why matching is per batch and truncation post hoc: the greedy rule is order-dependent only among the detections of one (image, category),
+and LvisEvaluatorFixedAP's per-category top k is a prefix of that category's score order.  A record inside the prefix has every
+higher-scoring detection of its image and category inside it too, so its match is the one the reference finds after truncating.  The
+records are therefore matched when they arrive and cut to each category's k best at the end; the k best are counted before the federated
+filter drops any, as the reference counts them.
+
+Deviations from the reference:
+  * two detections of one category with EQUAL scores are ranked in arrival order (update order, then image, then slot); the reference's
+    order then depends on its sorted image ids.
+  * a ground-truth box of zero or negative extent and a repeated image id are refused; the reference's 0 / 0 would match as NaN, and its
+    np.unique keeps one of the repeats.
+  * rec_thrs must ascend (the reference's searchsorted assumes it).
+
+This is the LVIS protocol.  COCO ground truth can be evaluated with crowd boxes packed as ignore = 1 and every category in every image's
+negative list, but that is the LVIS protocol on COCO data, not COCOeval: the COCO API's crowd rule (IoU over the detection's area,
+re-matchable crowd regions) is not reproduced.  Out of scope as well: segmentation and keypoint IoU, LvisDumper, test-time augmentation
+and the dataset readers.
+"""
+import numpy as np
+import torch
+
+from .. import ops
+
+MAX_GT = 4096                                                # = ops.ap_max_gt(); the host path keeps the same bound
+FREQUENCIES = ("r", "c", "f")
+AREA_LABELS = ("all", "small", "medium", "large")
+
+
+def default_params():
+    """Params (:52-76): (iou_thrs [10], rec_thrs [101], area_rng [4, 2]) as numpy computes them"""
+    iou_thrs = np.linspace(0.5, 0.95, int(np.round((0.95 - 0.5) / 0.05)) + 1, endpoint=True)
+    rec_thrs = np.linspace(0.0, 1.00, int(np.round((1.00 - 0.0) / 0.01)) + 1, endpoint=True)
+    area_rng = np.array([[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]], dtype=np.float64)
+    return iou_thrs, rec_thrs, area_rng
+
+
+class DetectionTargets:
+    """Ground truth of one batch: gt fp64 [B, G, 4] (xywh, original frame), area fp64 [B, G] (the annotation's own field), category int32
+    [B, G] (index into the sorted category ids), ignore uint8 [B, G], gt_count int32 [B], neg_mask / nel_mask int64 [B, ceil(C / 64)]
+    (the bits of a uint64: bit c of word c // 64 = category c is in the image's negative / not-exhaustive list); image_ids (host list of
+    B) and category_ids (host list of C) travel along."""
+
+    def __init__(self, gt, area, category, ignore, gt_count, neg_mask, nel_mask, image_ids, category_ids):
+        self.gt, self.area, self.category, self.ignore, self.gt_count = gt, area, category, ignore, gt_count
+        self.neg_mask, self.nel_mask = neg_mask, nel_mask
+        self.image_ids, self.category_ids = list(image_ids), list(category_ids)
+
+    def to(self, device):
+        return DetectionTargets(*(t.to(device) for t in (self.gt, self.area, self.category, self.ignore, self.gt_count, self.neg_mask,
+                                                         self.nel_mask)), self.image_ids, self.category_ids)
+
+
+def _category_ids(categories):
+    ids = [c["id"] for c in categories]
+    if not ids or ids != sorted(set(ids)):
+        raise ValueError("categories: a non-empty list of {'id', 'frequency'} in ascending id order without repeats")
+    for c in categories:
+        if c["frequency"] not in FREQUENCIES:
+            raise ValueError(f"categories: frequency {c['frequency']!r} of category {c['id']} is none of {FREQUENCIES}")
+    return ids
+
+
+def _mask_words(ids, index, words, what, image_id):
+    out = np.zeros(words, dtype=np.uint64)
+    for i in ids:
+        if i not in index:
+            raise ValueError(f"pack_detection_targets: image {image_id}: {what} names category {i}, which is not in categories")
+        out[index[i] >> 6] |= np.uint64(1) << np.uint64(index[i] & 63)
+    return out.view(np.int64)
+
+
+def pack_detection_targets(samples, categories, num_boxes=None):
+    """samples: one dict per image with "image_id", "annotations" (the dataset's own: "bbox" xywh, "area", "category_id", optional
+    "ignore"), "neg_category_ids" and "not_exhaustive_category_ids".  categories: [{"id", "frequency"}] in ascending id order.
+    num_boxes fixes G (default: the batch's maximum, at least 1).  -> DetectionTargets on the host."""
+    ids = _category_ids(categories)
+    index = {c: i for i, c in enumerate(ids)}
+    B, W = len(samples), (len(ids) + 63) // 64
+    most = max([len(s["annotations"]) for s in samples] + [0])
+    G = max(most, 1)
+    if num_boxes is not None:
+        if num_boxes < most:
+            raise ValueError(f"pack_detection_targets: an image has {most} annotations, more than num_boxes = {num_boxes}")
+        G = max(int(num_boxes), 1)
+    if G > MAX_GT:
+        raise ValueError(f"pack_detection_targets: {G} ground-truth boxes per image exceed the matching kernel's capacity of {MAX_GT}")
+    gt, area = np.zeros((B, G, 4), np.float64), np.zeros((B, G), np.float64)
+    cat, ign, cnt = np.zeros((B, G), np.int32), np.zeros((B, G), np.uint8), np.zeros((B,), np.int32)
+    neg, nel = np.zeros((B, W), np.int64), np.zeros((B, W), np.int64)
+    for b, s in enumerate(samples):
+        for g, ann in enumerate(s["annotations"]):
+            box = np.asarray(ann["bbox"], dtype=np.float64).reshape(4)
+            if not np.isfinite(box).all() or not np.isfinite(ann["area"]):
+                raise ValueError(f"pack_detection_targets: image {s['image_id']} annotation {g}: non-finite box or area")
+            if box[2] <= 0 or box[3] <= 0:
+                raise ValueError(f"pack_detection_targets: image {s['image_id']} annotation {g}: ground-truth box of no extent")
+            if ann["category_id"] not in index:
+                raise ValueError(f"pack_detection_targets: image {s['image_id']} annotation {g}: category {ann['category_id']} not in categories")
+            gt[b, g], area[b, g], cat[b, g], ign[b, g] = box, ann["area"], index[ann["category_id"]], 1 if ann.get("ignore", 0) else 0
+        cnt[b] = len(s["annotations"])
+        neg[b] = _mask_words(s.get("neg_category_ids", ()), index, W, "neg_category_ids", s["image_id"])
+        nel[b] = _mask_words(s.get("not_exhaustive_category_ids", ()), index, W, "not_exhaustive_category_ids", s["image_id"])
+    return DetectionTargets(*(torch.from_numpy(x) for x in (gt, area, cat, ign, cnt, neg, nel)), [s["image_id"] for s in samples], ids)
+
+
+def _match_host(boxes, labels, count, t, iou_thrs, area_rng, num_gt, max_dets):
+    """ops.ap_match on CPU tensors, in numpy: one fp64 rounding per operation in the order the kernel's header states.
+    num_gt is accumulated in place.  -> (match, ignore, valid)"""
+    bx = boxes.detach().float().numpy()
+    lab, cnt = labels.numpy(), count.numpy()
+    gt, garea, gcat, gign, gcnt = t.gt.numpy(), t.area.numpy(), t.category.numpy(), t.ignore.numpy(), t.gt_count.numpy()
+    neg, nel = t.neg_mask.numpy().view(np.uint64), t.nel_mask.numpy().view(np.uint64)
+    thrs, rng, ngt = iou_thrs.numpy(), area_rng.numpy(), num_gt.numpy()
+    B, D = lab.shape
+    C, A = ngt.shape
+    T = len(thrs)
+    match, ignore, valid = np.zeros((B, D), np.uint64), np.zeros((B, D), np.uint64), np.zeros((B, D), np.uint8)
+    w = (bx[:, :, 2] - bx[:, :, 0]).astype(np.float64)       # fp32 differences, then double
+    h = (bx[:, :, 3] - bx[:, :, 1]).astype(np.float64)
+    x, y = bx[:, :, 0].astype(np.float64), bx[:, :, 1].astype(np.float64)
+    darea = w * h
+    floor = np.minimum(thrs, 1 - 1e-10)
+
+    def listed(words, b, c):
+        return bool((words[b, c >> 6] >> np.uint64(c & 63)) & np.uint64(1))
+    for b in range(B):
+        n = min(max(int(cnt[b]), 0), D)
+        if max_dets >= 0:
+            n = min(n, max_dets)
+        m = min(max(int(gcnt[b]), 0), gt.shape[1])
+        cats, g, ga, gi = gcat[b, :m], gt[b, :m], garea[b, :m], gign[b, :m] != 0
+        for a in range(A):
+            out = gi | (ga < rng[a, 0]) | (ga > rng[a, 1])
+            np.add.at(ngt[:, a], cats[~out], 1)
+        for c in np.unique(lab[b, :n] - 1):
+            c = int(c)
+            if not 0 <= c < C:
+                continue
+            mine = np.nonzero(cats == c)[0]
+            if len(mine) == 0 and not listed(neg, b, c):
+                continue
+            dets = np.nonzero(lab[b, :n] - 1 == c)[0]
+            valid[b, dets] = 1
+            lazy = listed(nel, b, c)
+            iw = (np.minimum((x[b, dets] + w[b, dets])[:, None], g[mine, 0] + g[mine, 2]) - np.maximum(x[b, dets][:, None], g[mine, 0])).clip(min=0)
+            ih = (np.minimum((y[b, dets] + h[b, dets])[:, None], g[mine, 1] + g[mine, 3]) - np.maximum(y[b, dets][:, None], g[mine, 1])).clip(min=0)
+            inter = iw * ih
+            iou = inter / (darea[b, dets][:, None] + g[mine, 2] * g[mine, 3] - inter)
+            for a in range(A):
+                lo, hi = rng[a]
+                out = gi[mine] | (ga[mine] < lo) | (ga[mine] > hi)
+                small = (darea[b, dets] < lo) | (darea[b, dets] > hi) | lazy
+                for ti in range(T):
+                    bit = np.uint64(1) << np.uint64(a * T + ti)
+                    free = np.ones(len(mine), bool)
+                    for k, d in enumerate(dets):
+                        ok = free & (iou[k] >= floor[ti])
+                        pick = ok & ~out if (ok & ~out).any() else ok
+                        if pick.any():
+                            best = iou[k][pick].max()
+                            j = np.nonzero(pick & (iou[k] == best))[0][-1]      # the later one on an exact tie
+                            free[j] = False
+                            match[b, d] |= bit
+                            if out[j]:
+                                ignore[b, d] |= bit
+                        elif small[k]:
+                            ignore[b, d] |= bit
+    return torch.from_numpy(match.view(np.int64)), torch.from_numpy(ignore.view(np.int64)), torch.from_numpy(valid)
+
+
+def _accumulate_host(match, ignore, seg_ptr, num_gt, rec_thrs, T):
+    """ops.ap_accumulate on CPU tensors, in numpy"""
+    m, ig, seg, ngt, thr = match.numpy().view(np.uint64), ignore.numpy().view(np.uint64), seg_ptr.numpy(), num_gt.numpy(), rec_thrs.numpy()
+    C, A = ngt.shape
+    R = len(thr)
+    precision, recall = np.full((T, R, C, A), -1.0), np.full((T, C, A), -1.0)
+    eps = np.spacing(np.float64(1))
+    for c in range(C):
+        rows = slice(int(seg[c]), int(seg[c + 1]))
+        for a in range(A):
+            if ngt[c, a] == 0:
+                continue
+            for t in range(T):
+                sh = np.uint64(a * T + t)
+                hit, skip = ((m[rows] >> sh) & np.uint64(1)).astype(bool), ((ig[rows] >> sh) & np.uint64(1)).astype(bool)
+                tp = np.cumsum(hit & ~skip).astype(np.float64)
+                fp = np.cumsum(~hit & ~skip).astype(np.float64)
+                rc = tp / np.float64(ngt[c, a])
+                pr = tp / (fp + tp + eps)
+                pr = np.maximum.accumulate(pr[::-1])[::-1]
+                at = np.searchsorted(rc, thr, side="left")
+                if len(pr) == 0:                             # ground truth and no record: precision 0, recall 0
+                    precision[t, :, c, a], recall[t, c, a] = 0.0, 0.0
+                    continue
+                precision[t, :, c, a] = np.where(at < len(pr), pr[np.minimum(at, len(pr) - 1)], 0.0)
+                recall[t, c, a] = rc[-1]
+    return torch.from_numpy(precision), torch.from_numpy(recall)
+
+
+class BoxAPEvaluator:
+    """LvisEvaluator + LVISEval for boxes; with fixed_ap_topk = k, LvisEvaluatorFixedAP: no cap per image, every category keeps its k
+    best records over the whole set."""
+
+    def __init__(self, categories, max_dets=300, fixed_ap_topk=None, iou_thrs=None, rec_thrs=None, area_rng=None):
+        self.category_ids = _category_ids(categories)
+        self.freq_groups = [[i for i, c in enumerate(categories) if c["frequency"] == f] for f in FREQUENCIES]
+        d_iou, d_rec, d_area = default_params()
+        self.iou_thrs = np.asarray(d_iou if iou_thrs is None else iou_thrs, dtype=np.float64).reshape(-1)
+        self.rec_thrs = np.asarray(d_rec if rec_thrs is None else rec_thrs, dtype=np.float64).reshape(-1)
+        self.area_rng = np.asarray(d_area if area_rng is None else area_rng, dtype=np.float64).reshape(-1, 2)
+        if len(self.iou_thrs) == 0 or len(self.area_rng) == 0 or len(self.iou_thrs) * len(self.area_rng) > 64:
+            raise ValueError(f"{len(self.iou_thrs)} IoU thresholds x {len(self.area_rng)} area ranges: between 1 and the 64 bits of a record's "
+                             "match word")
+        if (np.diff(self.rec_thrs) < 0).any():
+            raise ValueError("rec_thrs must ascend")
+        if fixed_ap_topk is not None and int(fixed_ap_topk) <= 0:
+            raise ValueError(f"fixed_ap_topk {fixed_ap_topk}: a positive number of records per category")
+        self.fixed_ap_topk = None if fixed_ap_topk is None else int(fixed_ap_topk)
+        self.max_dets = -1 if self.fixed_ap_topk is not None else int(max_dets)
+        self.num_gt = self._iou = self._rec = self._area = None
+        self.reset()
+
+    def reset(self):
+        """Forget every update.  num_gt is zeroed in place."""
+        self._records = []                                   # per update: (scores, labels, match, ignore, valid, ranked), flat
+        self.image_ids = []
+        self._tables = None
+        self.results = None
+        if self.num_gt is not None:
+            self.num_gt.zero_()
+
+    def _state(self, device, targets):
+        if list(targets.category_ids) != self.category_ids:
+            raise ValueError("update: targets packed with other categories than the evaluator's")
+        if self.num_gt is None:
+            self.num_gt = torch.zeros((len(self.category_ids), len(self.area_rng)), dtype=torch.int64, device=device)
+            self._iou, self._rec, self._area = (torch.from_numpy(x.copy()).to(device) for x in (self.iou_thrs, self.rec_thrs, self.area_rng))
+        elif self.num_gt.device != device:
+            raise ValueError(f"update: tensors on {device}, earlier ones on {self.num_gt.device}")
+
+    def update(self, detections, targets, boxes=None):
+        """detections: Detections (scores, labels and count are read; boxes too unless `boxes` fp32 [B, D, 4] gives them in the ORIGINAL
+        image frame, DetImageList.boxes_to_original), targets: DetectionTargets on the same device.  One launch, no synchronisation.
+        -> (match int64 [B, D], ignore int64 [B, D], valid uint8 [B, D])."""
+        boxes = detections.boxes if boxes is None else boxes
+        dev = boxes.device
+        B, D = boxes.shape[:2]
+        if len(targets.image_ids) != B or targets.gt.shape[0] != B or targets.gt.device != dev:
+            raise ValueError(f"update: targets of {len(targets.image_ids)} samples on {targets.gt.device} for {B} images on {dev}")
+        if targets.gt.shape[1] > MAX_GT:
+            raise ValueError(f"update: {targets.gt.shape[1]} ground-truth boxes per image exceed the capacity of {MAX_GT}")
+        self._state(dev, targets)
+        labels, count = detections.labels.to(torch.int32), detections.count.to(torch.int32)
+        if boxes.is_cuda:
+            match, ignore, valid = ops.ap_match(boxes, labels, count, targets.gt, targets.area, targets.category, targets.ignore,
+                                                targets.gt_count, targets.neg_mask, targets.nel_mask, self._iou, self._area, self.num_gt,
+                                                self.max_dets)
+        else:
+            match, ignore, valid = _match_host(boxes, labels, count, targets, self._iou, self._area, self.num_gt, self.max_dets)
+        limit = count.clamp(0, D)
+        if self.max_dets >= 0:
+            limit = limit.clamp(max=self.max_dets)
+        ranked = torch.arange(D, device=dev)[None, :] < limit[:, None]       # the slots that hold a detection (:137-148)
+        self._records.append((detections.scores.detach().float().reshape(-1), labels.reshape(-1), match.reshape(-1), ignore.reshape(-1),
+                              valid.reshape(-1), ranked.reshape(-1)))
+        self.image_ids.extend(targets.image_ids)
+        self._tables = None
+        return match, ignore, valid
+
+    def _gathered(self):
+        dev = self.num_gt.device
+        if not self._records:
+            z = torch.zeros(0, device=dev)
+            return z.float(), z.int(), z.long(), z.long(), z.to(torch.uint8), z.bool()
+        return tuple(torch.cat(col) for col in zip(*self._records))
+
+    def synchronize(self):
+        """Data-parallel evaluation: every rank ends up with the records of all (all_gather, padded to the largest count) and the
+        summed num_gt (all_reduce).  The identity in a single-process run."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+            return
+        if self.num_gt is None:
+            raise RuntimeError("synchronize: no update on this rank yet (the device of the tables is unknown)")
+        world, dev = dist.get_world_size(), self.num_gt.device
+        cols = self._gathered()
+        n = torch.tensor([cols[0].numel()], dtype=torch.int64, device=dev)
+        counts = [torch.zeros_like(n) for _ in range(world)]
+        dist.all_gather(counts, n)
+        counts = [int(c) for c in counts]
+        most = max(counts)
+        merged = []
+        for col in cols:
+            col = col.to(torch.uint8) if col.dtype == torch.bool else col
+            pad = torch.zeros(most, dtype=col.dtype, device=dev)
+            pad[:col.numel()] = col
+            parts = [torch.zeros_like(pad) for _ in range(world)]
+            dist.all_gather(parts, pad)
+            merged.append(torch.cat([p[:k] for p, k in zip(parts, counts)]))
+        merged[5] = merged[5].bool()
+        ids = [None] * world
+        dist.all_gather_object(ids, self.image_ids)
+        dist.all_reduce(self.num_gt)
+        self._records = [tuple(merged)]
+        self.image_ids = [i for part in ids for i in part]
+        self._tables = None
+
+    def _ordered(self, scores, cat):
+        """the permutation by category, then by descending score, stable in arrival order; the sorted categories"""
+        by_score = torch.sort(scores, descending=True, stable=True).indices
+        cats, by_cat = torch.sort(cat[by_score], stable=True)
+        return by_score[by_cat], cats
+
+    def tables(self):
+        """-> (precision fp64 [T, R, C, A], recall fp64 [T, C, A]) on the device of the updates"""
+        if self._tables is not None:
+            return self._tables
+        if self.num_gt is None:
+            raise RuntimeError("tables: no update yet")
+        C, T, dev = len(self.category_ids), len(self.iou_thrs), self.num_gt.device
+        scores, labels, match, ignore, valid, ranked = self._gathered()
+        cat = labels.long() - 1
+        edges = torch.arange(C + 1, device=dev)
+        keep = valid.bool() & ranked
+        if self.fixed_ap_topk is not None:                   # the k best of a category, counted before the federated filter (:776-788)
+            every = torch.where(ranked & (cat >= 0) & (cat < C), cat, torch.full_like(cat, C))
+            order, cats = self._ordered(scores, every)
+            start = torch.searchsorted(cats, edges)
+            rank = torch.empty_like(order)
+            rank[order] = torch.arange(order.numel(), device=dev) - start[cats]
+            keep = keep & (rank < self.fixed_ap_topk)
+        kept = torch.where(keep, cat, torch.full_like(cat, C))                # dropped records sort behind the last category
+        order, cats = self._ordered(scores, kept)
+        seg_ptr = torch.searchsorted(cats, edges)
+        args = (match[order].contiguous(), ignore[order].contiguous(), seg_ptr, self.num_gt, self._rec, T)
+        self._tables = ops.ap_accumulate(*args) if dev.type == "cuda" else _accumulate_host(*args)
+        return self._tables
+
+    def _mean(self, s):
+        s = s[s > -1]
+        return -1 if len(s) == 0 else np.mean(s)
+
+    def summarize(self):
+        """-> the reference's `results`: AP, AP50, AP75, APs, APm, APl, APr, APc, APf and, without fixed_ap_topk, AR@{max_dets},
+        ARs@.., ARm@.., ARl@.. (:551-584); the mean over entries > -1, or -1 for an empty selection (:526-549).  A repeated image id
+        raises ValueError.  The one place that synchronises."""
+        seen = set()
+        for i in self.image_ids:
+            if i in seen:
+                raise ValueError(f"summarize: image {i} was given to update more than once")
+            seen.add(i)
+        precision, recall = self.tables()
+        flat = torch.cat((precision.reshape(-1), recall.reshape(-1))).cpu().numpy()       # the one device-to-host copy
+        precision, recall = flat[:precision.numel()].reshape(precision.shape), flat[precision.numel():].reshape(recall.shape)
+        area = {name: i for i, name in enumerate(AREA_LABELS[:len(self.area_rng)])}
+
+        def at(thr):
+            return np.where(thr == self.iou_thrs)[0]
+        res = {"AP": self._mean(precision[:, :, :, area["all"]]),
+               "AP50": self._mean(precision[at(0.50)][:, :, :, area["all"]]),
+               "AP75": self._mean(precision[at(0.75)][:, :, :, area["all"]])}
+        for key, name in (("APs", "small"), ("APm", "medium"), ("APl", "large")):
+            res[key] = self._mean(precision[:, :, :, area[name]]) if name in area else -1
+        for key, group in zip(("APr", "APc", "APf"), self.freq_groups):
+            res[key] = self._mean(precision[:, :, np.asarray(group, dtype=np.intp), area["all"]])
+        if self.fixed_ap_topk is None:
+            res[f"AR@{self.max_dets}"] = self._mean(recall[:, :, area["all"]])
+            for name in ("small", "medium", "large"):
+                res[f"AR{name[0]}@{self.max_dets}"] = self._mean(recall[:, :, area[name]]) if name in area else -1
+        self.results = res
+        return res
+
+
+def evaluate_detection(model, batches, evaluator):
+    """The detection loop of engine/inference.py, batched, as evaluate_grounding runs the grounding one.  batches yields dicts with
+    "images" (a DetImageList), "tokenizer_input", "positive_maps" and "targets" (DetectionTargets).  -> evaluator.summarize().
+    Nothing synchronises before summarize."""
+    model.eval()
+    with torch.no_grad():
+        for batch in batches:
+            images = batch["images"]
+            detections = model(images, tokenizer_input=batch["tokenizer_input"], positive_map=batch["positive_maps"])
+            boxes = images.boxes_to_original(detections)
+            evaluator.update(detections, batch["targets"].to(boxes.device), boxes=boxes)
+    return evaluator.summarize()

@@ -2082,6 +2082,69 @@ def ground_recall(boxes, labels, count, gt, gt_count, cat_mask, topk, positives,
     return hit, best
 
 
+# ---- box average precision: LVIS-protocol matching and precision / recall tables (csrc/apeval.hip) -----------------------------------
+def ap_max_gt():
+    return int(lib.plain("fiber_ap_max_gt"))
+
+
+def ap_chunk():
+    return int(lib.plain("fiber_ap_chunk"))
+
+
+def ap_match(boxes, labels, count, gt, gt_area, gt_cat, gt_ignore, gt_count, neg_mask, nel_mask, iou_thrs, area_rng, num_gt, max_dets):
+    """One launch of fiber_ap_match, no host synchronisation.  boxes fp32 [B, D, 4] xyxy in the original frame, labels int32 [B, D]
+    (category index + 1), count int32 [B]; gt fp64 [B, G, 4] xywh, gt_area fp64 [B, G], gt_cat int32 [B, G], gt_ignore uint8 [B, G],
+    gt_count int32 [B]; neg_mask / nel_mask int64 [B, ceil(C / 64)] (the bits of a uint64); iou_thrs fp64 [T], area_rng fp64 [A, 2];
+    num_gt int64 [C, A] is accumulated IN PLACE.  -> (match int64 [B, D], ignore int64 [B, D] (bit a * T + t), valid uint8 [B, D])."""
+    B, D = boxes.shape[:2]
+    G = gt.shape[1]
+    C, A = num_gt.shape
+    T = iou_thrs.numel()
+    W = (C + 63) // 64
+    if boxes.shape != (B, D, 4) or labels.shape != (B, D) or count.shape != (B,) or gt.shape != (B, G, 4) or gt_area.shape != (B, G) or \
+            gt_cat.shape != (B, G) or gt_ignore.shape != (B, G) or gt_count.shape != (B,) or neg_mask.shape != (B, W) or \
+            nel_mask.shape != (B, W) or area_rng.shape != (A, 2):
+        raise ValueError(f"ap_match: boxes {tuple(boxes.shape)}, labels {tuple(labels.shape)}, gt {tuple(gt.shape)}, masks "
+                         f"{tuple(neg_mask.shape)} for C = {C}, area_rng {tuple(area_rng.shape)} for A = {A}")
+    if labels.dtype != torch.int32 or count.dtype != torch.int32 or gt.dtype != torch.float64 or gt_area.dtype != torch.float64 or \
+            gt_cat.dtype != torch.int32 or gt_ignore.dtype != torch.uint8 or gt_count.dtype != torch.int32 or \
+            neg_mask.dtype != torch.int64 or nel_mask.dtype != torch.int64 or iou_thrs.dtype != torch.float64 or \
+            area_rng.dtype != torch.float64 or num_gt.dtype != torch.int64 or not num_gt.is_contiguous():
+        raise ValueError("ap_match: gt / gt_area / iou_thrs / area_rng fp64, labels / count / gt_cat / gt_count int32, gt_ignore uint8, "
+                         "masks and num_gt (contiguous) int64")
+    if T * A > 64:
+        raise ValueError(f"ap_match: {T} thresholds x {A} area ranges exceed the 64 bits of a record's match word")
+    if G > ap_max_gt():
+        raise ValueError(f"ap_match: {G} ground-truth boxes per image exceed the kernel's capacity of {ap_max_gt()}")
+    dev = boxes.device
+    match = torch.empty((B, D), dtype=torch.int64, device=dev)
+    ignore = torch.empty((B, D), dtype=torch.int64, device=dev)
+    valid = torch.empty((B, D), dtype=torch.uint8, device=dev)
+    lib.call("fiber_ap_match", lib.ptr(_det_f32(boxes)), lib.ptr(_c(labels)), lib.ptr(_c(count)), lib.ptr(_c(gt)), lib.ptr(_c(gt_area)),
+             lib.ptr(_c(gt_cat)), lib.ptr(_c(gt_ignore)), lib.ptr(_c(gt_count)), lib.ptr(_c(neg_mask)), lib.ptr(_c(nel_mask)),
+             lib.ptr(_c(iou_thrs)), lib.ptr(_c(area_rng)), lib.ptr(match), lib.ptr(ignore), lib.ptr(valid), lib.ptr(num_gt), B, D, G, C, T, A,
+             int(max_dets))
+    return match, ignore, valid
+
+
+def ap_accumulate(match, ignore, seg_ptr, num_gt, rec_thrs, T):
+    """One launch of fiber_ap_accumulate.  match / ignore int64 [N]: the kept records ordered by category, then by descending score;
+    seg_ptr int64 [C + 1]; num_gt int64 [C, A]; rec_thrs fp64 [R] ascending.  -> (precision fp64 [T, R, C, A], recall fp64 [T, C, A])."""
+    C, A = num_gt.shape
+    N, R = match.numel(), rec_thrs.numel()
+    if match.dtype != torch.int64 or ignore.dtype != torch.int64 or ignore.numel() != N or seg_ptr.dtype != torch.int64 or \
+            seg_ptr.shape != (C + 1,) or num_gt.dtype != torch.int64 or rec_thrs.dtype != torch.float64:
+        raise ValueError("ap_accumulate: match / ignore int64 [N], seg_ptr int64 [C + 1], num_gt int64 [C, A], rec_thrs fp64 [R]")
+    if T * A > 64:
+        raise ValueError(f"ap_accumulate: {T} thresholds x {A} area ranges exceed the 64 bits of a record's match word")
+    dev = num_gt.device
+    precision = torch.empty((T, R, C, A), dtype=torch.float64, device=dev)
+    recall = torch.empty((T, C, A), dtype=torch.float64, device=dev)
+    lib.call("fiber_ap_accumulate", lib.ptr(_c(match)), lib.ptr(_c(ignore)), lib.ptr(_c(seg_ptr)), lib.ptr(_c(num_gt)), lib.ptr(_c(rec_thrs)),
+             lib.ptr(precision), lib.ptr(recall), N, C, T, A, R)
+    return precision, recall
+
+
 # ---- grounding training: ATSS assignment + GIoU / centerness losses (csrc/atss.hip) --------------------------------------------------
 class Assignment:
     """ops.atss_assign's result, fixed shapes: matched int32 [B, A] (-1 unassigned), labels int32 [B, A] (0), reg_targets fp32 [B, A, 4]

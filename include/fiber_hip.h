@@ -404,6 +404,41 @@ int fiber_ground_recall(const float* boxes, const int* labels, const int* count,
                         const unsigned long long* cat_mask, const int* topk, int* hit, double* best, long long* positives, long long* totals,
                         int B, int D, int P, int G, int K, int ncat, double thresh, int mode, fiber_stream_t stream);
 
+/* Box average precision by the LVIS protocol (csrc/apeval.hip); file:line relative to the reference's
+ * fine_grained/maskrcnn_benchmark/data/datasets/evaluation/lvis/lvis_eval.py.  Nothing crosses to the host.
+ * fiber_ap_match replaces, for one batch, :137-148 (limit_dets_per_image), :237-241 (the federated filter), :293-317 (compute_iou) and
+ * :319-411 (evaluate_img); one wave per (image, area range, threshold).
+ * boxes fp32 [B,D,4] xyxy in the ORIGINAL image frame, labels int32 [B,D] (category index + 1), count int32 [B]: the first
+ * min(count[b], max_dets) rows are read in their stored descending-score order; max_dets < 0 = no cap.  gt fp64 [B,G,4] xywh, gt_area fp64
+ * [B,G] (the annotation's own area), gt_cat int32 [B,G] (category index), gt_ignore uint8 [B,G], gt_count int32 [B]; neg_mask / nel_mask
+ * uint64 [B,ceil(C/64)]: bit c = category c is in the image's negative / not-exhaustive list.  iou_thrs fp64 [T] and area_rng fp64 [A,2]
+ * are read from device memory as the host computed them.
+ * The detection box is x, y, fp32(x2 - x), fp32(y2 - y) (convert_to_xywh, :985-987), everything after it fp64: area w * h,
+ * iou = i / (da + ga - i) with i = max(min(dx + dw, gx + gw) - max(dx, gx), 0) * (the same in y) and ga = gw * gh.  A ground truth is
+ * ignored when gt_ignore or its area field < lo or > hi; non-ignored ones come first, stable in packing order.  Per (area range,
+ * threshold), detections in score order: among unmatched ground truths of the detection's category with iou >= min(thr, 1 - 1e-10) the
+ * largest (non-ignored, iou, index) wins.  match / ignore uint64 [B,D]: bit a * T + t; an unmatched detection is ignored when its area is
+ * outside the range or its category is not-exhaustive.  valid uint8 [B,D]: 0 past min(count, max_dets), for a label outside 1..C, and when
+ * the category is neither among the image's ground truth nor in its negative list (match = ignore = 0 there).  Every element is written.
+ * num_gt int64 [C,A]: the non-ignored ground truths, ACCUMULATED in place with integer atomic adds (two runs give the same bits).
+ * T * A > 64, G > fiber_ap_max_gt(), negative sizes, NULL or misaligned pointers -> 1; B == 0 -> 0 without a launch.
+ * fiber_ap_accumulate replaces :413-524 (accumulate) for all categories at once; one wave per (category, area range, threshold) over
+ * chunks of fiber_ap_chunk() records.  match / ignore uint64 [N]: the kept records ordered by category, then by descending score (stable
+ * in arrival order); seg_ptr int64 [C + 1] into that order; rec_thrs fp64 [R] ASCENDING.  tp = match & ~ignore, fp = ~match & ~ignore,
+ * cumulative integer sums, rc = tp / num_gt, pr = tp / (fp + tp + 2^-52) made non-increasing from the right; precision fp64 [T,R,C,A] = pr
+ * at the first index with rc >= rec_thrs[r], 0.0 when there is none; recall fp64 [T,C,A] = the last rc, 0.0 without records; both -1
+ * where num_gt == 0.  Every element is written, also with N == 0.  T * A > 64, negative sizes, NULL or misaligned pointers -> 1. */
+int fiber_ap_max_gt(void);
+int fiber_ap_chunk(void);
+int fiber_ap_match(const float* boxes, const int* labels, const int* count, const double* gt, const double* gt_area, const int* gt_cat,
+                   const unsigned char* gt_ignore, const int* gt_count, const unsigned long long* neg_mask,
+                   const unsigned long long* nel_mask, const double* iou_thrs, const double* area_rng, unsigned long long* match,
+                   unsigned long long* ignore, unsigned char* valid, long long* num_gt, int B, int D, int G, int C, int T, int A, int max_dets,
+                   fiber_stream_t stream);
+int fiber_ap_accumulate(const unsigned long long* match, const unsigned long long* ignore, const long long* seg_ptr, const long long* num_gt,
+                        const double* rec_thrs, double* precision, double* recall, long long N, int C, int T, int A, int R,
+                        fiber_stream_t stream);
+
 /* Grounding training: ATSS target assignment and the box / centerness losses with fixed shapes and no host synchronisation
  * (csrc/atss.hip); file:line relative to the reference's fine_grained/maskrcnn_benchmark/.  Targets: gt_boxes fp32 [B,Gmax,4] (xyxy),
  * gt_labels int32 [B,Gmax], num_gt int32 [B], positive_map uint8 [B,Gmax,T]; rows g >= num_gt[b] are never read.  anchors fp32 [A,4]: the
