@@ -209,7 +209,90 @@ __global__ __launch_bounds__(64) void det_nms_select_kernel(const float* __restr
   if (lane == 0) ocount[b] = count;
 }
 
+constexpr int MRG_THREADS = 1024;          // 16 waves: the binary searches are LDS-latency bound, more waves hide it
+constexpr int MRG_MAX_N = 16384;           // K * D: the image's scores as fp32 fill 64 KB of LDS (LVIS: 31 x 300)
+constexpr int MRG_MAX_K = 64;
+
+// how many of the descending list s[0, n) are >= v (strict = false) or > v (strict = true)
+__device__ __forceinline__ int merge_count(const float* s, int n, float v, bool strict) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    const float m = s[mid];
+    if (strict ? m > v : m >= v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// One workgroup per image merges its K descending lists.  Candidate (k, s) ranks at s + #{>= it in every earlier chunk} + #{> it in every
+// later chunk}: equal scores go to the earlier chunk, then the earlier slot, the ranks are a permutation of [0, total) and every rank
+// < N is one plain store.  rank <= total - 1 whatever the scores hold (each term is bounded by its list's length), so no score pattern,
+// NaN and unsorted lists included, writes out of bounds; with such input the ranks may collide and the result is unspecified.
+__global__ __launch_bounds__(MRG_THREADS) void det_merge_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                                const int* __restrict__ labels, const int* __restrict__ source,
+                                                                const int* __restrict__ count, const int* __restrict__ table,
+                                                                float* __restrict__ oboxes, float* __restrict__ oscores,
+                                                                int* __restrict__ olabels, int* __restrict__ osource,
+                                                                int* __restrict__ ochunk, int* __restrict__ ocount, int K, int D, int Cc,
+                                                                int N) {
+  extern __shared__ __attribute__((aligned(16))) float sc[];       // [K * D]
+  const int b = blockIdx.x, tid = threadIdx.x, KD = K * D;
+  const size_t base = (size_t)b * KD;
+  const int* __restrict__ cnt = count + (size_t)b * K;
+  for (int i = tid; i < KD; i += MRG_THREADS) sc[i] = scores[base + i];
+  int total = 0;
+  for (int k = 0; k < K; ++k) total += min(max(cnt[k], 0), D);
+  __syncthreads();
+  for (int i = tid; i < KD; i += MRG_THREADS) {
+    const int k = i / D, s = i - k * D;
+    if (s >= min(max(cnt[k], 0), D)) continue;              // whatever the slots past count hold is ignored
+    const float v = sc[i];
+    int rank = s;
+    for (int j = 0; j < K; ++j)
+      if (j != k) rank += merge_count(sc + j * D, min(max(cnt[j], 0), D), v, j > k);
+    if (rank >= N) continue;
+    const size_t src = base + i, dst = (size_t)b * N + rank;
+    const int local = labels[src];
+    *reinterpret_cast<f32x4*>(oboxes + dst * 4) = *reinterpret_cast<const f32x4*>(boxes + src * 4);
+    oscores[dst] = v;
+    olabels[dst] = (local >= 1 && local <= Cc) ? table[(size_t)k * Cc + local - 1] : 0;
+    osource[dst] = source[src];
+    ochunk[dst] = k;
+  }
+  const int kept = min(total, N);
+  for (int r = kept + tid; r < N; r += MRG_THREADS) {        // the padding fiber_det_nms_select writes
+    const size_t dst = (size_t)b * N + r;
+    *reinterpret_cast<f32x4*>(oboxes + dst * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+    oscores[dst] = -1.f;
+    olabels[dst] = 0;
+    osource[dst] = -1;
+    ochunk[dst] = -1;
+  }
+  if (tid == 0) ocount[b] = kept;
+}
+
 }  // namespace
+
+// Largest K * D (candidates per image over all chunks) the merge kernel stages in LDS
+extern "C" int fiber_det_merge_max_candidates(void) { return MRG_MAX_N; }
+
+extern "C" int fiber_det_merge(const float* boxes, const float* scores, const int* labels, const int* source, const int* count,
+                               const int* label_table, float* out_boxes, float* out_scores, int* out_labels, int* out_source,
+                               int* out_chunk, int* out_count, int B, int K, int D, int Cc, int N, hipStream_t stream) {
+  if (B < 0 || K < 0 || D < 0 || Cc < 0 || N < 0 || K > MRG_MAX_K || (long long)K * D > MRG_MAX_N || N > K * D) return FIBER_EINVAL;
+  if (B == 0 || K * D == 0) return FIBER_OK;
+  if (N == 0) return FIBER_EINVAL;
+  if (!boxes || !scores || !labels || !source || !count || (Cc > 0 && !label_table) || !out_boxes || !out_scores || !out_labels ||
+      !out_source || !out_chunk || !out_count)
+    return FIBER_EINVAL;
+  if (fiber_misaligned(16, boxes, out_boxes) ||
+      fiber_misaligned(4, scores, labels, source, count, label_table, out_scores, out_labels, out_source, out_chunk, out_count))
+    return FIBER_EINVAL;
+  hipLaunchKernelGGL(det_merge_kernel, dim3(B), dim3(MRG_THREADS), (size_t)K * D * sizeof(float), stream, boxes, scores, labels, source,
+                     count, label_table, out_boxes, out_scores, out_labels, out_source, out_chunk, out_count, K, D, Cc, N);
+  FIBER_CHECK_LAUNCH();
+  return FIBER_OK;
+}
 
 // Largest N (candidates per image after the per-level top-k) the select kernel's register bitmap holds
 extern "C" int fiber_det_max_candidates(void) { return SEL_MAX_N; }

@@ -31,6 +31,11 @@ This is the LVIS protocol.  COCO ground truth can be evaluated with crowd boxes 
 negative list, but that is the LVIS protocol on COCO data, not COCOeval: the COCO API's crowd rule (IoU over the detection's area,
 re-matchable crowd regions) is not reproduced.  Out of scope as well: segmentation and keypoint IoU, LvisDumper, test-time augmentation
 and the dataset readers.
+
+evaluate_detection runs one prompt per image; evaluate_detection_chunked a vocabulary cut into prompts (detection_prompts.py), with the
+prompt-independent part of the backbone computed once per image, the image-independent part once per evaluation and the chunks of an image
+merged by ops.det_merge.  Out of scope there: sharing the FPN lateral of the prompt-independent level between an image's pairs, the
+multi-scale im_detect_bbox_aug, and the result CSV writers.
 """
 import numpy as np
 import torch
@@ -396,6 +401,27 @@ def evaluate_detection(model, batches, evaluator):
         for batch in batches:
             images = batch["images"]
             detections = model(images, tokenizer_input=batch["tokenizer_input"], positive_map=batch["positive_maps"])
+            boxes = images.boxes_to_original(detections)
+            evaluator.update(detections, batch["targets"].to(boxes.device), boxes=boxes)
+    return evaluator.summarize()
+
+
+def evaluate_detection_chunked(model, batches, evaluator, prompts, prompts_per_pass=None):
+    """The detection loop over a vocabulary too large for one prompt (TEST.CHUNKED_EVALUATION: LVIS, 1203 categories as 31 prompts of
+    40).  prompts: detection_prompts.build_detection_prompts over the evaluator's categories; their text prefix is encoded once
+    (GeneralizedVLRCNN.encode_prompts), every batch then goes through detect_chunked, which merges an image's chunks on the device and cuts
+    to the evaluator's max_dets as LVISResults.limit_dets_per_image does (:137-148; no cut with fixed_ap_topk, :790-795).  batches yields
+    dicts with "images" (a DetImageList) and "targets" (DetectionTargets).  -> evaluator.summarize().  Nothing synchronises before
+    summarize."""
+    if list(prompts.category_ids) != list(evaluator.category_ids):
+        raise ValueError("evaluate_detection_chunked: the prompts were built over other categories than the evaluator's")
+    model.eval()
+    max_dets = evaluator.max_dets if evaluator.max_dets >= 0 else None
+    with torch.no_grad():
+        state = model.encode_prompts(prompts)
+        for batch in batches:
+            images = batch["images"]
+            detections = model.detect_chunked(images, state, prompts_per_pass, max_dets=max_dets)
             boxes = images.boxes_to_original(detections)
             evaluator.update(detections, batch["targets"].to(boxes.device), boxes=boxes)
     return evaluator.summarize()

@@ -215,51 +215,120 @@ class FusionSwinTransformer(nn.Module):
         aggregate = embedded.float().sum(1) / mask.sum(-1, keepdim=True).float()
         return {"aggregate": aggregate, "embedded": embedded, "masks": mask, "hidden": features}
 
-    def forward(self, tokenizer_input, images):
-        sw, tm = self.backbone.body, self.language_backbone.body.model
-        x = images.tensors if hasattr(images, "tensors") else images
-        x, Wh, Ww = sw.patch_embed(x)
-        text = tm.embeddings(input_ids=tokenizer_input["input_ids"])
-        ext = tm.get_extended_attention_mask(tokenizer_input["attention_mask"])
-        for layer in tm.encoder.layer[:6]:                          # num_pre_text = 6 (:849)
-            text = layer(text, ext)[0]
-        outs = []
-        fpn = self.backbone.fpn
-        nhwc = hasattr(fpn, "forward_nhwc")                         # modules/fpn.py: takes the channels-last tokens as they lie
+    # The two modalities are blind to each other up to stage-2 block 14 and text layer 6 (:849-865).  forward is cut there into a part that
+    # depends on the image alone, a part that depends on the prompt alone and the fused rest, so that chunked detection (many prompts
+    # per image, the same prompts for every image: GeneralizedVLRCNN.detect_chunked) computes each of the first two once.
+    NUM_PRE_TEXT, NUM_PRE_BLOCK = 6, 14
 
-        def emit(i, t, H, W):
-            if f"stage{i + 2}" in sw.out_features:
-                n = getattr(sw, f"norm{i}")
-                t = t if isinstance(n, nn.Identity) else ops.layernorm(t, n.weight, n.bias, n.eps)
-                t = t.view(-1, H, W, sw.num_features[i])
-                outs.append(t if nhwc else t.permute(0, 3, 1, 2).contiguous())
+    def _emit(self, outs, i, t, H, W):
+        sw = self.backbone.body
+        if f"stage{i + 2}" in sw.out_features:
+            n = getattr(sw, f"norm{i}")
+            t = t if isinstance(n, nn.Identity) else ops.layernorm(t, n.weight, n.bias, n.eps)
+            t = t.view(-1, H, W, sw.num_features[i])
+            nhwc = hasattr(self.backbone.fpn, "forward_nhwc")       # modules/fpn.py: takes the channels-last tokens as they lie
+            outs.append(t if nhwc else t.permute(0, 3, 1, 2).contiguous())
+
+    def _image_stages(self, x, Wh, Ww):
+        """The image side from the patch tokens up to the first block that reads text -> ImageState"""
+        sw = self.backbone.body
+        outs = []
         for i in (0, 1):                                            # num_pre_vision = 2 (:854)
             x_out, H, W, x, Wh, Ww = sw.layers[i](x, Wh, Ww)
-            emit(i, x_out, H, W)
+            self._emit(outs, i, x_out, H, W)
         stage = sw.layers[2]
-        for j, blk in enumerate(stage.blocks):
+        done = min(self.NUM_PRE_BLOCK, len(stage.blocks))           # num_pre_block = 14 (:865)
+        for blk in stage.blocks[:done]:
             blk.H, blk.W = Wh, Ww
-            if j < 14:                                              # num_pre_block = 14 (:865)
-                x = blk(x)
-            else:                                                   # both sides read the other's PRE-block state (:876-885)
-                fused = blk(x, None, text, ext)
-                text = tm.encoder.layer[j - 14 + 6](text, ext, encoder_hidden_states=x)[0]
-                x = fused
-        emit(2, x, Wh, Ww)
+            x = blk(x)
+        st = ImageState(x, Wh, Ww, outs, 2, done)
+        if done == len(stage.blocks):                               # a shallow stage 2 has no fused block: its tail is the image's too
+            self._finish_stage2(st)
+        return st
+
+    def _finish_stage2(self, st):
+        stage = self.backbone.body.layers[2]
+        self._emit(st.outs, 2, st.x, st.Wh, st.Ww)
         if stage.downsample is not None:
-            x = stage.downsample(x, Wh, Ww)
-            Wh, Ww = (Wh + 1) // 2, (Ww + 1) // 2
+            st.x = stage.downsample(st.x, st.Wh, st.Ww)
+            st.Wh, st.Ww = (st.Wh + 1) // 2, (st.Ww + 1) // 2
+        st.stage, st.block = 3, 0
+
+    def image_prefix(self, images):
+        """Everything that depends on the image alone: patch embedding, stages 0 and 1, the stage-2 blocks before the first fused one.
+        -> ImageState (token state x [B, Wh * Ww, C], Wh, Ww, the stage maps emitted so far, where fuse resumes)"""
+        x = images.tensors if hasattr(images, "tensors") else images
+        return self._image_stages(*self.backbone.body.patch_embed(x))
+
+    def text_prefix(self, tokenizer_input):
+        """Everything that depends on the prompt alone: the embeddings and encoder.layer[:6] -> TextState (text [K, S, 768], the
+        extended mask, input_ids, attention_mask)"""
+        tm = self.language_backbone.body.model
+        text = tm.embeddings(input_ids=tokenizer_input["input_ids"])
+        ext = tm.get_extended_attention_mask(tokenizer_input["attention_mask"])
+        for layer in tm.encoder.layer[:self.NUM_PRE_TEXT]:          # num_pre_text = 6 (:849)
+            text = layer(text, ext)[0]
+        return TextState(text, ext, tokenizer_input["input_ids"], tokenizer_input["attention_mask"])
+
+    def fuse(self, image_state, text_state, image_index=None, text_index=None):
+        """The fused blocks, the remaining stage maps, get_aggregated_output and the FPN on the batch whose sample n pairs image
+        image_index[n] with prompt text_index[n] (int64 device tensors, gathered with index_select; None = the state as it is, the
+        two batches then being equal).  The states are not modified.  -> (visual_features, language_dict_features, None)"""
+        sw, tm = self.backbone.body, self.language_backbone.body.model
+        x, Wh, Ww, outs = image_state.x, image_state.Wh, image_state.Ww, list(image_state.outs)
+        text, ext, ids, am = text_state.text, text_state.ext, text_state.input_ids, text_state.attention_mask
+        if image_index is not None:
+            x, outs = x.index_select(0, image_index), [o.index_select(0, image_index) for o in outs]
+        if text_index is not None:
+            text, ext, ids, am = (t.index_select(0, text_index) for t in (text, ext, ids, am))
+        if x.shape[0] != text.shape[0]:
+            raise ValueError(f"fuse: {x.shape[0]} image rows paired with {text.shape[0]} prompt rows")
+        st = ImageState(x, Wh, Ww, outs, image_state.stage, image_state.block)
+        if st.stage == 2:
+            stage = sw.layers[2]
+            for j in range(st.block, len(stage.blocks)):            # both sides read the other's PRE-block state (:876-885)
+                blk = stage.blocks[j]
+                blk.H, blk.W = st.Wh, st.Ww
+                fused = blk(st.x, None, text, ext)
+                text = tm.encoder.layer[j - self.NUM_PRE_BLOCK + self.NUM_PRE_TEXT](text, ext, encoder_hidden_states=st.x)[0]
+                st.x = fused
+            self._finish_stage2(st)
         stage = sw.layers[3]
+        x, Wh, Ww = st.x, st.Wh, st.Ww
         for j in (0, 1):
             blk = stage.blocks[j]
             blk.H, blk.W = Wh, Ww
             fused = blk(x, None, text, ext)
             text = tm.encoder.layer[10 + j](text, ext, encoder_hidden_states=x)[0]
             x = fused
-        emit(3, x, Wh, Ww)
-        lang = self.get_aggregated_output(text, tokenizer_input["input_ids"], tokenizer_input["attention_mask"])
-        if nhwc:                                                    # the same values fpn(outs) would transpose back (bit for bit)
-            visual = tuple(t.permute(0, 3, 1, 2).float() for t in fpn.forward_nhwc(outs))
+        self._emit(st.outs, 3, x, Wh, Ww)
+        lang = self.get_aggregated_output(text, ids, am)
+        fpn = self.backbone.fpn
+        if hasattr(fpn, "forward_nhwc"):                            # the same values fpn(outs) would transpose back (bit for bit)
+            visual = tuple(t.permute(0, 3, 1, 2).float() for t in fpn.forward_nhwc(st.outs))
         else:
-            visual = fpn(outs) if fpn is not None else outs
+            visual = fpn(st.outs) if fpn is not None else st.outs
         return visual, lang, None
+
+    def forward(self, tokenizer_input, images):
+        """fuse(image_prefix(images), text_prefix(tokenizer_input)), with the patch embedding ahead of the text prefix as it always ran,
+        so that the training-mode draws (dropout, DropPath) come from the key stream in the order they always did."""
+        x = images.tensors if hasattr(images, "tensors") else images
+        tokens = self.backbone.body.patch_embed(x)
+        text_state = self.text_prefix(tokenizer_input)
+        return self.fuse(self._image_stages(*tokens), text_state)
+
+
+class ImageState:
+    """The image side at the cut: x [B, Wh * Ww, C] token state, the stage maps emitted so far (`outs`), and where fuse resumes
+    (`stage` 2 with `block` the first fused block, or stage 3 when stage 2 has no fused block)."""
+
+    def __init__(self, x, Wh, Ww, outs, stage, block):
+        self.x, self.Wh, self.Ww, self.outs, self.stage, self.block = x, Wh, Ww, outs, stage, block
+
+
+class TextState:
+    """The text side at the cut: text [K, S, 768] after encoder.layer[:6], the extended mask and the tokenizer input it came from"""
+
+    def __init__(self, text, ext, input_ids, attention_mask):
+        self.text, self.ext, self.input_ids, self.attention_mask = text, ext, input_ids, attention_mask

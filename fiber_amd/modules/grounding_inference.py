@@ -215,11 +215,13 @@ def pack_positive_maps(maps, num_classes, v2=False):
 
 class Detections:
     """Fixed-size result: boxes fp32 [B, D, 4] (xyxy, +1 convention), scores fp32 [B, D] (-1 past count), labels int32 [B, D],
-    source int32 [B, D] (level << 28 | anchor << 10 | class; -1 past count), count int32 [B]; descending score per image."""
+    source int32 [B, D] (level << 28 | anchor << 10 | class; -1 past count), count int32 [B]; descending score per image.  chunk int32
+    [B, D] (the prompt a detection came from, -1 past count; its source's class field is local to that prompt) is set by chunked detection
+    (GeneralizedVLRCNN.detect_chunked) only, None otherwise."""
     SOURCE_A_SHIFT, SOURCE_LEVEL_SHIFT = 10, 28
 
-    def __init__(self, boxes, scores, labels, source, count):
-        self.boxes, self.scores, self.labels, self.source, self.count = boxes, scores, labels, source, count
+    def __init__(self, boxes, scores, labels, source, count, chunk=None):
+        self.boxes, self.scores, self.labels, self.source, self.count, self.chunk = boxes, scores, labels, source, count, chunk
 
     def to_list(self):
         """Per image {"boxes", "scores", "labels" (int64), "source"} trimmed to count.  The one call that synchronises."""
@@ -282,12 +284,13 @@ class ATSSPostProcessor(nn.Module):
         return min(int(self.pre_nms_top_n), num_anchors * C)
 
     def forward(self, box_regression, centerness, image_sizes, anchors, dot_product_logits=None, positive_map=None, box_cls=None,
-                token_logits=None):
+                token_logits=None, num_classes=None):
         """box_regression / centerness / dot_product_logits: per level, as VLDyHead.forward returns them; image_sizes fp32 [B, 2] device
         tensor of (w, h) per image; anchors: one [A_l, 4] tensor per level (AnchorGenerator.grid_anchors of the feature shapes: the
         reference's per-image BoxList copies differ in nothing but the size field).  positive_map: the reference's dict (one map for the
         batch, cached by csr()), a list of B dicts (one per sample: packed here with one host-to-device copy per call, not cached), or a
-        PackedPositiveMaps already on the device (no copy).  -> Detections"""
+        PackedPositiveMaps already on the device (no copy).  num_classes: the width C of the dense scores for this call (chunked detection
+        scores one prompt's classes at a time); None = num_score_classes().  -> Detections"""
         if token_logits is not None:
             raise NotImplementedError(f"ATSSPostProcessor token_logits: {_UNSUPPORTED['token_logits']}")
         if dot_product_logits is None:
@@ -298,7 +301,7 @@ class ATSSPostProcessor(nn.Module):
             raise NotImplementedError(f"ATSSPostProcessor num_anchors != 1: {_UNSUPPORTED['num_anchors']}")
         dev = dot_product_logits[0].device
         B = dot_product_logits[0].shape[0]
-        C = self.num_score_classes(box_cls)
+        C = self.num_score_classes(box_cls) if num_classes is None else int(num_classes)
         if isinstance(positive_map, (list, tuple)):
             if len(positive_map) != B:
                 raise ValueError(f"ATSSPostProcessor: {len(positive_map)} positive maps for a batch of {B}")
@@ -366,12 +369,13 @@ class VLDyHeadModule(nn.Module):
         w = getattr(self.cfg.MODEL.DYHEAD.FUSE_CONFIG, "DOT_PRODUCT_TOKEN_LOSS_WEIGHT", 1.0)
         return {"loss_reg": reg, "loss_centerness": ctr, "loss_cls": cls, "loss_dot_product_token": token * w}
 
-    def forward(self, image_sizes, features, language_dict_features, positive_map=None, targets=None):
+    def forward(self, image_sizes, features, language_dict_features, positive_map=None, targets=None, num_classes=None):
         """Training mode with `targets`: -> {"loss_reg", "loss_centerness", "loss_cls", "loss_dot_product_token"} (image_sizes and
         positive_map are not read: the anchors do not depend on the image and the targets carry their positive map).  Eval: image_sizes: [(h, w)] per image as ImageList.image_sizes, or a [B, 2] tensor of (w, h); features: the FPN levels
         [B, C, H, W]; language_dict_features["embedded"]: [B, 256, LANG_DIM]; positive_map: one dict for the batch, a list of B dicts or a
         PackedPositiveMaps (one map per sample: see ATSSPostProcessor.forward).  -> Detections.  A list of sizes is copied to the device
-        here (a host-to-device copy per call); pass the tensor, already on the device, to avoid it or to capture the call in a graph."""
+        here (a host-to-device copy per call); pass the tensor, already on the device, to avoid it or to capture the call in a graph.
+        num_classes: see ATSSPostProcessor.forward."""
         if self.training:
             if targets is None:
                 raise NotImplementedError("VLDyHeadModule in training mode needs targets= (grounding_train.pack_targets); without them "
@@ -384,4 +388,4 @@ class VLDyHeadModule(nn.Module):
         with torch.no_grad():
             out = self.head(features, language_dict_features, language_dict_features["embedded"])
             return self.box_selector_test(out[1], out[2], image_sizes, self.anchor_generator(features), out[6], positive_map,
-                                          box_cls=out[0], token_logits=out[3])
+                                          box_cls=out[0], token_logits=out[3], num_classes=num_classes)

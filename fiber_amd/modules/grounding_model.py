@@ -13,12 +13,14 @@ Differences in the call surface, none in the computation:
     four-entry loss dict; eval returns grounding_inference.Detections instead of a list of BoxLists;
   * `images` is a padded [B, 3, H, W] tensor, a (tensor, image_sizes) pair, or an object with .tensors / .image_sizes (ImageList).
 """
+import torch
 import torch.nn as nn
 
+from .. import ops
 from . import roberta as RB
 from .fpn import build_swint_fpn
 from .fusion_swin import FusionSwinTransformer
-from .grounding_inference import VLDyHeadModule
+from .grounding_inference import Detections, PackedPositiveMaps, VLDyHeadModule
 
 
 def _need(cond, name, why):
@@ -101,13 +103,7 @@ class GeneralizedVLRCNN(nn.Module):
         (phrase grounding, referring expressions).  greenlight_map is read by the MLM branch only and is accepted for signature parity."""
         if self.training and targets is None:
             raise ValueError("In training mode, targets should be passed")
-        sizes = None
-        if isinstance(images, (tuple, list)):
-            images, sizes = images
-        elif hasattr(images, "tensors"):
-            images, sizes = images.tensors, getattr(images, "image_sizes", None)
-        if sizes is None:
-            sizes = [tuple(images.shape[-2:])] * images.shape[0]     # (h, w) per image, as ImageList.image_sizes
+        images, sizes = self._images_and_sizes(images)
         if tokenizer_input is None:
             if captions is None:
                 raise ValueError("GeneralizedVLRCNN: captions (with a tokenizer) or tokenizer_input is required")
@@ -117,3 +113,75 @@ class GeneralizedVLRCNN(nn.Module):
         if targets is not None and self.training:
             targets = targets.to(images.device)
         return self.rpn(sizes, list(visual_features), language_dict_features, positive_map, targets if self.training else None)
+
+    @staticmethod
+    def _images_and_sizes(images):
+        """-> (the padded [B, 3, H, W] tensor, [(h, w)] per image as ImageList.image_sizes)"""
+        sizes = None
+        if isinstance(images, (tuple, list)):
+            images, sizes = images
+        elif hasattr(images, "tensors"):
+            images, sizes = images.tensors, getattr(images, "image_sizes", None)
+        if sizes is None:
+            sizes = [tuple(images.shape[-2:])] * images.shape[0]     # (h, w) per image, as ImageList.image_sizes
+        return images, sizes
+
+    # ---- chunked open-vocabulary detection (TEST.CHUNKED_EVALUATION, engine/inference.py:483-575) ---------------------------------------
+    # The reference runs the whole model once per (image, chunk of the vocabulary) and lets the evaluator sort the union.  Here the part of
+    # the backbone that reads the image alone runs once per image, the part that reads the prompt alone once per evaluation, and only the
+    # fused blocks, the FPN and the head run per pair; the chunks of an image are merged on the device (ops.det_merge).
+    def encode_prompts(self, prompts):
+        """prompts: detection_prompts.DetectionPrompts -> PromptState: the text prefix of all K prompts and the prompts on the device of the
+        model.  Computed in eval mode under no_grad; nothing is cached here, the caller holds the state for as long as the weights stand."""
+        if self.training:
+            raise RuntimeError("encode_prompts: the model is in training mode (chunked detection is an inference path: call .eval())")
+        prompts = prompts.to(next(self.parameters()).device)
+        with torch.no_grad():
+            text = self.fusion_backbone.text_prefix({"input_ids": prompts.input_ids, "attention_mask": prompts.attention_mask})
+        return PromptState(text, prompts)
+
+    def detect_chunked(self, images, prompt_state, prompts_per_pass=None, max_dets=None):
+        """images as forward takes them; prompt_state: encode_prompts' result.  The K prompts are walked in passes of prompts_per_pass
+        (default: all K at once; the last pass may be narrower): a pass runs the fused blocks, the FPN and the head on the pair batch whose
+        sample b * P + p is (image b, prompt p of the pass), scoring the chunk's own classes only (C = the chunk width).  The K results
+        per image are merged into one ranked list of at most max_dets (default K * DETECTIONS_PER_IMG) with the labels BoxAPEvaluator
+        reads.  -> Detections with `chunk` set.  Nothing synchronises."""
+        if self.training:
+            raise RuntimeError("detect_chunked: the model is in training mode (chunked detection is an inference path: call .eval())")
+        images, sizes = self._images_and_sizes(images)
+        prompts, fb = prompt_state.prompts, self.fusion_backbone
+        dev = images.device
+        B, K, Cc = int(images.shape[0]), len(prompts), prompts.packed.num_classes
+        if prompts.input_ids.device != dev:
+            raise ValueError(f"detect_chunked: images on {dev}, the prompt state on {prompts.input_ids.device}")
+        P = K if prompts_per_pass is None else int(prompts_per_pass)
+        if P <= 0:
+            raise ValueError(f"detect_chunked: prompts_per_pass {prompts_per_pass}")
+        if not torch.is_tensor(sizes):
+            sizes = torch.tensor([[float(w), float(h)] for h, w in sizes], dtype=torch.float32)
+        sizes = sizes.to(device=dev, dtype=torch.float32, non_blocking=True)
+        parts = []
+        with torch.no_grad():
+            image_state = fb.image_prefix(images)
+            rows = torch.arange(B, device=dev)
+            for k0 in range(0, K, P):
+                p = min(P, K - k0)
+                image_index = rows[:, None].expand(B, p).reshape(-1)              # (repeat_interleave would read its size back)
+                text_index = torch.arange(k0, k0 + p, device=dev).repeat(B)
+                visual, lang, _ = fb.fuse(image_state, prompt_state.text, image_index, text_index)
+                lang["mlm_labels"] = None
+                maps = PackedPositiveMaps(prompts.packed.class_ptr.index_select(0, text_index), prompts.packed.tok_idx)
+                det = self.rpn(sizes.index_select(0, image_index), list(visual), lang, maps, None, num_classes=Cc)
+                D = det.scores.shape[1]
+                parts.append((det.boxes.view(B, p, D, 4), det.scores.view(B, p, D), det.labels.view(B, p, D), det.source.view(B, p, D),
+                              det.count.view(B, p)))
+            boxes, scores, labels, source, count = (torch.cat(col, dim=1) for col in zip(*parts))
+            *merged, chunk, total = ops.det_merge(boxes, scores, labels, source, count, prompts.label_table, max_dets)
+        return Detections(*merged, total, chunk=chunk)
+
+
+class PromptState:
+    """encode_prompts' result: `text` (fusion_swin.TextState of the K prompts) and `prompts` (DetectionPrompts on the device)"""
+
+    def __init__(self, text, prompts):
+        self.text, self.prompts = text, prompts

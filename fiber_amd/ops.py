@@ -2055,6 +2055,81 @@ def nms_ml(boxes, scores, labels, source, nms_thresh, detections_per_img):
     return ob, osc, ol, osr, cnt
 
 
+def det_merge_max_candidates():
+    return int(lib.plain("fiber_det_merge_max_candidates"))
+
+
+DET_MERGE_MAX_CHUNKS, DET_MERGE_MAX_CANDIDATES = 64, 16384   # = det_merge_max_candidates(); the host path keeps the same bounds
+
+
+def _det_merge_host(boxes, scores, labels, source, count, label_table, N, out):
+    """fiber_det_merge on CPU tensors, in numpy (a stable sort of the live slots in chunk order, then slot order)"""
+    import numpy as np
+    bx, sc, lb, sr = boxes.detach().float().numpy(), scores.detach().float().numpy(), labels.numpy(), source.numpy()
+    cnt, tab = count.numpy(), label_table.numpy()
+    B, K, D = sc.shape
+    Cc = tab.shape[1]
+    ob, osc, ol, osr, och, ocnt = (t.numpy() for t in out)
+    ob[:], osc[:], ol[:], osr[:], och[:] = 0.0, -1.0, 0, -1, -1
+    for b in range(B):
+        live = np.arange(D)[None, :] < np.clip(cnt[b], 0, D)[:, None]
+        k, s = np.nonzero(live)                              # row-major: chunk order, then slot order
+        order = np.argsort(-sc[b, k, s].astype(np.float64), kind="stable")[:N]
+        k, s, n = k[order], s[order], len(order)
+        local = lb[b, k, s]
+        ok = (local >= 1) & (local <= Cc)
+        ob[b, :n], osc[b, :n], osr[b, :n], och[b, :n] = bx[b, k, s], sc[b, k, s], sr[b, k, s], k
+        ol[b, :n] = np.where(ok, tab[k, np.clip(local - 1, 0, Cc - 1)], 0) if Cc else 0
+        ocnt[b] = n
+    return out
+
+
+def det_merge(boxes, scores, labels, source, count, label_table, max_dets=None, out=None):
+    """Merge the K per-chunk results of each image into one ranked list (chunked open-vocabulary detection; lvis_eval.py:137-148's
+    sorted(.., reverse=True)[:max_dets] over the concatenation).  boxes fp32 [B, K, D, 4], scores fp32 [B, K, D], labels / source int32
+    [B, K, D], count int32 [B, K], label_table int32 [K, Cc] (chunk-local class -> output label).  CONTRACT: the first count[b, k] scores
+    of every (b, k) descend, which is how Detections come; the slots past count are ignored whatever they hold.
+    -> (boxes [B, N, 4], scores [B, N], labels [B, N], source [B, N], chunk [B, N], count [B]), N = K * D, or min(max_dets, K * D):
+    descending score, equal scores to the earlier chunk, then the earlier slot; labels = label_table[k, local - 1] (0 for a local label
+    outside 1..Cc), source unchanged, chunk = k; past count the padding of nms_ml and chunk -1.  One launch, no synchronisation; on CPU
+    tensors the same in numpy.  out: the six result tensors to write into (contiguous, of the result's shapes and dtypes)."""
+    if boxes.dim() != 4 or scores.dim() != 3:
+        raise ValueError(f"det_merge: boxes {tuple(boxes.shape)}, scores {tuple(scores.shape)}: [B, K, D, 4] and [B, K, D]")
+    B, K, D = scores.shape
+    if boxes.shape != (B, K, D, 4) or labels.shape != (B, K, D) or source.shape != (B, K, D) or count.shape != (B, K) or \
+            label_table.dim() != 2 or label_table.shape[0] != K:
+        raise ValueError(f"det_merge: boxes {tuple(boxes.shape)}, labels {tuple(labels.shape)}, source {tuple(source.shape)}, count "
+                         f"{tuple(count.shape)}, label_table {tuple(label_table.shape)} for scores {tuple(scores.shape)}")
+    if boxes.dtype != torch.float32 or scores.dtype != torch.float32 or labels.dtype != torch.int32 or source.dtype != torch.int32 or \
+            count.dtype != torch.int32 or label_table.dtype != torch.int32:
+        raise ValueError("det_merge: boxes / scores fp32, labels / source / count / label_table int32")
+    if K > DET_MERGE_MAX_CHUNKS or K * D > DET_MERGE_MAX_CANDIDATES:
+        raise ValueError(f"det_merge: {K} chunks x {D} slots exceed the merge kernel's capacity of {DET_MERGE_MAX_CHUNKS} chunks and "
+                         f"{DET_MERGE_MAX_CANDIDATES} candidates per image")
+    if max_dets is not None and int(max_dets) < 0:
+        raise ValueError(f"det_merge: max_dets {max_dets}")
+    dev = scores.device
+    if any(t.device != dev for t in (boxes, labels, source, count, label_table)):
+        raise ValueError("det_merge: the tensors lie on different devices")
+    N = K * D if max_dets is None else min(int(max_dets), K * D)
+    shapes = (((B, N, 4), torch.float32), ((B, N), torch.float32), ((B, N), torch.int32), ((B, N), torch.int32), ((B, N), torch.int32),
+              ((B,), torch.int32))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=dt, device=dev) for s, dt in shapes)      # the kernel writes every element
+    elif len(out) != 6 or any(t.shape != s or t.dtype != dt or t.device != dev or not t.is_contiguous() for t, (s, dt) in zip(out, shapes)):
+        raise ValueError(f"det_merge: out must be six contiguous tensors on {dev} of {shapes}")
+    if B == 0 or N == 0:                                     # nothing to rank: no launch
+        out[5].zero_()
+        return tuple(out)
+    if not scores.is_cuda:
+        return tuple(_det_merge_host(boxes, scores, labels, source, count, label_table, N, out))
+    ob, osc, ol, osr, och, ocnt = out
+    lib.call("fiber_det_merge", lib.ptr(_c(boxes)), lib.ptr(_c(scores)), lib.ptr(_c(labels)), lib.ptr(_c(source)), lib.ptr(_c(count)),
+             lib.ptr(_c(label_table)), lib.ptr(ob), lib.ptr(osc), lib.ptr(ol), lib.ptr(osr), lib.ptr(och), lib.ptr(ocnt), B, K, D,
+             int(label_table.shape[1]), N)
+    return ob, osc, ol, osr, och, ocnt
+
+
 # ---- grounding evaluation: recall@k of Detections against per-phrase ground truth (csrc/geval.hip) -----------------------------------
 def ground_recall(boxes, labels, count, gt, gt_count, cat_mask, topk, positives, totals, thresh, mode, num_categories=64):
     """One launch of fiber_ground_recall, no host synchronisation.  boxes fp32 [B, D, 4] in the original frame, labels int32 [B, D]

@@ -369,8 +369,23 @@ int fiber_ground_bwd_bf16(const void* X, const void* P, const float* tbias, cons
  * Only words on or right of the diagonal block are written.
  * fiber_det_nms_select replaces the host loop ml_nms.cu:122-140 and select_over_all_levels inference.py:717-738: walks each image's sorted
  * candidates, stops at D kept; out_boxes fp32 [B,D,4], out_scores [B,D] (-1 past count), out_labels, out_source int32 [B,D], out_count
- * int32 [B].  Deviation: the reference keeps every score >= the kthvalue cut, i.e. more than D on an exact tie at the cut. */
+ * int32 [B].  Deviation: the reference keeps every score >= the kthvalue cut, i.e. more than D on an exact tie at the cut.
+ * fiber_det_merge replaces, for chunked evaluation (TEST.CHUNKED_EVALUATION, engine/inference.py:483-575), the concatenation of an image's
+ * per-chunk results and data/datasets/evaluation/lvis/lvis_eval.py:137-148 (limit_dets_per_image: sorted(.., reverse=True)[:max_dets]).
+ * Inputs are K results per image as fiber_det_nms_select leaves them: boxes fp32 [B,K,D,4], scores fp32 [B,K,D] DESCENDING within each
+ * (b,k) over the first count[b,k] slots, labels (chunk-local, 1-based) / source int32 [B,K,D], count int32 [B,K] (clamped to [0,D]; the
+ * slots past it are not read as candidates), label_table int32 [K,Cc] (local class c of chunk k -> output label; a label outside 1..Cc
+ * reads nothing and yields 0).  Output [B,N,..], N <= K*D: the image's candidates in chunk order then slot order, sorted by descending
+ * score, stable (ties: the earlier chunk, then the earlier slot), cut to N; out_chunk int32 [B,N] holds k, out_source is carried
+ * unchanged, out_count int32 [B] = min(sum_k count, N); past it box 0, score -1, label 0, source -1, chunk -1.  Every output element
+ * is written.  One workgroup per image, the scores in LDS, each candidate's rank by binary searches, a plain scatter: no atomics.
+ * K > 64, K*D > fiber_det_merge_max_candidates(), N > K*D, N == 0 with work to do, NULL or misaligned pointers -> 1; B == 0 or
+ * K*D == 0 -> 0 without a launch.  NaN scores or lists that do not descend give an unspecified order, never an out-of-bounds access. */
 int fiber_det_max_candidates(void);
+int fiber_det_merge_max_candidates(void);
+int fiber_det_merge(const float* boxes, const float* scores, const int* labels, const int* source, const int* count,
+                    const int* label_table, float* out_boxes, float* out_scores, int* out_labels, int* out_source, int* out_chunk,
+                    int* out_count, int B, int K, int D, int Cc, int N, fiber_stream_t stream);
 int fiber_det_scores_f32(const float* logits, const float* centerness, const int* class_ptr, const int* tok_idx, float* out, int B, int A,
                          int T, int C, float pre_nms_thresh, int agg_max, fiber_stream_t stream);
 int fiber_det_scores_rows_f32(const float* logits, const float* centerness, const int* class_ptr, const int* tok_idx, float* out, int B,
