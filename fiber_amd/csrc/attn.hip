@@ -24,7 +24,7 @@
 //   pass B (wave = key strip):    dK, dV
 #include <stdlib.h>
 
-#include "common.h"
+#include "attn_frag.h"
 
 namespace {
 
@@ -51,8 +51,6 @@ struct AttnP {
   float p_drop; uint64_t seed; const uint64_t* seed_base;   // key = seed + *seed_base (seed_base nullable: hipGraph replay)
 };
 
-__device__ __forceinline__ int region_of(int x, int n, int ws, int shift) { return x < n - ws ? 0 : (x < n - shift ? 1 : 2); }
-
 // token row (in the [B*Hres*Wres] token-ordered tensors) and shift-mask region of window-local position i of window g
 __device__ __forceinline__ void window_tok(const AttnP& p, int g, int i, int& tok, int& reg) {
   const int b = g / p.nW, w = g - b * p.nW;
@@ -66,9 +64,6 @@ __device__ __forceinline__ void window_tok(const AttnP& p, int g, int i, int& to
   reg = p.shift > 0 ? region_of(R, p.Hres, p.ws, p.shift) * 3 + region_of(C, p.Wres, p.ws, p.shift) : 0;
 }
 
-__device__ __forceinline__ float group4_max(float v) { return rows4_max(v); }
-__device__ __forceinline__ float group4_sum(float v) { return rows4_sum(v); }
-
 // Head served by block y.  With head_dim 32 a head's slice of a token row is 64 B = half a cache line, and blocks y and y+1 (which
 // share every line) land on different XCDs when grid.x == 1 (linear block id = y + H*z, XCD = id % 8): each XCD's L2 then fetches
 // the whole line and the i2t kernels read 2 x their algorithmic bytes (PMC: 0.62 vs 0.30 GB forward).  Blocks y and y+8 share an
@@ -77,13 +72,6 @@ template <int D, bool WINDOW>
 __device__ __forceinline__ int head_of(int y, int H) {
   if (D == 32 && !WINDOW && gridDim.x == 1 && (H & 7) == 0) return (y & 7) * (H >> 3) + (y >> 3);
   return y;
-}
-
-__device__ __forceinline__ bf16x8 pack8(const f32x4& a, const f32x4& b) {
-  bf16x8 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { o[e] = f2bf(a[e]); o[4 + e] = f2bf(b[e]); }
-  return o;
 }
 
 // Stage `nrows` rows (row r of the chunk <-> global row rowmap[r]) of a [*, ld] bf16 matrix (head slice D wide) into a
@@ -118,22 +106,6 @@ __device__ __forceinline__ void stage(const bf16* __restrict__ src, int ld, int 
       if (idx < total) *reinterpret_cast<bf16x8*>(rm + r * (D + 16) + c * 8) = v[u];
     }
   }
-}
-
-// MFMA operand A = transposed fragment out of a ROW-MAJOR image: rows {t0*16+g*4..+3} U {t0*16+16+g*4..+3}, column d0 + l.
-// ds_read_b64_tr_b16 hands lane l of a 16-lane group column l of the 4x16 block whose (row l>>2, 4-column piece l&3)
-// address that lane supplies.
-template <int D>
-__device__ __forceinline__ bf16x8 trr_frag(const bf16* rm, int d0, int t0, int g, int l) {
-  typedef __attribute__((ext_vector_type(4))) short s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  const bf16* a = rm + (t0 * 16 + g * 4 + (l >> 2)) * (D + 16) + d0 + (l & 3) * 4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 16 * (D + 16)));
-  s16x8 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { o[e] = lo[e]; o[4 + e] = hi[e]; }
-  return __builtin_bit_cast(bf16x8, o);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -280,7 +252,7 @@ __global__ __launch_bounds__(768) void attn_fwd_kernel(AttnP p) {
         }
       }
     }
-    cmax = group4_max(cmax);
+    cmax = rows4_max(cmax);
     const float mnew = fmaxf(m, cmax);
     const float alpha = __builtin_amdgcn_exp2f(m - mnew);   // m = -inf on the first chunk -> 0
     m = mnew;
@@ -308,13 +280,13 @@ __global__ __launch_bounds__(768) void attn_fwd_kernel(AttnP p) {
         const bf16x8 pf = pack8(s[2 * t2], s[2 * t2 + 1]);
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
-          const bf16x8 vf = trr_frag<D>(Vs, dt * 16, 2 * t2, gq, lq);
+          const bf16x8 vf = trr_frag<D + 16>(Vs, dt * 16, 2 * t2, gq, lq);
           oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, oacc[dt], 0, 0, 0);   // O^T[d][query]
         }
       }
     }
   }
-  lsum = group4_sum(lsum);
+  lsum = rows4_sum(lsum);
   if (qvalid) {
     const float inv = 1.f / lsum;
 #pragma unroll
@@ -468,7 +440,7 @@ __global__ __launch_bounds__((WINDOW || NT > 6) ? 512 : 768) void attn_bwd_dq_ke
           const bf16x8 dsf = pack8(ds[0], ds[1]);
 #pragma unroll
           for (int dt = 0; dt < DT; ++dt) {
-            const bf16x8 ktf = trr_frag<D>(Ks, dt * 16, 2 * t2, gq, lq);
+            const bf16x8 ktf = trr_frag<D + 16>(Ks, dt * 16, 2 * t2, gq, lq);
             dqacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ktf, dsf, dqacc[dt], 0, 0, 0);   // dQ^T[d][query]
           }
         }
@@ -638,8 +610,8 @@ __global__ __launch_bounds__((!WINDOW && NT > 6 && D == 64) ? 512 : 768) void at
           const bf16x8 dsf = pack8(ds[0], ds[1]), pf = pack8(pd[0], pd[1]);
   #pragma unroll
           for (int dt = 0; dt < DT; ++dt) {
-            const bf16x8 qtf = trr_frag<D>(Qs, dt * 16, 2 * t2, gq, lq);
-            const bf16x8 dotf = trr_frag<D>(dOs, dt * 16, 2 * t2, gq, lq);
+            const bf16x8 qtf = trr_frag<D + 16>(Qs, dt * 16, 2 * t2, gq, lq);
+            const bf16x8 dotf = trr_frag<D + 16>(dOs, dt * 16, 2 * t2, gq, lq);
             dkacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qtf, dsf, dkacc[dt], 0, 0, 0);   // dK^T[d][key]
             dvacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dotf, pf, dvacc[dt], 0, 0, 0);   // dV^T[d][key]
           }

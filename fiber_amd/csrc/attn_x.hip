@@ -22,7 +22,7 @@
 //     at 4.2-5.5), and dQ leaves as 16-byte stores.
 // No barrier inside the strip loop.  Conditions (else the generic passes run): head_dim 32, Lk <= 48, Lq % 16 == 0, heads % 4 == 0, no
 // attention dropout (the reference applies none at this site).
-#include "common.h"
+#include "attn_frag.h"
 
 namespace {
 
@@ -37,35 +37,17 @@ struct XP {
   float scale;
 };
 
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ bf16x8 pack8(const f32x4& a, const f32x4& b) {
-  bf16x8 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { o[e] = f2bf(a[e]); o[4 + e] = f2bf(b[e]); }
-  return o;
-}
 __device__ __forceinline__ s16x4 pack4(const f32x4& a) {
   bf16x4 o;
 #pragma unroll
   for (int e = 0; e < 4; ++e) o[e] = f2bf(a[e]);
   return __builtin_bit_cast(s16x4, o);
 }
-// transposed MFMA operand out of a row-major [row][32] image: rows {t0*16 + g*4 ..+3} U {t0*16 + 16 + g*4 ..+3}, column d0 + l
-__device__ __forceinline__ bf16x8 trr_frag(const bf16* rm, int d0, int t0, int g, int l) {
-  const bf16* a = rm + (t0 * 16 + g * 4 + (l >> 2)) * XRS + d0 + (l & 3) * 4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 16 * XRS));
-  return __builtin_bit_cast(bf16x8, s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
-}
-// the same for ONE 16-row tile (K = 16 operand): [d0 + l][rows g*4 .. +3]
+// trr_frag<XRS> (attn_frag.h) for ONE 16-row tile (K = 16 operand): [d0 + l][rows g*4 .. +3]
 __device__ __forceinline__ s16x4 tr16(const bf16* rm, int d0, int g, int l) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(rm + (g * 4 + (l >> 2)) * XRS + d0 + (l & 3) * 4));
-}
-__device__ __forceinline__ f32x4 exp2x4(f32x4 a) {
-  return f32x4{__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1]), __builtin_amdgcn_exp2f(a[2]), __builtin_amdgcn_exp2f(a[3])};
 }
 // 16-byte row pieces out of the C layout of two 16x16 MFMAs (see win_attn.hip rows4_gather16)
 __device__ __forceinline__ u32x4 rows4_gather16(f32x4 a, f32x4 b) {
@@ -128,7 +110,7 @@ __global__ __launch_bounds__(512) void i2t_bwd_kernel(XP p) {
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-    for (int pr = 0; pr < 2; ++pr) ktf[dt][pr] = trr_frag(Kh, dt * 16, 2 * pr, gq, lq);
+    for (int pr = 0; pr < 2; ++pr) ktf[dt][pr] = trr_frag<XRS>(Kh, dt * 16, 2 * pr, gq, lq);
   // additive key mask in the log2 domain: lane = query form (keys kt*16 + gq*4 + r) and lane = key form (key kt*16 + lq); -inf past Lk
   f32x4 mkT[3];
   float mkS[3];
@@ -289,12 +271,6 @@ __device__ __forceinline__ s16x4 tr16s(const bf16* rm, int stride, int d0, int g
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(rm + (g * 4 + (l >> 2)) * stride + d0 + (l & 3) * 4));
 }
 
-template <typename T>
-__device__ __forceinline__ T* atx(T* base, unsigned elem_off) {        // wave-uniform 64-bit base + 32-bit per-lane offset (win_attn.hip at())
-  using C = std::conditional_t<std::is_const<T>::value, const char, char>;
-  return reinterpret_cast<T*>(reinterpret_cast<C*>(base) + elem_off * (unsigned)sizeof(T));
-}
-
 // CAUSAL (text decoder self-attention, Lq == Lk): key j > query i is masked.  A wave's key tile kt only meets query tiles qt >= kt: the tiles
 // above the diagonal get no MFMA and no softmax work, the diagonal tile masks per element.  The padding mask is clamped to a finite floor so
 // that a row whose keys of one tile are all padding (finfo.min * log2 e overflows to -inf) cannot produce exp2(-inf + inf).
@@ -373,8 +349,8 @@ __global__ __launch_bounds__(256, 2) void t2i_bwd_kernel(TP p) {
     const unsigned r = (unsigned)min(kt * 16 + lq, p.Lk - 1);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      kk[ks] = *reinterpret_cast<const bf16x8*>(atx(kbase, r * (unsigned)p.ldk + ks * 32));
-      vv[ks] = *reinterpret_cast<const bf16x8*>(atx(vbase, r * (unsigned)p.ldv + ks * 32));
+      kk[ks] = *reinterpret_cast<const bf16x8*>(at(kbase, r * (unsigned)p.ldk + ks * 32));
+      vv[ks] = *reinterpret_cast<const bf16x8*>(at(vbase, r * (unsigned)p.ldv + ks * 32));
     }
   };
   u32x4 wk[2], wv[2];                                    // the previous tile's dK / dV rows (16 bytes per lane and half)
@@ -383,8 +359,8 @@ __global__ __launch_bounds__(256, 2) void t2i_bwd_kernel(TP p) {
     if (key < p.Lk) {
 #pragma unroll
       for (int hp = 0; hp < 2; ++hp) {
-        *reinterpret_cast<u32x4*>(atx(dkbase, (unsigned)key * (unsigned)p.lddk + hp * 32)) = wk[hp];
-        *reinterpret_cast<u32x4*>(atx(dvbase, (unsigned)key * (unsigned)p.lddv + hp * 32)) = wv[hp];
+        *reinterpret_cast<u32x4*>(at(dkbase, (unsigned)key * (unsigned)p.lddk + hp * 32)) = wk[hp];
+        *reinterpret_cast<u32x4*>(at(dvbase, (unsigned)key * (unsigned)p.lddv + hp * 32)) = wv[hp];
       }
     }
   };
@@ -557,8 +533,8 @@ __global__ __launch_bounds__(256, 3) void t2i_fwd_kernel(FP p) {
     const unsigned r = (unsigned)min(kt * 16 + lq, p.Lk - 1);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      kk[ks] = *reinterpret_cast<const bf16x8*>(atx(kbase, r * (unsigned)p.ldk + ks * 32));
-      vv[ks] = *reinterpret_cast<const bf16x8*>(atx(vbase, r * (unsigned)p.ldv + ks * 32));
+      kk[ks] = *reinterpret_cast<const bf16x8*>(at(kbase, r * (unsigned)p.ldk + ks * 32));
+      vv[ks] = *reinterpret_cast<const bf16x8*>(at(vbase, r * (unsigned)p.ldv + ks * 32));
     }
   };
   if (wave < ntiles) request(wave);
@@ -719,7 +695,7 @@ __global__ __launch_bounds__(512, 3) void i2t_fwd_kernel(XF p) {
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-    for (int pr = 0; pr < 2; ++pr) vtf[dt][pr] = trr_frag(Vh, dt * 16, 2 * pr, gq, lq);
+    for (int pr = 0; pr < 2; ++pr) vtf[dt][pr] = trr_frag<XRS>(Vh, dt * 16, 2 * pr, gq, lq);
   f32x4 mkT[3];                                          // additive key mask in the log2 domain (keys kt*16 + gq*4 + r), -inf past Lk
 #pragma unroll
   for (int kt = 0; kt < 3; ++kt) mkT[kt] = *reinterpret_cast<const f32x4*>(mkl + kt * 16 + gq * 4);
@@ -735,7 +711,7 @@ __global__ __launch_bounds__(512, 3) void i2t_fwd_kernel(XF p) {
 #pragma unroll
     for (int kt = 0; kt < 3; ++kt) st[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr[kt], qf, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
-    qreg = *reinterpret_cast<const bf16x8*>(atx(qbase, (unsigned)((s_next < nstrips ? s_next : s_) * 16 + lq) * (unsigned)p.ldq));
+    qreg = *reinterpret_cast<const bf16x8*>(at(qbase, (unsigned)((s_next < nstrips ? s_next : s_) * 16 + lq) * (unsigned)p.ldq));
     __builtin_amdgcn_sched_barrier(0);
     f32x4 sv[3];
     float mx = -INFINITY;
@@ -757,11 +733,11 @@ __global__ __launch_bounds__(512, 3) void i2t_fwd_kernel(XF p) {
       oT[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vtf[dt][1], p2, oT[dt], 0, 0, 0);
     }
     const float inv = 1.f / sum;
-    *reinterpret_cast<u32x4*>(atx(obase, (unsigned)(s_ * 16 + lq) * (unsigned)p.ldo)) = rows4_gather16(oT[0] * inv, oT[1] * inv);
+    *reinterpret_cast<u32x4*>(at(obase, (unsigned)(s_ * 16 + lq) * (unsigned)p.ldo)) = rows4_gather16(oT[0] * inv, oT[1] * inv);
     if (gq == 0 && p.lse) p.lse[((size_t)b * p.Lq + s_ * 16 + lq) * p.H + h] = mx * 0.6931471805599453f + __logf(sum);
   };
-  if (half < nstrips) qa = *reinterpret_cast<const bf16x8*>(atx(qbase, (unsigned)(half * 16 + lq) * (unsigned)p.ldq));
-  if (half + 2 < nstrips) qb = *reinterpret_cast<const bf16x8*>(atx(qbase, (unsigned)((half + 2) * 16 + lq) * (unsigned)p.ldq));
+  if (half < nstrips) qa = *reinterpret_cast<const bf16x8*>(at(qbase, (unsigned)(half * 16 + lq) * (unsigned)p.ldq));
+  if (half + 2 < nstrips) qb = *reinterpret_cast<const bf16x8*>(at(qbase, (unsigned)((half + 2) * 16 + lq) * (unsigned)p.ldq));
   for (int s_ = half; s_ < nstrips; s_ += 4) {
     strip(s_, qa, s_ + 4);
     if (s_ + 2 < nstrips) strip(s_ + 2, qb, s_ + 6);

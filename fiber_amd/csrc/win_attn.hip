@@ -18,9 +18,9 @@
 // all windows the workgroup visits; pass B (wave = key strip) -> dK, dV.
 #include <stdlib.h>
 
-#include <type_traits>
+#include <algorithm>
 
-#include "common.h"
+#include "attn_frag.h"
 
 namespace {
 
@@ -56,30 +56,7 @@ __device__ __forceinline__ int chan_q(const WinP& p, int h) { return p.hmajor ==
 __device__ __forceinline__ int chan_k(const WinP& p, int h) { return p.hmajor == 1 ? h * 96 + 32 : p.hmajor == 2 ? p.C + h * 64 : p.C + h * 32; }
 __device__ __forceinline__ int chan_v(const WinP& p, int h) { return p.hmajor == 1 ? h * 96 + 64 : p.hmajor == 2 ? p.C + h * 64 + 32 : 2 * p.C + h * 32; }
 
-__device__ __forceinline__ int region_of(int x, int n, int ws, int shift) { return x < n - ws ? 0 : (x < n - shift ? 1 : 2); }
-__device__ __forceinline__ float g4max(float v) { return rows4_max(v); }
-__device__ __forceinline__ float g4sum(float v) { return rows4_sum(v); }
-__device__ __forceinline__ bf16x8 pack8(const f32x4& a, const f32x4& b) {
-  bf16x8 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { o[e] = f2bf(a[e]); o[4 + e] = f2bf(b[e]); }
-  return o;
-}
-// MFMA operand A (transposed fragment) out of a ROW-MAJOR [token][32] image (row stride RS): rows {t0*16+g*4..+3} U
-// {t0*16+16+g*4..+3}, column d0 + l.  ds_read_b64_tr_b16 hands lane l of a 16-lane group column l of the 4x16 block whose
-// (row l>>2, 4-column piece l&3) address that lane supplies, so a transposed copy of the image never has to be written
-// (8 ds_write_b16 per staged chunk less).
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-__device__ __forceinline__ bf16x8 trr_frag(const bf16* rm, int d0, int t0, int g, int l) {
-  const bf16* a = rm + (t0 * 16 + g * 4 + (l >> 2)) * RS + d0 + (l & 3) * 4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 16 * RS));
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  s16x8 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { o[e] = lo[e]; o[4 + e] = hi[e]; }
-  return __builtin_bit_cast(bf16x8, o);
-}
+// (pack8, zero8, exp2x4, region_of, at() and the transposed MFMA operand trr_frag<RS> out of a row-major image: attn_frag.h)
 // max of three without the canonicalising v_max_f32 x, x that fmaxf() drags in for every operand (inputs are never sNaN here)
 __device__ __forceinline__ float max3(float a, float b, float c) {
   float r;
@@ -90,28 +67,12 @@ __device__ __forceinline__ float max3(float a, float b, float c) {
 // (the SLP vectoriser otherwise pairs lanes (1,2) and pays v_alignbit/v_perm shuffles before every pack)
 __device__ __forceinline__ f32x4 fma4(f32x4 a, float b, f32x4 c) { return __builtin_elementwise_fma(a, f32x4{b, b, b, b}, c); }
 __device__ __forceinline__ f32x4 fma4(f32x4 a, float b, float c) { return __builtin_elementwise_fma(a, f32x4{b, b, b, b}, f32x4{c, c, c, c}); }
-__device__ __forceinline__ f32x4 exp2x4(f32x4 a) {
-  return f32x4{__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1]), __builtin_amdgcn_exp2f(a[2]), __builtin_amdgcn_exp2f(a[3])};
-}
 // shift-mask term: -100 (natural-log logits) on keys of another shift region, as arithmetic on the integer-valued float region labels:
 // pen * min((region_a - region_b)^2, 1) is 0 when equal and exactly pen otherwise.  (Swin's mask is additive -100, not -inf: where the
 // scores span more than 100 the masked keys keep weight, and (region_a - region_b)^2 alone -- up to 64 -- gave them too little.)
 __device__ __forceinline__ f32x4 region_mask(f32x4 sv, f32x4 ra, float rb, float pen) {
   const f32x4 d = ra - rb;
   return __builtin_elementwise_fma(__builtin_elementwise_min(d * d, f32x4{1.f, 1.f, 1.f, 1.f}), f32x4{pen, pen, pen, pen}, sv);
-}
-__device__ __forceinline__ bf16x8 zero8() {
-  bf16x8 z;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) z[e] = f2bf(0.f);
-  return z;
-}
-
-// uniform base pointer + 32-bit BYTE offset: the form the backend turns into `global_load/store v, voff, s[base:base+1]`
-template <typename T>
-__device__ __forceinline__ T* at(T* base, unsigned elem_off) {
-  using C = std::conditional_t<std::is_const<T>::value, const char, char>;
-  return reinterpret_cast<T*>(reinterpret_cast<C*>(base) + elem_off * (unsigned)sizeof(T));
 }
 
 // window g, window-local (pr,pc) -> token row of the [B*H*W] tensors and shift-mask region label
@@ -148,6 +109,14 @@ struct Smem {
   int* koff; int* kreg; float* btab; float* lse; float* dlt;
   bf16* a0; bf16* a1;
 };
+// Dynamic LDS of every kernel below = carve_bytes() + what the kernel itself appends; each kernel's total is stated once, as a
+// constexpr function next to the kernel's own pointer arithmetic, and win_plan() asks for exactly that.
+// bytes of carve(): four MAXN-entry tables and the bias column of nb = (2ws-1)^2 entries (padded to 16 bytes), then n_rm images
+template <int MTT>
+__host__ __device__ constexpr size_t carve_bytes(int nb, int n_rm) {
+  WIN_DIMS(MTT);
+  return (size_t)(4 * MAXN + ((nb + 3) & ~3)) * 4 + (size_t)n_rm * MAXN * RS * 2;
+}
 template <int MTT>
 __device__ __forceinline__ Smem carve(char* base, int nb, int n_rm) {
   WIN_DIMS(MTT);
@@ -157,16 +126,16 @@ __device__ __forceinline__ Smem carve(char* base, int nb, int n_rm) {
   S.lse = reinterpret_cast<float*>(S.kreg + MAXN);
   S.dlt = S.lse + MAXN;
   S.btab = S.dlt + MAXN;
-  bf16* img = reinterpret_cast<bf16*>(base + (size_t)(4 * MAXN + ((nb + 3) & ~3)) * 4);
+  bf16* img = reinterpret_cast<bf16*>(base + carve_bytes<MTT>(nb, 0));
   S.a0 = img; img += (n_rm > 0) * MAXN * RS;
   S.a1 = img; img += (n_rm > 1) * MAXN * RS;
   return S;
 }
-template <int MTT>
-size_t smem_bytes(int nb, int n_rm) {
-  WIN_DIMS(MTT);
-  return (size_t)(4 * MAXN + ((nb + 3) & ~3)) * 4 + (size_t)n_rm * MAXN * RS * 2;
-}
+// Threads a MAXC form is built for: 160 rows x 4 sixteen-byte pieces staged as one chunk per thread (MAXC = 1: 10 waves), or 21 x 16
+// rows as three chunks per thread of a 7-wave strip group (MAXC = 3).  It is the __launch_bounds__ of the form (the run-time-tile-count
+// dQ pass alone is bounded lower, DQ_BOUND) and the stride of the per-thread LDS slots of colsum_zero / colsum_flush and the dQ pass.
+template <int MAXC>
+constexpr int WIN_NTH = MAXC == 1 ? 640 : 448;
 
 // Column sums of a backward pass's outputs (the bias gradient of the qkv linear), produced where the values already are instead
 // of by a second pass over dqkv: each lane adds its 4-channel pieces into private LDS slots once per window (ds_read_b128 +
@@ -174,7 +143,7 @@ size_t smem_bytes(int nb, int n_rm) {
 // whole backward), and at the end of the kernel 32 threads per 32-channel group sum the slots over waves and the 16 query /
 // key lanes and write one fp32 row per workgroup; a fold kernel adds the rows.  Thread t = wave*64 + g*16 + l owns channels
 // dt*16 + g*4 + 0..3 of query / key l; slot(piece k = grp*2 + dt, thread t) = slots[k * NTH + t] (f32x4), NTH = the kernel's
-// launch bound: lane-contiguous (conflict-free) and one address register + immediate offsets.
+// WIN_NTH<MAXC>: lane-contiguous (conflict-free) and one address register + immediate offsets.
 template <int NV, int NTH>
 __device__ __forceinline__ void colsum_zero(f32x4* slots) {
 #pragma unroll
@@ -218,8 +187,10 @@ __device__ __forceinline__ void setup(const WinP& p, const Smem& S, int h, int n
 // ================================================================ forward =====================================
 // MAXC: 16-byte staging chunks per thread; NTC: key/query tiles if known at compile time (9 for 12x12 windows);
 // MTT: tile capacity (10 / 21); BREG: window-invariant bias slice in registers (else LDS look-ups per score)
+template <int MTT>
+constexpr size_t fwd_lds_bytes(int nb) { return carve_bytes<MTT>(nb, 2); }   // tables + the K and V images
 template <int MAXC, int NTC = 0, int MTT = 10, bool BREG = true>
-__global__ __launch_bounds__(MAXC == 1 ? 640 : 448) void win_fwd_kernel(WinP p) {
+__global__ __launch_bounds__(WIN_NTH<MAXC>) void win_fwd_kernel(WinP p) {
   WIN_DIMS(MTT);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nb = (2 * p.ws - 1) * (2 * p.ws - 1);
@@ -380,7 +351,7 @@ __global__ __launch_bounds__(MAXC == 1 ? 640 : 448) void win_fwd_kernel(WinP p) 
 #pragma unroll
       for (int t2 = 0; t2 < VE; ++t2)
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) vf[t2][dt] = trr_frag(Vs, dt * 16, 2 * t2, gq, lq);
+        for (int dt = 0; dt < 2; ++dt) vf[t2][dt] = trr_frag<RS>(Vs, dt * 16, 2 * t2, gq, lq);
       __builtin_amdgcn_sched_barrier(0);
       // VALU diet (a plain VALU op is ~4.3 cycles per wave-instruction on a SIMD, v_exp_f32 / v_rcp_f32 8.4): the softmax works on
       // t = q.k + bias/scale straight out of the MFMA; p = exp2(t * scale*log2e - max) is ONE packed fma + exp2 per score.
@@ -396,7 +367,7 @@ __global__ __launch_bounds__(MAXC == 1 ? 640 : 448) void win_fwd_kernel(WinP p) 
 #pragma unroll
       for (int kt = 0; kt < MT; ++kt)
         if (kt < ntile) { m0 = max3(m0, s[kt][0], s[kt][1]); m1 = max3(m1, s[kt][2], s[kt][3]); }
-      mx = g4max(max3(m0, m1, m1));
+      mx = rows4_max(max3(m0, m1, m1));
       const float nm = -mx * scale2;
       float s0 = 0.f, s1 = 0.f;
 #pragma unroll
@@ -411,12 +382,12 @@ __global__ __launch_bounds__(MAXC == 1 ? 640 : 448) void win_fwd_kernel(WinP p) 
           s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
       }
-      sum = g4sum(s0 + s1);
+      sum = rows4_sum(s0 + s1);
 #pragma unroll
       for (int t2 = 0; t2 < MTP / 2; ++t2) {
         if (t2 + VE < MTP / 2) {                           // keep VE pairs of V^T fragments ahead of the PV MFMAs
 #pragma unroll
-          for (int dt = 0; dt < 2; ++dt) vf[t2 + VE][dt] = trr_frag(Vs, dt * 16, 2 * (t2 + VE), gq, lq);
+          for (int dt = 0; dt < 2; ++dt) vf[t2 + VE][dt] = trr_frag<RS>(Vs, dt * 16, 2 * (t2 + VE), gq, lq);
           __builtin_amdgcn_sched_barrier(0);
         }
         if (t2 * 2 < ntile) {
@@ -455,10 +426,20 @@ __global__ __launch_bounds__(MAXC == 1 ? 640 : 448) void win_fwd_kernel(WinP p) 
 // MTT: tile capacity (10 / 21); BREG: window-invariant bias slice in registers (else LDS look-ups per score)
 // The run-time-tile-count instance (NTC = 0, MAXC = 1: windows of at most 128 tokens, e.g. the 7 x 7 windows of Swin-T) is bounded at 8 waves:
 // under the 10-wave bound's 168 registers it left 92 bytes of scratch per lane.  NTH stays the slot stride of the LDS column-sum slots.
+template <int MAXC, int NTC>
+constexpr int DQ_BOUND = (MAXC == 1 && !NTC) ? 512 : WIN_NTH<MAXC>;
+template <int MTT>
+constexpr int DQ_NLD = MTT > 10 ? 8 : 0;                  // dbias tiles kept in LDS slots (see the kernel), in front of the column-sum slots
+constexpr int DQ_NV = 2;                                  // column-sum pieces per thread: two 16-channel halves of dQ
+// tables + K and V images, then f32x4 slots: [BREG: bias slab nw x MT x 64][DQ_NLD x NTH dbias tiles][colsum: DQ_NV x NTH]
+template <int MAXC, int MTT, bool BREG>
+constexpr size_t dq_lds_bytes(int nb, int nw, bool colsum) {
+  return carve_bytes<MTT>(nb, 2) + ((size_t)(BREG ? nw * MTT * 64 : 0) + DQ_NLD<MTT> * WIN_NTH<MAXC> + (colsum ? DQ_NV * WIN_NTH<MAXC> : 0)) * sizeof(f32x4);
+}
 template <int MAXC, int NTC = 0, int MTT = 10, bool BREG = true>
-__global__ __launch_bounds__(MAXC == 1 ? (NTC ? 640 : 512) : 448) void win_bwd_dq_kernel(WinP p) {
+__global__ __launch_bounds__((DQ_BOUND<MAXC, NTC>)) void win_bwd_dq_kernel(WinP p) {
   WIN_DIMS(MTT);
-  constexpr int NTH = MAXC == 1 ? 640 : 448;
+  constexpr int NTH = WIN_NTH<MAXC>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nb = (2 * p.ws - 1) * (2 * p.ws - 1);
   Smem S = carve<MTT>(smem, nb, 2);
@@ -492,9 +473,9 @@ __global__ __launch_bounds__(MAXC == 1 ? (NTC ? 640 : 512) : 448) void win_bwd_d
   // nothing for keeping LDS operands in flight.
   f32x4* slab = reinterpret_cast<f32x4*>(S.a1 + MAXN * RS) + wave * MT * 64 + lane;
   // column-sum slots of this kernel's dQ values (after the bias slab when there is one)
-  constexpr int NLD = MTT > 10 ? 8 : 0;                   // dbias tiles kept in LDS slots (see below), in front of the column-sum slots
+  constexpr int NLD = DQ_NLD<MTT>;                        // dbias tiles kept in LDS slots (see below), in front of the column-sum slots
   f32x4* cs_all = reinterpret_cast<f32x4*>(S.a1 + MAXN * RS) + (BREG ? (blockDim.x >> 6) * MT * 64 : 0) + NLD * NTH;
-  if (p.colsum_part) colsum_zero<2, NTH>(cs_all);
+  if (p.colsum_part) colsum_zero<DQ_NV, NTH>(cs_all);
   // dbias accumulators: one f32x4 per key tile and lane, summed over the windows of the run.  With 21 tiles (18 x 18 windows) 84 registers
   // of them left 156 bytes of scratch per lane; the first NLD tiles live in private LDS slots instead (ds_read_b128 + add + ds_write_b128
   // on the thread's own slot, lane-contiguous), in front of the column-sum slots.
@@ -577,7 +558,7 @@ __global__ __launch_bounds__(MAXC == 1 ? (NTC ? 640 : 512) : 448) void win_bwd_d
 #pragma unroll
     for (int e = 0; e < 8; e += 2)
       dpart = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, bf16x2{don[e], don[e + 1]}), __builtin_bit_cast(bf16x2_t, bf16x2{on[e], on[e + 1]}), dpart, false);
-    const float dlt = g4sum(dpart);
+    const float dlt = rows4_sum(dpart);
     const unsigned opix = qpix;
     const size_t oimg = qimg;
     if (gq == 0 && qval) *at(p.delta + oimg * p.heads + (size_t)h * p.Hres * p.Wres, opix) = dlt;
@@ -627,7 +608,7 @@ __global__ __launch_bounds__(MAXC == 1 ? (NTC ? 640 : 512) : 448) void win_bwd_d
             __builtin_amdgcn_sched_barrier(0);
             mfmas(0); mfmas(1);
 #pragma unroll
-            for (int dt = 0; dt < 2; ++dt) kt_[dt] = trr_frag(Ks, dt * 16, 2 * t2, gq, lq);   // lands during the VALU pass
+            for (int dt = 0; dt < 2; ++dt) kt_[dt] = trr_frag<RS>(Ks, dt * 16, 2 * t2, gq, lq);   // lands during the VALU pass
             __builtin_amdgcn_sched_barrier(0);
             valu(0); valu(1);
           } else {
@@ -637,7 +618,7 @@ __global__ __launch_bounds__(MAXC == 1 ? (NTC ? 640 : 512) : 448) void win_bwd_d
           const bf16x8 dsf = pack8(ds[0], ds[1]);
 #pragma unroll
           for (int dt = 0; dt < 2; ++dt) {
-            if constexpr (!PIPE) kt_[dt] = trr_frag(Ks, dt * 16, 2 * t2, gq, lq);
+            if constexpr (!PIPE) kt_[dt] = trr_frag<RS>(Ks, dt * 16, 2 * t2, gq, lq);
             dqacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt_[dt], dsf, dqacc[dt], 0, 0, 0);
           }
         }
@@ -671,23 +652,29 @@ __global__ __launch_bounds__(MAXC == 1 ? (NTC ? 640 : 512) : 448) void win_bwd_d
   }
   if (p.colsum_part) {
     const int chan0[1] = {qo};
-    colsum_flush<2, NTH>(cs_all, p.colsum_part + (size_t)(blockIdx.x * gridDim.z + blockIdx.z) * 3 * C, chan0);
+    colsum_flush<DQ_NV, NTH>(cs_all, p.colsum_part + (size_t)(blockIdx.x * gridDim.z + blockIdx.z) * 3 * C, chan0);
   }
 }
 
 // ================================================================ backward pass B: dK, dV ======================
 // MAXC: 16-byte staging chunks per thread; NTC: key/query tiles if known at compile time (9 for 12x12 windows);
 // MTT: tile capacity (10 / 21); BREG: window-invariant bias slice in registers (else LDS look-ups per score)
+constexpr int DKV_NV = 4;                                 // column-sum pieces per thread: two 16-channel halves of dK and of dV
+// tables + Q and dO images, then the column-sum slots [DKV_NV x NTH] f32x4
+template <int MAXC, int MTT>
+constexpr size_t dkv_lds_bytes(int nb, bool colsum) {
+  return carve_bytes<MTT>(nb, 2) + (size_t)(colsum ? DKV_NV * WIN_NTH<MAXC> : 0) * sizeof(f32x4);
+}
 template <int MAXC, int NTC = 0, int MTT = 10, bool BREG = true>
-__global__ __launch_bounds__(MAXC == 1 ? 640 : 448) void win_bwd_dkv_kernel(WinP p) {
+__global__ __launch_bounds__(WIN_NTH<MAXC>) void win_bwd_dkv_kernel(WinP p) {
   WIN_DIMS(MTT);
-  constexpr int NTH = MAXC == 1 ? 640 : 448;
+  constexpr int NTH = WIN_NTH<MAXC>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nb = (2 * p.ws - 1) * (2 * p.ws - 1);
   Smem S = carve<MTT>(smem, nb, 2);
   bf16* Qs = S.a0; bf16* dOs = S.a1;
   f32x4* cs_all = reinterpret_cast<f32x4*>(S.a1 + MAXN * RS);   // column-sum slots of dK / dV (see colsum_flush)
-  if (p.colsum_part) colsum_zero<4, NTH>(cs_all);
+  if (p.colsum_part) colsum_zero<DKV_NV, NTH>(cs_all);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int gq = lane >> 4, lq = lane & 15;
   const int h = blockIdx.y, C = p.C, ld = 3 * C;
@@ -819,8 +806,8 @@ __global__ __launch_bounds__(MAXC == 1 ? 640 : 448) void win_bwd_dkv_kernel(WinP
           }
 #pragma unroll
           for (int dt = 0; dt < 2; ++dt) {                   // transposed operands of the dK / dV MFMAs land during the VALU pass
-            qt[dt] = trr_frag(Qs, dt * 16, 2 * t2, gq, lq);
-            dt_[dt] = trr_frag(dOs, dt * 16, 2 * t2, gq, lq);
+            qt[dt] = trr_frag<RS>(Qs, dt * 16, 2 * t2, gq, lq);
+            dt_[dt] = trr_frag<RS>(dOs, dt * 16, 2 * t2, gq, lq);
           }
           __builtin_amdgcn_sched_barrier(0);
           f32x4 ds[2], pd[2];
@@ -865,7 +852,7 @@ __global__ __launch_bounds__(MAXC == 1 ? 640 : 448) void win_bwd_dkv_kernel(WinP
   }
   if (p.colsum_part) {
     const int chan0[2] = {ko, vo};
-    colsum_flush<4, NTH>(cs_all, p.colsum_part + (size_t)(blockIdx.x * gridDim.z + blockIdx.z) * 3 * C, chan0);
+    colsum_flush<DKV_NV, NTH>(cs_all, p.colsum_part + (size_t)(blockIdx.x * gridDim.z + blockIdx.z) * 3 * C, chan0);
   }
 }
 
@@ -876,7 +863,7 @@ __global__ __launch_bounds__(MAXC == 1 ? 640 : 448) void win_bwd_dkv_kernel(WinP
 //           dK, dV of the strip complete in registers; dS is ALSO what dbias accumulates (registers, over the windows of the run)
 //           and is written -- transposed, bf16 -- into an LDS image DSt[key][query] (one ds_write_b64 per query tile);
 //   phase 2 (wave = query strip, after one barrier): dQ^T = K^T . dS^T, ten MFMAs per window whose B operand is read back from
-//           DSt with ds_read_b64_tr_b16 (the same fragment trr_frag() builds for K^T: both operands see the same key order).
+//           DSt with ds_read_b64_tr_b16 (the same fragment trr_frag<RS>() builds for K^T: both operands see the same key order).
 // delta = rowsum(dO . O) is formed while staging (the four lanes that stage a row hold its four chunks of dO and O).
 // LDS: tables 4.7 KB + Q, dO, K images (160 rows: tile 9 stays zero) 46 KB + DSt 144 x 352 B = 50.7 KB + column-sum slots 55 KB.
 // Row stride of DSt: 88 dwords = 24 mod 64, the stride class the transposed read is conflict-free for (see RS above).
@@ -900,9 +887,22 @@ __device__ __forceinline__ bf16x8 trr_frag_lohi(const bf16* lo_img, int lo_strid
 // Key strip 8 is cut by QUERY tiles into three helper waves 8 / 9 / 10 (SIMDs 0 / 1 / 2: 21 / 21 / 21 / 18 tile steps per SIMD instead of
 // 27 / 18 / 18 / 18).  Waves 8 and 9 hand their partial dK / dV of the strip to wave 10 through two LDS slots; wave 10, idle in phase 2,
 // adds them in a fixed order and stores the strip.  Waves 9 and 10 have no query strip (phase 2) and stage nothing.
+namespace fused {
+constexpr int N = 144, MT = N / 16, MAXN = 160, NST = N * 4;   // 12x12 windows: 9 strips of 16, images padded to 10 tiles; NST staging threads
+constexpr int NL = 5;                                    // dbias tiles kept in LDS slots [tile][staging thread]; tiles NL .. 8 stay in registers
+constexpr int NV = 6;                                    // column-sum pieces per (wave, lane group): dQ | dK | dV x two 16-channel halves
+template <int NWV>
+constexpr int PSLOTS = NWV == 11 ? 2 * 4 * 64 : 0;       // helper form: [helper wave 8 | 9][4 accumulators][lane]
+}  // namespace fused
+// tables, the Q / dO / K images and DSt[key][query], then f32x4 slots: [NL x NST dbias tiles][NWV x 4 x NV column sums][PSLOTS]
+template <int NWV>
+constexpr size_t fused_lds_bytes(int nb) {
+  using namespace fused;
+  return carve_bytes<10>(nb, 0) + (size_t)3 * MAXN * RS * 2 + (size_t)N * DSS * 2 + (size_t)(NL * NST + NWV * 4 * NV + PSLOTS<NWV>) * sizeof(f32x4);
+}
 template <bool SHIFT, int NWV = 9>
 __global__ __launch_bounds__(NWV * 64) void win_bwd_fused_kernel(WinP p) {
-  constexpr int MT = 9, MAXN = 160, NTH = NWV * 64, NST = 576;   // 12x12 windows: 9 strips of 16, images padded to 10 tiles; NST staging threads
+  constexpr int MT = fused::MT, MAXN = fused::MAXN, NTH = NWV * 64, NST = fused::NST;
   constexpr bool HELP = NWV == 11;
   static_assert(NWV == 9 || NWV == 11, "9 waves, or 8 + 3 helpers of key strip 8");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -912,12 +912,12 @@ __global__ __launch_bounds__(NWV * 64) void win_bwd_fused_kernel(WinP p) {
   // dbias accumulators of query tiles 0 .. NL-1: private LDS slots [tile][thread] (read + add + write per window, conflict-free);
   // tiles NL .. 8 stay in registers.  All nine in registers put the kernel 17-36 registers over its 168-register cap (scratch
   // traffic: shifted stage-2 backward 1820 us against 1330 without spills).
-  constexpr int NL = 5;
-  f32x4* db_lds = reinterpret_cast<f32x4*>(DSt + 144 * DSS);
+  constexpr int NL = fused::NL;
+  f32x4* db_lds = reinterpret_cast<f32x4*>(DSt + fused::N * DSS);
   // column sums of dQ | dK | dV (the qkv bias gradient): reduced over the 16 key / query lanes in registers (the kernel is not
   // VALU-bound), then one f32x4 per (wave, lane group, piece) in LDS: [wave][gq][6]
   f32x4* cs_small = db_lds + NL * NST;
-  f32x4* pslot = cs_small + NWV * 4 * 6;                 // HELP: partial dK | dV of key strip 8, [helper wave 8 | 9][4 accumulators][lane]
+  f32x4* pslot = cs_small + NWV * 4 * fused::NV;                // HELP: partial dK | dV of key strip 8, [helper wave 8 | 9][4 accumulators][lane]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool helper = HELP && wave >= 8;                 // (wave-uniform)
   // A helper runs the code of tiles 6, 7, 8 (first of a pair, second of a pair, alone; register accumulators 1 .. 3) on its query tiles
@@ -939,7 +939,7 @@ __global__ __launch_bounds__(NWV * 64) void win_bwd_fused_kernel(WinP p) {
     uint32_t* z = reinterpret_cast<uint32_t*>(Qs);
     for (int t = tid; t < 3 * MAXN * RS / 2; t += NTH) z[t] = 0u;
   }
-  for (int t = tid; t < NL * NST + NWV * 4 * 6; t += NTH) db_lds[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = tid; t < NL * NST + NWV * 4 * fused::NV; t += NTH) db_lds[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   // staging chunk of this thread: row sr of the window, 16-byte piece sc (576 threads = 144 rows x 4 pieces exactly)
   const int sr = tid >> 2, sc = tid & 3;
   const int spr = sr / p.ws, spc = sr - spr * p.ws;
@@ -972,7 +972,7 @@ __global__ __launch_bounds__(NWV * 64) void win_bwd_fused_kernel(WinP p) {
     }
     return v;
   };
-  f32x4* cs_mine = cs_small + (wave * 4 + gq) * 6;
+  f32x4* cs_mine = cs_small + (wave * 4 + gq) * fused::NV;
   const int* koff_b = S.koff + trb * 16 + gq * 4;
   auto bias_tile = [&](int qt) -> f32x4 {                 // (the tile's base offset is re-read as well: nine more registers do not exist)
     const float* b = S.btab + koff_b[qt * 16] + kconst;
@@ -1094,14 +1094,14 @@ __global__ __launch_bounds__(NWV * 64) void win_bwd_fused_kernel(WinP p) {
         bf16x8 qt2[2], dt2[2];
         if constexpr (PAIR_END) {
 #pragma unroll
-          for (int dt = 0; dt < 2; ++dt) { qt2[dt] = trr_frag(Qb, dt * 16, qi - 1, gq, lq); dt2[dt] = trr_frag(dOb, dt * 16, qi - 1, gq, lq); }
+          for (int dt = 0; dt < 2; ++dt) { qt2[dt] = trr_frag<RS>(Qb, dt * 16, qi - 1, gq, lq); dt2[dt] = trr_frag<RS>(dOb, dt * 16, qi - 1, gq, lq); }
         } else if constexpr (ALONE) {
           // Q^T / dO^T of this tile and of the image rows behind it (tile 8: the all-zero, never staged rows 144..159; a helper's lone tile:
           // the next tile's rows, finite, against the zero half of dS / P): the lone tile runs as a K = 32 MFMA whose upper half is zero.  NOT the K = 16 opcode (round 5): a 16x16x16 MFMA that takes the D of a 16x16x32 MFMA as
           // its C is padded by hipcc like an accumulate chain of ONE opcode (one wait state) and can read the accumulator before the
           // K = 32 instruction has written it -- seen in a forward kernel as row sums of "last tile + stale registers".
 #pragma unroll
-          for (int dt = 0; dt < 2; ++dt) { qt2[dt] = trr_frag(Qb, dt * 16, qi, gq, lq); dt2[dt] = trr_frag(dOb, dt * 16, qi, gq, lq); }
+          for (int dt = 0; dt < 2; ++dt) { qt2[dt] = trr_frag<RS>(Qb, dt * 16, qi, gq, lq); dt2[dt] = trr_frag<RS>(dOb, dt * 16, qi, gq, lq); }
         }
         f32x4 sv = fma4(sa, scale * 1.4426950408889634f, bq);
         if constexpr (BORDER) sv = region_mask(sv, qg, kregf_own, -144.26950408889634f);
@@ -1196,7 +1196,7 @@ __global__ __launch_bounds__(NWV * 64) void win_bwd_fused_kernel(WinP p) {
                                 : trr_frag_lohi(lo, DSS, Ks + 144 * RS, RS, gq, lq);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
-        const bf16x8 kt_ = trr_frag(Ks, dt * 16, 2 * t2, gq, lq);
+        const bf16x8 kt_ = trr_frag<RS>(Ks, dt * 16, 2 * t2, gq, lq);
         dqacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt_, dsb, dqacc[dt], 0, 0, 0);
       }
     }
@@ -1298,63 +1298,128 @@ __global__ __launch_bounds__(256) void win_dbias_gather_kernel(const float* __re
   if (lane == 0) dtable[(size_t)e * H + h] = s;
 }
 
-bool attrs_set[16] = {};
-void ensure_attrs() {
-  if (!fiber_first_on_device(attrs_set)) return;
-  const int big = 160 * 1024;
-  hipFuncSetAttribute((const void*)win_fwd_kernel<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)win_bwd_dq_kernel<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)win_bwd_dkv_kernel<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)win_fwd_kernel<1, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)win_fwd_kernel<3, 0, 21, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)win_bwd_dq_kernel<3, 0, 21, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)win_bwd_dkv_kernel<3, 0, 21, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)win_bwd_fused_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)win_bwd_fused_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)win_bwd_fused_kernel<false, 11>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  hipFuncSetAttribute((const void*)win_bwd_fused_kernel<true, 11>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+// ===================================================== dispatch ================================================
+// win_plan() decides everything about the launches of one pass, each quantity once; fiber_win_fwd_launch / fiber_win_bwd_launch fill WinP
+// and launch what the plan says.  Plain arithmetic: no HIP call, no environment.
+enum WinPass { WIN_FWD, WIN_BWD };
+enum WinForm {             // the instantiations that exist
+  WIN_NONE,
+  FWD_10, FWD_12, FWD_21,                     // win_fwd_kernel<1, 0> | <1, 9> | <3, 0, 21, false>
+  DQ_10, DQ_21, DKV_10, DKV_21,               // win_bwd_dq_kernel / win_bwd_dkv_kernel<1, 0> | <3, 0, 21, false>
+  FUSED_9, FUSED_9S, FUSED_11, FUSED_11S,     // win_bwd_fused_kernel<shift > 0, 9 | 11>
+};
+struct WinPlan {
+  int rc;                  // FIBER_EINVAL: no form serves these arguments (the rest is not to be used then)
+  WinForm form, form2;     // first launch; backward: the dK/dV pass that follows the dQ pass (WIN_NONE after the one-pass kernel)
+  size_t lds, lds2;        // dynamic LDS bytes of the two
+  int nw, sg;              // waves per workgroup (block = 64 nw); strip groups of nw waves a window is cut into (grid z)
+  int gpb, gx;             // WinP.gpb: windows per run; runs (grid x) = slices of the partial bias gradient the backward writes
+  // backward: win_dbias_fold_kernel over fold_n float4 (else win_dbias_fold1_kernel over fold_n floats), the gather's workgroups, and the rows
+  // of the column-sum workspace handed to fiber_fold_rows_f32 (0: no column sums)
+  bool fold4; long fold_n; int gather_blocks, colsum_rows;
+};
+
+// N <= WIN_SMALL_N: one workgroup per (window run, head) with one wave per 16-query strip: each thread stages exactly one 16-byte
+// chunk (MAXC = 1).  A split into <=4-wave strip groups (MAXC = 3, several workgroups per CU) measured no faster.
+// WIN_SMALL_N < N <= WIN_MAX_N (18x18 windows: 21 strips): strip groups of 7 waves, each staging the whole window (MAXC = 3).
+constexpr int WIN_SMALL_N = 160, WIN_MAX_N = 336, WIN_BIG_WAVES = WIN_NTH<3> / 64;
+int win_strip_groups(int N) { return N <= WIN_SMALL_N ? 1 : cdiv(cdiv(N, 16), WIN_BIG_WAVES); }
+
+// Windows per run when G windows are shared out among the workgroups of one (head, strip group), hsg = heads * strip groups of them.
+// One 9-wave workgroup fits per CU.  One round of 256 workgroups (256/heads window runs per head) when there are few heads:
+// rocprof ablation showed ~45 % of the kernel was per-workgroup setup (bias column, key offsets, LDS clear, bias-slice
+// gather) + per-window geometry when 768 short-lived workgroups ran in 3 rounds.  From 8 heads on (stages 1-3: fewer windows
+// per run, so the end of the single round is ragged) two rounds of half-length runs measured 3-8 % faster
+// (tools/op_bench.py 512 attn: stage 2 forward 399 -> 368 us, backward 1790 -> 1716 us; stage 0 backward 5880 -> 5966 us).
+// (The lower clamp needs hsg > 512, which no model has; it keeps the division below defined.)
+int win_gpb(int G, int hsg) { return cdiv(G, std::min(std::max((hsg >= 8 ? 512 : 256) / hsg, 1), G)); }
+int win_runs(int G, int hsg) { return G < 1 ? 0 : cdiv(G, win_gpb(G, hsg)); }
+
+// helpers: the 11-wave form of the one-pass backward (FIBER_WIN_BWD_WAVES=11: key strip 8 on three helper waves)
+WinPlan win_plan(WinPass pass, int G, int heads, int ws, int shift, int hmajor, bool colsum, bool helpers) {
+  WinPlan a{};
+  a.rc = FIBER_EINVAL;
+  const int N = ws * ws, nb = (2 * ws - 1) * (2 * ws - 1);
+  const bool big = N > WIN_SMALL_N, w12 = N == fused::N;
+  // channel layouts 0..2 everywhere; the planar probe layouts 3 / 4 exist only in the 12 x 12 forward and one-pass backward
+  if (G < 1 || heads < 1 || N < 1 || N > WIN_MAX_N || hmajor < 0 || hmajor > 4 || (hmajor >= 3 && !w12)) return a;
+  a.sg = win_strip_groups(N);
+  a.nw = big ? WIN_BIG_WAVES : cdiv(N, 16);
+  a.gpb = win_gpb(G, heads * a.sg);                      // about one workgroup per CU in total
+  a.gx = cdiv(G, a.gpb);
+  int bound;                                             // __launch_bounds__ of the form(s)
+  if (pass == WIN_FWD) {
+    // compile-time tile count for 12x12 windows (NTC = 9): forward 1828 -> 1542 us at 512 images, stage 0, when it was introduced.  (The
+    // two-pass dQ kernel could not afford it while its bias slice lived in registers -- 168-VGPR cap, spills inside the window loop:
+    // backward 7441 -> 8837 us; 12x12 windows now take the one-pass backward.)
+    a.form = big ? FWD_21 : w12 ? FWD_12 : FWD_10;
+    a.lds = big ? fwd_lds_bytes<21>(nb) : fwd_lds_bytes<10>(nb);
+    bound = big ? WIN_NTH<3> : WIN_NTH<1>;
+  } else if (w12) {
+    // 12x12 windows: one pass (delta_ws stays unused).  The two-pass instances with the compile-time tile count carried 8 / 24 bytes of
+    // scratch and are not built.
+    a.nw = helpers ? 11 : 9;
+    a.form = helpers ? (shift > 0 ? FUSED_11S : FUSED_11) : (shift > 0 ? FUSED_9S : FUSED_9);
+    a.lds = helpers ? fused_lds_bytes<11>(nb) : fused_lds_bytes<9>(nb);
+    bound = 64 * a.nw;
+  } else {
+    // (delta[query, head] = sum_d dO*O is produced by the dQ pass itself and read back by the dK/dV pass)
+    a.form = big ? DQ_21 : DQ_10;
+    a.form2 = big ? DKV_21 : DKV_10;
+    a.lds = big ? dq_lds_bytes<3, 21, false>(nb, a.nw, colsum) : dq_lds_bytes<1, 10, true>(nb, a.nw, colsum);   // (big: 150 KB in all)
+    a.lds2 = big ? dkv_lds_bytes<3, 21>(nb, colsum) : dkv_lds_bytes<1, 10>(nb, colsum);
+    bound = big ? DQ_BOUND<3, 0> : DQ_BOUND<1, 0>;       // (the dK/dV forms' is no lower)
+  }
+  // Never taken for a square window: N <= 121 below 12 x 12 is at most 8 waves.  It states that a form is not launched above its bound.
+  if (64 * a.nw > bound) return a;
+  if (pass == WIN_BWD) {
+    const long n = (long)heads * N * N;
+    a.fold4 = n % 4 == 0;                                // (odd windows: slices are not float4-sized)
+    a.fold_n = a.fold4 ? n / 4 : n;
+    a.gather_blocks = cdiv(nb * heads, 4);
+    a.colsum_rows = colsum ? a.gx * a.sg : 0;
+  }
+  a.rc = FIBER_OK;
+  return a;
 }
 
-// waves per workgroup / strip groups of the three passes
-void strip_geometry(int N, int& nw, int& sg) {
-  // N <= 160: one workgroup per (window run, head) with one wave per 16-query strip: each thread stages exactly one 16-byte
-  // chunk (MAXC = 1).  A split into <=4-wave strip groups (MAXC = 3, several workgroups per CU) measured no faster.
-  // 160 < N <= 336 (18x18 windows: 21 strips): strip groups of 7 waves, each staging the whole window (MAXC = 3).
-  if (N <= 160) { nw = cdiv(N, 16); sg = 1; }
-  else { nw = 7; sg = cdiv(cdiv(N, 16), 7); }
-}
-
-// which kernels use the compile-time tile count for 12x12 windows (bit 0 forward, 1 dQ pass, 2 dK/dV pass; FIBER_WIN_NTC).
-// Forward 1828 -> 1542 us at 512 images, stage 0, when it was introduced.  The dQ pass could not afford it while its bias slice
-// lived in registers (168-VGPR cap, spills inside the window loop: backward 7441 -> 8837 us); with the slice in an LDS slab all
-// three passes use it.
-int ntc_mask() {
-  static const int m = getenv("FIBER_WIN_NTC") ? atoi(getenv("FIBER_WIN_NTC")) : 7;
-  return m;
-}
-
-int blocks_for(int G, int heads) {
-  // One 9-wave workgroup fits per CU.  One round of 256 workgroups (256/heads window runs per head) when there are few heads:
-  // rocprof ablation showed ~45 % of the kernel was per-workgroup setup (bias column, key offsets, LDS clear, bias-slice
-  // gather) + per-window geometry when 768 short-lived workgroups ran in 3 rounds.  From 8 heads on (stages 1-3: fewer windows
-  // per run, so the end of the single round is ragged) two rounds of half-length runs measured 3-8 % faster
-  // (tools/op_bench.py 512 attn: stage 2 forward 399 -> 368 us, backward 1790 -> 1716 us; stage 0 backward 5880 -> 5966 us).
-  static const int forced = getenv("FIBER_WIN_BLOCKS") ? atoi(getenv("FIBER_WIN_BLOCKS")) : 0;
-  const int per = forced > 0 ? forced : (heads >= 8 ? 512 : 256);
-  int nz = per / heads;
-  nz = nz < 1 ? 1 : nz;
-  return nz > G ? G : nz;
-}
-
-bool big_window(int N) { return N > 160; }
-// bias-table gradient from the per-workgroup-run partials [nz, H, N, N] (slice 0 is overwritten with the sum)
-int dbias_fold_gather(float* part, float* dtable, int nz, int H, int ws, hipStream_t st) {
-  const int N = ws * ws, W2 = 2 * ws - 1;
-  const long n = (long)H * N * N, n4 = n / 4;
-  if (n % 4 == 0) hipLaunchKernelGGL(win_dbias_fold_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, part, nz, n4);
-  else hipLaunchKernelGGL(win_dbias_fold1_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, nz, n);   // (odd windows: slices are not float4-sized)
+// Launch K as the plan says.  A form's dynamic-LDS limit is raised here, on the function that is about to be launched, the first time a
+// device launches it with more than the default limit.
+using WinKernel = void (*)(WinP);
+template <WinKernel K>
+int launch_as(const WinP& p, const WinPlan& a, size_t lds, hipStream_t st) {
+  static bool raised[16] = {};
+  if (lds > 64 * 1024 && fiber_first_on_device(raised))
+    hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipLaunchKernelGGL(K, dim3(a.gx, p.heads, a.sg), dim3(64 * a.nw), lds, st, p);
   FIBER_CHECK_LAUNCH();
-  hipLaunchKernelGGL(win_dbias_gather_kernel, dim3((unsigned)((W2 * W2 * H + 3) / 4)), dim3(256), 0, st, part, dtable, H, ws);
+  return FIBER_OK;
+}
+int launch_form(WinForm f, const WinP& p, const WinPlan& a, size_t lds, hipStream_t st) {
+  switch (f) {
+    case FWD_10: return launch_as<win_fwd_kernel<1, 0>>(p, a, lds, st);
+    case FWD_12: return launch_as<win_fwd_kernel<1, 9>>(p, a, lds, st);
+    case FWD_21: return launch_as<win_fwd_kernel<3, 0, 21, false>>(p, a, lds, st);
+    case DQ_10: return launch_as<win_bwd_dq_kernel<1, 0>>(p, a, lds, st);
+    case DQ_21: return launch_as<win_bwd_dq_kernel<3, 0, 21, false>>(p, a, lds, st);
+    case DKV_10: return launch_as<win_bwd_dkv_kernel<1, 0>>(p, a, lds, st);
+    case DKV_21: return launch_as<win_bwd_dkv_kernel<3, 0, 21, false>>(p, a, lds, st);
+    case FUSED_9: return launch_as<win_bwd_fused_kernel<false>>(p, a, lds, st);
+    case FUSED_9S: return launch_as<win_bwd_fused_kernel<true>>(p, a, lds, st);
+    case FUSED_11: return launch_as<win_bwd_fused_kernel<false, 11>>(p, a, lds, st);
+    case FUSED_11S: return launch_as<win_bwd_fused_kernel<true, 11>>(p, a, lds, st);
+    case WIN_NONE: break;
+  }
+  return FIBER_EINVAL;
+}
+
+// bias-table gradient from the per-run partials [gx, H, N, N] (slice 0 is overwritten with the sum)
+int dbias_fold_gather(float* part, float* dtable, const WinPlan& a, int H, int ws, hipStream_t st) {
+  const dim3 grid((unsigned)((a.fold_n + 255) / 256));
+  if (a.fold4) hipLaunchKernelGGL(win_dbias_fold_kernel, grid, dim3(256), 0, st, part, a.gx, a.fold_n);
+  else hipLaunchKernelGGL(win_dbias_fold1_kernel, grid, dim3(256), 0, st, part, a.gx, a.fold_n);
+  FIBER_CHECK_LAUNCH();
+  hipLaunchKernelGGL(win_dbias_gather_kernel, dim3(a.gather_blocks), dim3(256), 0, st, part, dtable, H, ws);
   FIBER_CHECK_LAUNCH();
   return FIBER_OK;
 }
@@ -1365,10 +1430,6 @@ WinP make(const void* qkv, int B, int Hres, int Wres, int C, int heads, int ws, 
   p.B = B; p.Hres = Hres; p.Wres = Wres; p.C = C; p.heads = heads; p.ws = ws; p.shift = shift;
   p.hmajor = hmajor;
   p.nWw = Wres / ws; p.nWh = Hres / ws; p.nW = p.nWw * p.nWh; p.G = B * p.nW; p.N = ws * ws;
-  int nw, sg;
-  strip_geometry(p.N, nw, sg);
-  const int nz = blocks_for(p.G, heads * sg);            // about one workgroup per CU in total
-  p.gpb = cdiv(p.G, nz);
   return p;
 }
 
@@ -1379,77 +1440,38 @@ namespace {
 #endif
 }  // namespace
 
-// Used by attn.hip's C entry points when the window fits the specialised path (head_dim 32, N <= 160).
+// Used by attn.hip's C entry points when the window fits the specialised path (head_dim 32, N <= WIN_MAX_N).
 int fiber_win_fwd_launch(const void* qkv, const float* bias_table, void* o, float* lse, int B, int Hres, int Wres, int C,
                          int heads, int ws, int shift, int hmajor, hipStream_t st) {
-  // channel layouts 0..2 everywhere; the planar probe layouts 3 / 4 exist only in the 12 x 12 forward and fused backward
-  if (hmajor < 0 || hmajor > 4 || (hmajor >= 3 && ws * ws != 144)) return FIBER_EINVAL;
-  ensure_attrs();
   WinP p = make(qkv, B, Hres, Wres, C, heads, ws, shift, hmajor);
-  p.o = (bf16*)o; p.lse = lse; p.bias_table = bias_table;
-  const int nb = (2 * ws - 1) * (2 * ws - 1);
-  int nw, sg;
-  strip_geometry(p.N, nw, sg);
-  if (big_window(p.N)) hipLaunchKernelGGL((win_fwd_kernel<3, 0, 21, false>), dim3(cdiv(p.G, p.gpb), heads, sg), dim3(64 * nw), smem_bytes<21>(nb, 2), st, p);
-  else if (p.N == 144 && (ntc_mask() & 1)) hipLaunchKernelGGL((win_fwd_kernel<1, 9>), dim3(cdiv(p.G, p.gpb), heads, sg), dim3(64 * nw), smem_bytes<10>(nb, 2), st, p);
-  else hipLaunchKernelGGL((win_fwd_kernel<1, 0>), dim3(cdiv(p.G, p.gpb), heads, sg), dim3(64 * nw), smem_bytes<10>(nb, 2), st, p);
-  FIBER_CHECK_LAUNCH();
-  return FIBER_OK;
+  const WinPlan a = win_plan(WIN_FWD, p.G, heads, ws, shift, hmajor, false, false);
+  if (a.rc) return a.rc;
+  p.gpb = a.gpb; p.o = (bf16*)o; p.lse = lse; p.bias_table = bias_table;
+  return launch_form(a.form, p, a, a.lds, st);
 }
 
-int fiber_win_bwd_slices(int n_windows, int heads) {
-  const int nz = blocks_for(n_windows, heads);
-  return cdiv(n_windows, cdiv(n_windows, nz));
-}
-
-int fiber_win_colsum_rows(int n_windows, int heads, int N) {
-  int nw, sg;
-  strip_geometry(N, nw, sg);
-  return fiber_win_bwd_slices(n_windows, heads) * sg;
-}
+// Workspace sizes of the backward.  Both are stated for one strip group (hsg = heads), the launch runs sg of them per head: its
+// gx = win_runs(G, heads * sg) <= win_runs(G, heads), because (512 or 256) / hsg does not grow with hsg (256 / heads >= 512 / (heads * sg) for
+// sg >= 2), so windows per run do not shrink and runs do not increase.  For 18 x 18 windows (sg = 3) the workspaces are therefore larger than the
+// launch needs; the sizes are part of the ABI and stay.
+int fiber_win_bwd_slices(int n_windows, int heads) { return win_runs(n_windows, heads); }
+int fiber_win_colsum_rows(int n_windows, int heads, int N) { return win_runs(n_windows, heads) * win_strip_groups(N); }
 
 extern "C" int fiber_fold_rows_f32(const float* part, float* out, int rows, int N, hipStream_t stream);
 
 int fiber_win_bwd_launch(const void* qkv, const float* bias_table, const void* o, const void* dout, const float* lse,
                          void* dqkv, float* dbias_table, float* delta_ws, float* dbias_ws, float* dqkv_colsum, float* colsum_ws,
                          int B, int Hres, int Wres, int C, int heads, int ws, int shift, int hmajor, hipStream_t st) {
-  if (hmajor < 0 || hmajor > 4 || (hmajor >= 3 && ws * ws != 144)) return FIBER_EINVAL;
-  ensure_attrs();
-  WinP p = make(qkv, B, Hres, Wres, C, heads, ws, shift, hmajor);
-  p.o = (bf16*)o; p.lse = (float*)lse; p.bias_table = bias_table; p.dout = (const bf16*)dout; p.dqkv = (bf16*)dqkv;
-  p.delta = delta_ws; p.dbias_part = dbias_ws; p.colsum_part = colsum_ws;
-  const int nb = (2 * ws - 1) * (2 * ws - 1);
-  int nw, sg;
-  strip_geometry(p.N, nw, sg);
-  // (delta[query, head] = sum_d dO*O is produced by the dQ pass itself and read back by the dK/dV pass)
-  const int gz = cdiv(p.G, p.gpb);
-  const size_t slab = (size_t)nw * 10 * 64 * sizeof(float) * 4;   // dQ pass: per-lane bias slices [wave][tile][lane] x f32x4
-  const size_t nth = big_window(p.N) ? 448 : 640;        // launch bounds = slot stride of the column-sum slots
-  const size_t csq = colsum_ws ? nth * 2 * 16 : 0, cskv = colsum_ws ? nth * 4 * 16 : 0;
+  static const bool helpers = getenv("FIBER_WIN_BWD_WAVES") && atoi(getenv("FIBER_WIN_BWD_WAVES")) == 11;
   if ((colsum_ws == nullptr) != (dqkv_colsum == nullptr)) return FIBER_EINVAL;
-  if (p.N == 144 && sg == 1) {                           // 12x12 windows: one pass (delta_ws stays unused).  The two-pass instances for this
-    // size (round 3's A/B switch FIBER_WIN_FUSED=0) carried 8 / 24 bytes of scratch and are no longer built.
-    static const int nwv = getenv("FIBER_WIN_BWD_WAVES") ? atoi(getenv("FIBER_WIN_BWD_WAVES")) : 9;   // 11: key strip 8 on three helper waves
-    const size_t bytes = (size_t)(4 * 160 + ((nb + 3) & ~3)) * 4 + (size_t)3 * 160 * RS * 2 + (size_t)144 * DSS * 2 +
-                         (size_t)(5 * 576 + (nwv == 11 ? 11 * 4 * 6 + 2 * 4 * 64 : 9 * 4 * 6)) * 16;
-    if (nwv == 11) {
-      if (shift > 0) hipLaunchKernelGGL((win_bwd_fused_kernel<true, 11>), dim3(gz, heads, 1), dim3(704), bytes, st, p);
-      else hipLaunchKernelGGL((win_bwd_fused_kernel<false, 11>), dim3(gz, heads, 1), dim3(704), bytes, st, p);
-    } else if (shift > 0) hipLaunchKernelGGL(win_bwd_fused_kernel<true>, dim3(gz, heads, 1), dim3(576), bytes, st, p);
-    else hipLaunchKernelGGL(win_bwd_fused_kernel<false>, dim3(gz, heads, 1), dim3(576), bytes, st, p);
-    FIBER_CHECK_LAUNCH();
-    if (int rc = dbias_fold_gather(dbias_ws, dbias_table, gz, heads, ws, st)) return rc;
-    if (colsum_ws) return fiber_fold_rows_f32(colsum_ws, dqkv_colsum, gz, 3 * C, st);
-    return FIBER_OK;
-  }
-  if (big_window(p.N)) hipLaunchKernelGGL((win_bwd_dq_kernel<3, 0, 21, false>), dim3(gz, heads, sg), dim3(64 * nw), smem_bytes<21>(nb, 2) + csq + 8 * 448 * 16, st, p);   // (+ the 8 dbias tiles kept in LDS: 150 KB in all)
-  else if (nw > 8) return FIBER_EINVAL;                  // (N = ws * ws: no square window has 129..160 tokens other than 12 x 12)
-  else hipLaunchKernelGGL((win_bwd_dq_kernel<1, 0>), dim3(gz, heads, sg), dim3(64 * nw), smem_bytes<10>(nb, 2) + slab + csq, st, p);
-  FIBER_CHECK_LAUNCH();
-  if (int rc = dbias_fold_gather(dbias_ws, dbias_table, gz, heads, ws, st)) return rc;
-  if (big_window(p.N)) hipLaunchKernelGGL((win_bwd_dkv_kernel<3, 0, 21, false>), dim3(gz, heads, sg), dim3(64 * nw), smem_bytes<21>(nb, 2) + cskv, st, p);
-  else hipLaunchKernelGGL((win_bwd_dkv_kernel<1, 0>), dim3(gz, heads, sg), dim3(64 * nw), smem_bytes<10>(nb, 2) + cskv, st, p);
-  FIBER_CHECK_LAUNCH();
-  if (colsum_ws) return fiber_fold_rows_f32(colsum_ws, dqkv_colsum, gz * sg, 3 * C, st);
-  return FIBER_OK;
+  WinP p = make(qkv, B, Hres, Wres, C, heads, ws, shift, hmajor);
+  const WinPlan a = win_plan(WIN_BWD, p.G, heads, ws, shift, hmajor, colsum_ws != nullptr, helpers);
+  if (a.rc) return a.rc;
+  p.gpb = a.gpb; p.o = (bf16*)o; p.lse = (float*)lse; p.bias_table = bias_table; p.dout = (const bf16*)dout; p.dqkv = (bf16*)dqkv;
+  p.delta = delta_ws; p.dbias_part = dbias_ws; p.colsum_part = colsum_ws;
+  if (int rc = launch_form(a.form, p, a, a.lds, st)) return rc;
+  if (int rc = dbias_fold_gather(dbias_ws, dbias_table, a, heads, ws, st)) return rc;
+  if (a.form2 != WIN_NONE)
+    if (int rc = launch_form(a.form2, p, a, a.lds2, st)) return rc;
+  return a.colsum_rows ? fiber_fold_rows_f32(colsum_ws, dqkv_colsum, a.colsum_rows, 3 * C, st) : FIBER_OK;
 }

@@ -1106,7 +1106,7 @@ def window_attention(qkv, bias_table, B, H, W, heads, ws, shift, head_major=Fals
 
 
 def head_major_supported(ws):
-    """The specialised window kernels (N = ws*ws <= 160) accept the head-major qkv layout."""
+    """The one-chunk window kernels (N = ws*ws <= 160, WIN_SMALL_N of csrc/win_attn.hip's win_plan()) are the sizes the model runs head-major."""
     return ws * ws <= 160
 
 

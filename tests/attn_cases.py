@@ -4,12 +4,13 @@ the forward and the backward must launch.  Shared by tests/test_hip_attn_paths.p
 tools/probes/attn_paths.py (which kernels each case actually launched).  Also: the fp64 reference and its per-element bounds,
 used on the GPU by the path tests and on the host by tests/test_attn_compare_host.py.
 
-Selection, as read from the dispatch (win_attn.hip fiber_win_*_launch; attn_x.hip fiber_*_launch, which alone decide whether a one-pass
-kernel serves a call -- attn.hip's mha_fwd / mha_bwd add only the head_dim and, for i2t, "no dropout"; attn.hip attn_plan() and
-launch_fwd / launch_dq / launch_dkv for the generic kernels):
-  window, N = ws*ws <= 160, N != 144   win_fwd_kernel<1, 0>, win_bwd_dq / dkv_kernel<1, 0>; dbias fold (fold1 when heads*N*N is odd)
+Selection, as read from the dispatch (win_attn.hip win_plan(), one per pass, whose form launch_form() maps to a template; attn_x.hip
+fiber_*_launch, which alone decide whether a one-pass kernel serves a call -- attn.hip's mha_fwd / mha_bwd add only the head_dim and,
+for i2t, "no dropout"; attn.hip attn_plan() and launch_fwd / launch_dq / launch_dkv for the generic kernels):
+  window, N = ws*ws <= 160, N != 144   win_fwd_kernel<1, 0>, win_bwd_dq / dkv_kernel<1, 0>; dbias fold (fold1 when heads*N*N % 4 != 0)
   window, N == 144                      win_fwd_kernel<1, 9>, win_bwd_fused_kernel<shift > 0>
   window, 160 < N <= 336                win_fwd_kernel<3, 0, 21, false>, win_bwd_dq / dkv_kernel<3, 0, 21, false>
+  (every window form: runs of ceil(G / min(G, (256, from 8 heads * strip groups on 512) / (heads * strip groups))) windows per workgroup)
   window, N > 336                       attn_fwd_kernel<32, true>, attn_delta_kernel, attn_bwd_dq / dkv_kernel<32, true>, dbias_scatter
   mha, D = 32, Lk <= 48, no dropout     i2t_fwd_kernel if Lq % 16 == 0 and heads % 4 == 0; i2t_bwd_kernel if also lddq % 8 == 0
   mha, D = 64, Lq <= 48, Lk <= 1024     t2i_fwd_kernel<DROP>, t2i_bwd_kernel<DROP> (all leading dimensions % 8 == 0)
@@ -88,6 +89,7 @@ for nm, B, H, W, h, ws, s, lays in [
     # rectangular padded grid; shifted single-window grids; ragged last window run (G not a multiple of gpb)
     ("w12rect", 1, 24, 36, 4, 12, 6, (0,)), ("w12one", 2, 12, 12, 2, 12, 6, (0,)), ("w7one", 2, 7, 7, 2, 7, 3, (0,)),
     ("w12rag", 33, 24, 24, 16, 12, 6, (0,)), ("w7rag", 35, 14, 14, 4, 7, 3, (0,)), ("w18rag", 33, 18, 18, 16, 18, 0, (0,)),
+    ("w7rag8", 1, 63, 63, 8, 7, 3, (0,)),      # the two-pass kernels at >= 8 heads: 81 windows in 41 runs of two, the last run one window
     ("w18bench", 8, 18, 18, 32, 18, 0, (0,)),                                         # the bench's stage 3 at 576^2 (Swin-B, 32 heads)
 ]:
     for lay in lays:

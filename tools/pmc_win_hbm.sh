@@ -1,6 +1,6 @@
 #!/bin/bash
 # Kernel durations + HBM bytes of the window-attention kernels (tools/op_bench.py 512 attn, head-major layout).
-# usage (GPU box): bash tools/pmc_win_hbm.sh [tag]  -> gpurun_out/win_hbm_<tag>.txt      env FIBER_WIN_FUSED=0|1 selects the backward
+# usage (GPU box): bash tools/pmc_win_hbm.sh [tag]  -> win_hbm_<tag>.txt in the output directory ($out below)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 tag=${1:-run}
 out=gpurun_out/win_hbm_$tag.txt
