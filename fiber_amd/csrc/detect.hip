@@ -271,7 +271,205 @@ __global__ __launch_bounds__(MRG_THREADS) void det_merge_kernel(const float* __r
   if (tid == 0) ocount[b] = kept;
 }
 
+// ---- multi-scale test-time augmentation (data/datasets/evaluation/box_aug.py) -----------------------------------------------------------
+constexpr int AUG_THREADS = 256;
+constexpr int AUG_MAX_T = 1 << 20;         // candidates per image over all views (24 views x SEL_MAX_N = 393216 fit)
+constexpr int AUG_DEAD_LABEL = 1 << 30;    // the label dead slots are sorted under: behind every class
+
+struct AugView {                           // one record per image and view (32 bytes)
+  float scaled_w;                          // width of the resized image (the frame the candidates are in)
+  float ratio_w, ratio_h;                  // original / resized, computed in double, rounded to fp32
+  int equal_ratio;                         // BoxList.resize's first branch: ratio_w on all four coordinates
+  int flip;
+  int has_range;
+  float min2, max2;                        // the squares of TEST.RANGES' pair
+};
+
+// first index of the ascending list l[0, n) that is >= v
+__device__ __forceinline__ int aug_lower_bound(const int* __restrict__ l, int n, int v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (l[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// is `label` in the ascending table?
+__device__ __forceinline__ bool aug_allowed(const int* __restrict__ classes, int C, int label) {
+  const int at = aug_lower_bound(classes, C, label);
+  return at < C && classes[at] == label;
+}
+
+// One thread per candidate of one view: un-flip in the scaled frame (BoxList.transpose), remove_boxes' strict area test there, then
+// BoxList.resize to the original frame; every slot [off, off + Nv) of the image's concatenated buffers is written.
+__global__ __launch_bounds__(AUG_THREADS) void det_aug_collect_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                                      const int* __restrict__ labels, const int* __restrict__ source,
+                                                                      const AugView* __restrict__ table, const int* __restrict__ classes,
+                                                                      float* __restrict__ oboxes, float* __restrict__ oscores,
+                                                                      int* __restrict__ olabels, int* __restrict__ osource,
+                                                                      int* __restrict__ oview, int Nv, int T, int off, int view, int C) {
+  const int n = blockIdx.x * AUG_THREADS + threadIdx.x, b = blockIdx.y;
+  if (n >= Nv) return;
+  const size_t src = (size_t)b * Nv + n, dst = (size_t)b * T + off + n;
+  const AugView p = table[b];
+  f32x4 box = *reinterpret_cast<const f32x4*>(boxes + src * 4);
+  const float sc = scores[src];
+  const int lab = labels[src];
+  bool live = sc >= 0.f && aug_allowed(classes, C, lab);
+  if (p.flip) {
+    const float x1 = p.scaled_w - box[2] - 1.f, x2 = p.scaled_w - box[0] - 1.f;
+    box[0] = x1;
+    box[2] = x2;
+  }
+  if (p.has_range) {
+    const float w = box[2] - box[0] + 1.f, h = box[3] - box[1] + 1.f;
+    const float area = w * h;
+    live = live && area > p.min2 && area < p.max2;
+  }
+  const float ry = p.equal_ratio ? p.ratio_w : p.ratio_h;
+  box[0] = box[0] * p.ratio_w;
+  box[1] = box[1] * ry;
+  box[2] = box[2] * p.ratio_w;
+  box[3] = box[3] * ry;
+  *reinterpret_cast<f32x4*>(oboxes + dst * 4) = live ? box : f32x4{0.f, 0.f, 0.f, 0.f};
+  oscores[dst] = live ? sc : -1.f;
+  olabels[dst] = live ? lab : 0;
+  osource[dst] = live ? source[src] : -1;
+  oview[dst] = live ? view : -1;
+}
+
+// One workgroup per (class-table entry, image) over candidates sorted by (label ascending, score descending, slot ascending), dead slots
+// under AUG_DEAD_LABEL.  The leader is the first undecided slot of the segment; every thread strides over the slots from the leader on
+// and decides the undecided ones against the leader alone: mode 0 (greedy NMS, nms.cu) marks IoU > thresh suppressed; mode 1 (bbox_vote)
+// takes IoU >= thresh, the leader included, into the cluster and sums score * box and score.  The same pass finds the next leader as the
+// smallest slot left undecided, so the loop runs once per kept box or cluster, not once per slot.  state: 0 undecided (as it arrives),
+// 1 kept, 2 gone; slot i is read and written by thread (i - lo) % AUG_THREADS only.  The sums go lane tree -> wave 0..3 in that order:
+// two runs give the same bits.  lo <= hi <= T whatever the labels hold, and every index used lies in [lo, hi).
+__global__ __launch_bounds__(AUG_THREADS) void det_aug_merge_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                                    const int* __restrict__ labels, const int* __restrict__ classes,
+                                                                    int* __restrict__ state, float* __restrict__ oboxes, int T,
+                                                                    float thresh, int mode) {
+  __shared__ float red[AUG_THREADS / 64][5];
+  __shared__ int red_next[AUG_THREADS / 64], red_n[AUG_THREADS / 64];
+  const int b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const size_t base = (size_t)b * T;
+  const int* __restrict__ lab = labels + base;
+  const int label = classes[blockIdx.x];
+  if (label < 0 || label >= AUG_DEAD_LABEL) return;
+  const int lo = aug_lower_bound(lab, T, label);
+  const int hi = lo + aug_lower_bound(lab + lo, T - lo, label + 1);
+  if (hi <= lo) return;                                    // whole workgroup: no barrier has been reached
+  const float* __restrict__ bx = boxes + base * 4;
+  const float* __restrict__ sc = scores + base;
+  int* __restrict__ st = state + base;
+  float* __restrict__ ob = oboxes + base * 4;
+  int leader = lo;
+  while (leader < hi) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(bx + (size_t)leader * 4);
+    const float Sa = (a[2] - a[0] + 1.f) * (a[3] - a[1] + 1.f);
+    float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    int next = hi, members = 0;
+    // the first slot >= leader that this thread owns
+    int i = leader + ((tid - (leader - lo)) % AUG_THREADS + AUG_THREADS) % AUG_THREADS;
+    for (; i < hi; i += AUG_THREADS) {
+      if (i != leader && st[i] != 0) continue;
+      const f32x4 c = *reinterpret_cast<const f32x4*>(bx + (size_t)i * 4);
+      const float left = fmaxf(a[0], c[0]), right = fminf(a[2], c[2]);
+      const float top = fmaxf(a[1], c[1]), bottom = fminf(a[3], c[3]);
+      const float width = fmaxf(right - left + 1.f, 0.f), height = fmaxf(bottom - top + 1.f, 0.f);
+      const float inter = width * height;
+      const float Sb = (c[2] - c[0] + 1.f) * (c[3] - c[1] + 1.f);
+      const float iou = inter / (Sa + Sb - inter);
+      const bool hit = i == leader || (mode ? iou >= thresh : iou > thresh);
+      if (hit) {
+        st[i] = i == leader ? 1 : 2;
+        if (mode) {
+          const float s = sc[i];
+          acc[0] += c[0] * s;
+          acc[1] += c[1] * s;
+          acc[2] += c[2] * s;
+          acc[3] += c[3] * s;
+          acc[4] += s;
+          ++members;
+        }
+      } else {
+        next = min(next, i);
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      next = min(next, __shfl_xor(next, o));
+      if (mode) {
+        members += __shfl_xor(members, o);
+#pragma unroll
+        for (int r = 0; r < 5; ++r) acc[r] += __shfl_xor(acc[r], o);
+      }
+    }
+    if (lane == 0) {
+      red_next[wave] = next;
+      red_n[wave] = members;
+#pragma unroll
+      for (int r = 0; r < 5; ++r) red[wave][r] = acc[r];
+    }
+    __syncthreads();
+    next = red_next[0];
+    members = red_n[0];
+#pragma unroll
+    for (int r = 0; r < 5; ++r) acc[r] = red[0][r];
+#pragma unroll
+    for (int w = 1; w < AUG_THREADS / 64; ++w) {
+      next = min(next, red_next[w]);
+      members += red_n[w];
+#pragma unroll
+      for (int r = 0; r < 5; ++r) acc[r] += red[w][r];
+    }
+    if (tid == 0) {
+      f32x4 out = a;
+      if (mode && members > 1) out = f32x4{acc[0] / acc[4], acc[1] / acc[4], acc[2] / acc[4], acc[3] / acc[4]};
+      *reinterpret_cast<f32x4*>(ob + (size_t)leader * 4) = out;
+    }
+    __syncthreads();                                       // red is rewritten by the next round
+    leader = next;                                         // > the old leader: every round decides its leader
+  }
+}
+
 }  // namespace
+
+// Largest T (candidates per image over all views) of fiber_det_aug_collect / fiber_det_aug_merge
+extern "C" int fiber_det_aug_max_candidates(void) { return AUG_MAX_T; }
+
+extern "C" int fiber_det_aug_collect(const float* boxes, const float* scores, const int* labels, const int* source, const void* table,
+                                     const int* classes, float* out_boxes, float* out_scores, int* out_labels, int* out_source,
+                                     int* out_view, int B, int Nv, int T, int offset, int view, int C, hipStream_t stream) {
+  static_assert(sizeof(AugView) == 32, "the host packs 32-byte records");
+  if (B < 0 || Nv < 0 || T < 0 || T > AUG_MAX_T || offset < 0 || (long long)offset + Nv > T || view < 0 || C < 0 || B > 65535)
+    return FIBER_EINVAL;
+  if (B == 0 || Nv == 0) return FIBER_OK;
+  if (!boxes || !scores || !labels || !source || !table || (C > 0 && !classes) || !out_boxes || !out_scores || !out_labels ||
+      !out_source || !out_view)
+    return FIBER_EINVAL;
+  if (fiber_misaligned(16, boxes, out_boxes) ||
+      fiber_misaligned(4, scores, labels, source, table, classes, out_scores, out_labels, out_source, out_view))
+    return FIBER_EINVAL;
+  hipLaunchKernelGGL(det_aug_collect_kernel, dim3(cdiv(Nv, AUG_THREADS), B), dim3(AUG_THREADS), 0, stream, boxes, scores, labels, source,
+                     static_cast<const AugView*>(table), classes, out_boxes, out_scores, out_labels, out_source, out_view, Nv, T, offset,
+                     view, C);
+  FIBER_CHECK_LAUNCH();
+  return FIBER_OK;
+}
+
+extern "C" int fiber_det_aug_merge(const float* boxes, const float* scores, const int* labels, const int* classes, int* state,
+                                   float* out_boxes, int B, int T, int C, float thresh, int mode, hipStream_t stream) {
+  if (B < 0 || T < 0 || T > AUG_MAX_T || C < 0 || B > 65535 || (mode != 0 && mode != 1) || !(thresh > 0.f)) return FIBER_EINVAL;
+  if (B == 0 || T == 0 || C == 0) return FIBER_OK;
+  if (!boxes || !scores || !labels || !classes || !state || !out_boxes) return FIBER_EINVAL;
+  if (fiber_misaligned(16, boxes, out_boxes) || fiber_misaligned(4, scores, labels, classes, state)) return FIBER_EINVAL;
+  hipLaunchKernelGGL(det_aug_merge_kernel, dim3(C, B), dim3(AUG_THREADS), 0, stream, boxes, scores, labels, classes, state, out_boxes, T,
+                     thresh, mode);
+  FIBER_CHECK_LAUNCH();
+  return FIBER_OK;
+}
 
 // Largest K * D (candidates per image over all chunks) the merge kernel stages in LDS
 extern "C" int fiber_det_merge_max_candidates(void) { return MRG_MAX_N; }

@@ -193,20 +193,35 @@ class DeviceDetectionTransform:
         else:
             min_size, max_size, flip_prob = inp.MIN_SIZE_TEST, inp.MAX_SIZE_TEST, 0.0
         _need(not getattr(inp, "FIX_RES", False), "INPUT.FIX_RES", "the fixed (size, max_size) resolution of Resize(restrict=True) is not built")
+        self.min_size = tuple(int(v) for v in (min_size if isinstance(min_size, (list, tuple)) else (min_size,)))
+        self.max_size = None if max_size is None else int(max_size)
+        self.flip_threshold = int(flip_prob * 2 ** 32)
+        self._pixels(cfg)
+        self.is_train = bool(is_train)
+
+    def _pixels(self, cfg):
+        """the pixel format, mean / std and divisibility: what apply() reads"""
+        inp = cfg.INPUT
         fmt = getattr(inp, "FORMAT", "")
         if fmt == "":
             if not getattr(inp, "TO_BGR255", False):
                 raise ValueError("INPUT.FORMAT is empty and INPUT.TO_BGR255 is false: build_transforms defines no input format")
             fmt = "bgr255"
         fmt = fmt.lower()
-        self.min_size = tuple(int(v) for v in (min_size if isinstance(min_size, (list, tuple)) else (min_size,)))
-        self.max_size = None if max_size is None else int(max_size)
-        self.flip_threshold = int(flip_prob * 2 ** 32)
         self.bgr, self.times255 = int("bgr" in fmt), int("255" in fmt)
         self.mean = (lib.C.c_float * 3)(*inp.PIXEL_MEAN)
         self.std = (lib.C.c_float * 3)(*inp.PIXEL_STD)
         self.size_divisible = int(getattr(getattr(cfg, "DATALOADER", None), "SIZE_DIVISIBILITY", 0))
-        self.is_train = bool(is_train)
+
+    @classmethod
+    def for_views(cls, cfg):
+        """A transform for sizes and flips chosen by the caller (multi-scale testing: box_aug.py:73-126 builds Resize(scale, max_size)
+        [+ RandomHorizontalFlip(1.0)] + ToTensor + Normalize per view): it carries INPUT's pixel format, mean / std and
+        DATALOADER.SIZE_DIVISIBILITY only; apply(images, sizes, flips) is the one call it serves (no size list, no flip probability)."""
+        t = cls.__new__(cls)
+        t.min_size, t.max_size, t.flip_threshold, t.is_train = (), None, 0, False
+        t._pixels(cfg)
+        return t
 
     def choose(self, seed, index, w, h):
         """-> ((oh, ow), flipped) of sample `index` of the batch keyed `seed` for a w x h source"""

@@ -79,6 +79,8 @@ SIGNATURES = {
     "fiber_det_nms_mask": [P, P, P, P, I, I, F],
     "fiber_det_nms_select": [P, P, P, P, P, P, P, P, P, P, I, I, I],
     "fiber_det_merge": [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I],
+    "fiber_det_aug_collect": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I],
+    "fiber_det_aug_merge": [P, P, P, P, P, P, I, I, I, F, I],
     "fiber_ground_recall": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, DBL, I],
     "fiber_ap_match": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I],
     "fiber_ap_accumulate": [P, P, P, P, P, P, P, C.c_longlong, I, I, I, I],
@@ -94,7 +96,7 @@ SIGNATURES = {
 # host-side helpers without a stream argument
 PLAIN = {"fiber_layernorm_bwd_grid": [I], "fiber_window_attn_bwd_slices": [I, I], "fiber_window_attn_colsum_rows": [I, I, I], "fiber_colsum_slabs": [I, I], "fiber_colsum_labelled_slabs": [I], "fiber_gemm_row_tile": [I, I, I], "fiber_gemm_tn_splits": [I, I, I],
          "fiber_adamw_chunk": [], "fiber_resample_ksize": [I, I], "fiber_resample_ksize_bilinear": [I, I], "fiber_dcn_dx_workspace": [I, I, I, I, I, I, I],
-         "fiber_roberta_embed_bwd_workspace": [I, I, I], "fiber_ground_workspace": [I, I, I], "fiber_det_max_candidates": [], "fiber_det_merge_max_candidates": [],
+         "fiber_roberta_embed_bwd_workspace": [I, I, I], "fiber_ground_workspace": [I, I, I], "fiber_det_max_candidates": [], "fiber_det_merge_max_candidates": [], "fiber_det_aug_max_candidates": [],
          "fiber_ap_max_gt": [], "fiber_ap_chunk": [],
          "fiber_atss_num_candidates": [P, I, I], "fiber_atss_loss_rows": [I, I]}
 

@@ -29,13 +29,14 @@ Deviations from the reference:
 
 This is the LVIS protocol.  COCO ground truth can be evaluated with crowd boxes packed as ignore = 1 and every category in every image's
 negative list, but that is the LVIS protocol on COCO data, not COCOeval: the COCO API's crowd rule (IoU over the detection's area,
-re-matchable crowd regions) is not reproduced.  Out of scope as well: segmentation and keypoint IoU, LvisDumper, test-time augmentation
-and the dataset readers.
+re-matchable crowd regions) is not reproduced.  Out of scope as well: segmentation and keypoint IoU, LvisDumper and the dataset readers.
 
 evaluate_detection runs one prompt per image; evaluate_detection_chunked a vocabulary cut into prompts (detection_prompts.py), with the
 prompt-independent part of the backbone computed once per image, the image-independent part once per evaluation and the chunks of an image
-merged by ops.det_merge.  Out of scope there: sharing the FPN lateral of the prompt-independent level between an image's pairs, the
-multi-scale im_detect_bbox_aug, and the result CSV writers.
+merged by ops.det_merge; evaluate_detection_multiscale one prompt per image over the views of TEST.SCALES x TEST.FLIP
+(box_aug.im_detect_bbox_aug: GeneralizedVLRCNN.detect_multiscale, merged by ops.det_aug_merge with plain NMS or box voting).  Out of
+scope there: sharing the FPN lateral of the prompt-independent level between an image's pairs, multi-scale testing of a chunked
+vocabulary, TEST.SPECIAL_NMS "soft-nms" / "soft-vote", and the result CSV writers.
 """
 import numpy as np
 import torch
@@ -403,6 +404,20 @@ def evaluate_detection(model, batches, evaluator):
             detections = model(images, tokenizer_input=batch["tokenizer_input"], positive_map=batch["positive_maps"])
             boxes = images.boxes_to_original(detections)
             evaluator.update(detections, batch["targets"].to(boxes.device), boxes=boxes)
+    return evaluator.summarize()
+
+
+def evaluate_detection_multiscale(model, batches, evaluator, test_cfg=None):
+    """The detection loop with test-time augmentation (TEST.USE_MULTISCALE: engine/inference.py:47-48 and :492-504, im_detect_bbox_aug).
+    batches yields dicts as evaluate_detection takes them, except that "images" is the list of raw uint8 [H, W, 3] device tensors:
+    GeneralizedVLRCNN.detect_multiscale resizes and flips them per view itself and returns boxes in each image's original frame.
+    test_cfg: the TEST node (default model.cfg.TEST).  -> evaluator.summarize().  Nothing synchronises before summarize."""
+    model.eval()
+    with torch.no_grad():
+        for batch in batches:
+            detections = model.detect_multiscale(batch["images"], tokenizer_input=batch["tokenizer_input"], positive_map=batch["positive_maps"],
+                                                 test_cfg=test_cfg)
+            evaluator.update(detections, batch["targets"].to(detections.boxes.device), boxes=detections.boxes)
     return evaluator.summarize()
 
 

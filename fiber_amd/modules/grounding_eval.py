@@ -20,7 +20,8 @@ Deviations from the reference, each by construction of the fixed-shape form:
   * RefExp ranks by stored position, i.e. by descending score; the reference's sorted(zip(scores, boxes)) breaks score ties by box.
 
 Out of scope: gathering predictions across ranks (synchronize_between_processes), the csv writers (write_flickr_results,
-write_refexp_results), the COCO evaluator (pycocotools; LVIS box AP is detection_eval.py) and test-time augmentation (im_detect_bbox_aug).  Tokenisation and
+write_refexp_results), the COCO evaluator (pycocotools; LVIS box AP is detection_eval.py) and test-time augmentation of the grounding loops (im_detect_bbox_aug
+is built for detection: GeneralizedVLRCNN.detect_multiscale, detection_eval.evaluate_detection_multiscale).  Tokenisation and
 the dataset readers stay with the caller, as everywhere in this package.
 """
 import warnings

@@ -12,6 +12,8 @@ synchronisation), then the N x N/64 suppression mask copied to the host and walk
   torch.sort       per image, descending and stable, + one gather
   ops.nms_ml       mask kernel (one wave per 64 x 64 block) + select kernel (one wave per image, stops at detections_per_img)
 so the whole of ATSSPostProcessor.forward can be captured in a hipGraph; Detections.to_list() is the only call that synchronises.
+ATSSPostProcessor.candidates stops after the decode: multi-scale testing (GeneralizedVLRCNN.detect_multiscale) merges the candidates of
+all views itself (ops.det_aug_collect, ops.det_aug_merge).
 
 Deviations from the reference, each pinned by tests/test_detect_compare_host.py or tests/test_hip_detect.py:
   * the cut to detections_per_img takes the first D survivors in score order; the reference's kthvalue keeps every score >= the cut, i.e.
@@ -33,7 +35,9 @@ _UNSUPPORTED = {
     "box_cls": "classification-only scoring (no dot_product_logits): FIBER's grounding head always returns them",
     "POWER": "DYHEAD.SCORE_AGG POWER: no FIBER config sets it (MEAN and MAX are built)",
     "ONEHOT": "DYHEAD.SCORE_AGG ONEHOT: no FIBER config sets it (MEAN and MAX are built)",
-    "bbox_aug": "TEST.USE_MULTISCALE / bbox_aug_vote: multi-scale testing returns before select_over_all_levels",
+    "bbox_aug": "bbox_aug_enabled / bbox_aug_vote change what forward returns (the candidates before select_over_all_levels); a "
+                "post-processor here keeps one return contract: multi-scale testing (TEST.USE_MULTISCALE) calls candidates() instead, "
+                "through GeneralizedVLRCNN.detect_multiscale",
     "nms_thresh": "NMS_TH <= 0 (boxlist_ml_nms returns its input): every FIBER config suppresses",
     "num_anchors": "one anchor per position: the dot product pairs ONE 256-channel feature with the tokens (vldyhead.py:861-865)",
 }
@@ -217,11 +221,14 @@ class Detections:
     """Fixed-size result: boxes fp32 [B, D, 4] (xyxy, +1 convention), scores fp32 [B, D] (-1 past count), labels int32 [B, D],
     source int32 [B, D] (level << 28 | anchor << 10 | class; -1 past count), count int32 [B]; descending score per image.  chunk int32
     [B, D] (the prompt a detection came from, -1 past count; its source's class field is local to that prompt) is set by chunked detection
-    (GeneralizedVLRCNN.detect_chunked) only, None otherwise."""
+    (GeneralizedVLRCNN.detect_chunked) only, None otherwise.  view int32 [B, D] (the view of multi-scale testing a detection came from,
+    scale-major, un-flipped before flipped; -1 past count; for a voted cluster `source` and `view` are its leader's) is set by
+    GeneralizedVLRCNN.detect_multiscale only, None otherwise."""
     SOURCE_A_SHIFT, SOURCE_LEVEL_SHIFT = 10, 28
 
-    def __init__(self, boxes, scores, labels, source, count, chunk=None):
+    def __init__(self, boxes, scores, labels, source, count, chunk=None, view=None):
         self.boxes, self.scores, self.labels, self.source, self.count, self.chunk = boxes, scores, labels, source, count, chunk
+        self.view = view
 
     def to_list(self):
         """Per image {"boxes", "scores", "labels" (int64), "source"} trimmed to count.  The one call that synchronises."""
@@ -283,14 +290,12 @@ class ATSSPostProcessor(nn.Module):
     def level_k(self, num_anchors, C):
         return min(int(self.pre_nms_top_n), num_anchors * C)
 
-    def forward(self, box_regression, centerness, image_sizes, anchors, dot_product_logits=None, positive_map=None, box_cls=None,
-                token_logits=None, num_classes=None):
-        """box_regression / centerness / dot_product_logits: per level, as VLDyHead.forward returns them; image_sizes fp32 [B, 2] device
-        tensor of (w, h) per image; anchors: one [A_l, 4] tensor per level (AnchorGenerator.grid_anchors of the feature shapes: the
-        reference's per-image BoxList copies differ in nothing but the size field).  positive_map: the reference's dict (one map for the
-        batch, cached by csr()), a list of B dicts (one per sample: packed here with one host-to-device copy per call, not cached), or a
-        PackedPositiveMaps already on the device (no copy).  num_classes: the width C of the dense scores for this call (chunked detection
-        scores one prompt's classes at a time); None = num_score_classes().  -> Detections"""
+    def candidates(self, box_regression, centerness, image_sizes, anchors, dot_product_logits=None, positive_map=None, box_cls=None,
+                   token_logits=None, num_classes=None):
+        """forward up to and including the per-level decode (arguments as forward takes them) -> (boxes fp32 [B, N, 4], scores fp32
+        [B, N], labels int32 [B, N], source int32 [B, N]), N = sum of the levels' fixed k: the decoded, clipped top-k of every level,
+        concatenated in level order, padding under score -1; no sort, no NMS, no cut.  What the reference's post-processor returns with
+        bbox_aug_enabled (inference.py:708), in fixed shapes."""
         if token_logits is not None:
             raise NotImplementedError(f"ATSSPostProcessor token_logits: {_UNSUPPORTED['token_logits']}")
         if dot_product_logits is None:
@@ -325,7 +330,18 @@ class ATSSPostProcessor(nn.Module):
             val, flat = torch.topk(dense.view(B, -1), k, dim=1)
             ops.det_decode(val, flat, reg, anc, image_sizes, out, off, l, C, self.min_size)
             off += k
-        boxes, scores, labels, source = out
+        return out
+
+    def forward(self, box_regression, centerness, image_sizes, anchors, dot_product_logits=None, positive_map=None, box_cls=None,
+                token_logits=None, num_classes=None):
+        """box_regression / centerness / dot_product_logits: per level, as VLDyHead.forward returns them; image_sizes fp32 [B, 2] device
+        tensor of (w, h) per image; anchors: one [A_l, 4] tensor per level (AnchorGenerator.grid_anchors of the feature shapes: the
+        reference's per-image BoxList copies differ in nothing but the size field).  positive_map: the reference's dict (one map for the
+        batch, cached by csr()), a list of B dicts (one per sample: packed here with one host-to-device copy per call, not cached), or a
+        PackedPositiveMaps already on the device (no copy).  num_classes: the width C of the dense scores for this call (chunked detection
+        scores one prompt's classes at a time); None = num_score_classes().  -> Detections"""
+        boxes, scores, labels, source = self.candidates(box_regression, centerness, image_sizes, anchors, dot_product_logits, positive_map,
+                                                        box_cls, token_logits, num_classes)
         scores, order = torch.sort(scores, dim=1, descending=True, stable=True)
         boxes = torch.gather(boxes, 1, order[:, :, None].expand(-1, -1, 4))
         labels, source = torch.gather(labels, 1, order), torch.gather(source, 1, order)
@@ -333,14 +349,15 @@ class ATSSPostProcessor(nn.Module):
 
 
 def make_atss_postprocessor(config, box_coder, is_train=False):
-    """inference.py:798-823"""
+    """inference.py:798-823.  TEST.USE_MULTISCALE is not forwarded into bbox_aug_enabled: the switch selects
+    GeneralizedVLRCNN.detect_multiscale, which asks the same post-processor for its candidates()."""
     a = config.MODEL.ATSS
     return ATSSPostProcessor(
         pre_nms_thresh=a.INFERENCE_TH_TRAIN if is_train else a.INFERENCE_TH,
         pre_nms_top_n=a.PRE_NMS_TOP_N_TRAIN if is_train else a.PRE_NMS_TOP_N,
         nms_thresh=a.NMS_TH,
         fpn_post_nms_top_n=a.POST_NMS_TOP_N_TRAIN if is_train else a.DETECTIONS_PER_IMG,
-        min_size=0, num_classes=a.NUM_CLASSES, box_coder=box_coder, bbox_aug_enabled=config.TEST.USE_MULTISCALE,
+        min_size=0, num_classes=a.NUM_CLASSES, box_coder=box_coder,
         score_agg=config.MODEL.DYHEAD.SCORE_AGG, mdetr_style_aggregate_class_num=config.TEST.MDETR_STYLE_AGGREGATE_CLASS_NUM)
 
 
@@ -369,13 +386,14 @@ class VLDyHeadModule(nn.Module):
         w = getattr(self.cfg.MODEL.DYHEAD.FUSE_CONFIG, "DOT_PRODUCT_TOKEN_LOSS_WEIGHT", 1.0)
         return {"loss_reg": reg, "loss_centerness": ctr, "loss_cls": cls, "loss_dot_product_token": token * w}
 
-    def forward(self, image_sizes, features, language_dict_features, positive_map=None, targets=None, num_classes=None):
+    def forward(self, image_sizes, features, language_dict_features, positive_map=None, targets=None, num_classes=None, candidates=False):
         """Training mode with `targets`: -> {"loss_reg", "loss_centerness", "loss_cls", "loss_dot_product_token"} (image_sizes and
         positive_map are not read: the anchors do not depend on the image and the targets carry their positive map).  Eval: image_sizes: [(h, w)] per image as ImageList.image_sizes, or a [B, 2] tensor of (w, h); features: the FPN levels
         [B, C, H, W]; language_dict_features["embedded"]: [B, 256, LANG_DIM]; positive_map: one dict for the batch, a list of B dicts or a
         PackedPositiveMaps (one map per sample: see ATSSPostProcessor.forward).  -> Detections.  A list of sizes is copied to the device
         here (a host-to-device copy per call); pass the tensor, already on the device, to avoid it or to capture the call in a graph.
-        num_classes: see ATSSPostProcessor.forward."""
+        num_classes: see ATSSPostProcessor.forward.  candidates=True (eval only): -> ATSSPostProcessor.candidates' (boxes, scores, labels,
+        source) instead of Detections (multi-scale testing merges the views' candidates itself)."""
         if self.training:
             if targets is None:
                 raise NotImplementedError("VLDyHeadModule in training mode needs targets= (grounding_train.pack_targets); without them "
@@ -387,5 +405,6 @@ class VLDyHeadModule(nn.Module):
         image_sizes = image_sizes.to(device=dev, dtype=torch.float32)
         with torch.no_grad():
             out = self.head(features, language_dict_features, language_dict_features["embedded"])
-            return self.box_selector_test(out[1], out[2], image_sizes, self.anchor_generator(features), out[6], positive_map,
-                                          box_cls=out[0], token_logits=out[3], num_classes=num_classes)
+            post = self.box_selector_test.candidates if candidates else self.box_selector_test
+            return post(out[1], out[2], image_sizes, self.anchor_generator(features), out[6], positive_map, box_cls=out[0],
+                        token_logits=out[3], num_classes=num_classes)

@@ -179,6 +179,78 @@ class GeneralizedVLRCNN(nn.Module):
             *merged, chunk, total = ops.det_merge(boxes, scores, labels, source, count, prompts.label_table, max_dets)
         return Detections(*merged, total, chunk=chunk)
 
+    # ---- multi-scale test-time augmentation (TEST.USE_MULTISCALE, data/datasets/evaluation/box_aug.py) ---------------------------------
+    # Every view (scale x flip) of every image runs the image side of the model; the un-cut candidates of all views are brought back to the
+    # image's own frame (ops.det_aug_collect, one launch per view) and merged class by class on the device (ops.det_aug_merge).  The text
+    # prefix does not depend on the view and is computed once.
+    @staticmethod
+    def multiscale_views(test_cfg):
+        """-> [(scale, keep_range or None, flip)] in the reference's order: scale-major, un-flipped before flipped (box_aug.py:24-57)"""
+        scales, ranges = list(test_cfg.SCALES), list(getattr(test_cfg, "RANGES", ()))
+        if len(ranges) != len(scales):
+            ranges = [None] * len(scales)
+        views = []
+        for scale, keep in zip(scales, ranges):
+            keep = None if keep is None else (keep[0], keep[1])
+            views.append((scale, keep, False))
+            if getattr(test_cfg, "FLIP", False):
+                views.append((scale, keep, True))
+        return views
+
+    def detect_multiscale(self, images, captions=None, positive_map=None, tokenizer_input=None, test_cfg=None):
+        """images: a list of uint8 [H, W, 3] RGB device tensors, untransformed (as the reference's BBoxAugCollator hands them over);
+        captions / tokenizer_input / positive_map as forward takes them; test_cfg (default cfg.TEST) is read for SCALES, RANGES,
+        MAX_SIZE, FLIP, SPECIAL_NMS, TH, PRE_NMS_TOP_N, NUM_CLASSES and SELECT_CLASSES.  -> Detections of the fixed size
+        [B, PRE_NMS_TOP_N] with boxes IN EACH IMAGE'S ORIGINAL FRAME and `view` set.  Eval mode only; nothing synchronises: every size
+        comes from the images' shapes."""
+        from ..data import DeviceDetectionTransform, det_resize_size
+        if self.training:
+            raise RuntimeError("detect_multiscale: the model is in training mode (multi-scale testing is an inference path: call .eval())")
+        t = self.cfg.TEST if test_cfg is None else test_cfg
+        top_n, mode = int(t.PRE_NMS_TOP_N), getattr(t, "SPECIAL_NMS", "none")
+        if top_n <= 0:
+            raise NotImplementedError("detect_multiscale: TEST.PRE_NMS_TOP_N <= 0 (no cut): the outputs have the fixed size [B, PRE_NMS_TOP_N]")
+        if mode in ("soft-nms", "soft-vote"):
+            raise NotImplementedError(f"detect_multiscale: TEST.SPECIAL_NMS {mode!r} is out of scope (\"vote\" and plain NMS are built)")
+        mode = mode if mode == "vote" else "none"                # boxlist_nms: any other string is plain NMS
+        views = self.multiscale_views(t)
+        if not views:
+            raise ValueError("detect_multiscale: TEST.SCALES is empty")
+        select = [int(c) for c in getattr(t, "SELECT_CLASSES", ())]
+        classes = sorted(set(select)) if select else list(range(1, int(t.NUM_CLASSES)))
+        images = list(images)
+        dev = images[0].device
+        shapes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+        B = len(images)
+        if tokenizer_input is None:
+            if captions is None:
+                raise ValueError("GeneralizedVLRCNN: captions (with a tokenizer) or tokenizer_input is required")
+            tokenizer_input = self._tokenize(captions, dev)
+        transform = DeviceDetectionTransform.for_views(self.cfg)
+        fb = self.fusion_backbone
+        per_view = []
+        with torch.no_grad():
+            d_classes = torch.tensor(classes, dtype=torch.int32).to(dev, non_blocking=True)
+            text_state = fb.text_prefix(tokenizer_input)
+            for scale, keep, flip in views:
+                sizes = [det_resize_size(W, H, scale, getattr(t, "MAX_SIZE", None)) for H, W in shapes]
+                batch = transform.apply(images, sizes, [flip] * B)
+                visual, lang, _ = fb.fuse(fb.image_prefix(batch.tensors), text_state)
+                lang["mlm_labels"] = None
+                wh = torch.tensor([[float(ow), float(oh)] for oh, ow in batch.image_sizes], dtype=torch.float32).to(dev, non_blocking=True)
+                cand = self.rpn(wh, list(visual), lang, positive_map, None, candidates=True)
+                per_view.append((cand, ops.det_aug_view_rows(shapes, batch.image_sizes, flip, keep)))
+            T = sum(int(cand[1].shape[1]) for cand, _ in per_view)
+            out = (torch.empty((B, T, 4), dtype=torch.float32, device=dev), torch.empty((B, T), dtype=torch.float32, device=dev),
+                   torch.empty((B, T), dtype=torch.int32, device=dev), torch.empty((B, T), dtype=torch.int32, device=dev),
+                   torch.empty((B, T), dtype=torch.int32, device=dev))
+            off = 0
+            for v, (cand, rows) in enumerate(per_view):
+                ops.det_aug_collect(*cand, rows, d_classes, out, off, v)
+                off += int(cand[1].shape[1])
+            *merged, view, count = ops.det_aug_merge(*out, d_classes, float(t.TH), mode, top_n)
+        return Detections(*merged, count, view=view)
+
 
 class PromptState:
     """encode_prompts' result: `text` (fusion_swin.TextState of the K prompts) and `prompts` (DetectionPrompts on the device)"""

@@ -2130,6 +2130,237 @@ def det_merge(boxes, scores, labels, source, count, label_table, max_dets=None, 
     return ob, osc, ol, osr, och, ocnt
 
 
+# ---- multi-scale test-time augmentation: collect the views' candidates, merge them class by class (csrc/detect.hip) -----------------
+DET_AUG_MAX_CANDIDATES = 1 << 20                             # = det_aug_max_candidates(); the host path keeps the same bound
+DET_AUG_MODES = {"none": 0, "vote": 1}
+_DET_AUG_DEAD = 1 << 30                                      # the label dead slots sort under (AUG_DEAD_LABEL)
+
+
+def det_aug_max_candidates():
+    return int(lib.plain("fiber_det_aug_max_candidates"))
+
+
+def _det_aug_view_dtype():
+    import numpy as np
+    return np.dtype([("scaled_w", "<f4"), ("ratio_w", "<f4"), ("ratio_h", "<f4"), ("equal", "<i4"), ("flip", "<i4"), ("has_range", "<i4"),
+                     ("min2", "<f4"), ("max2", "<f4")])
+
+
+def det_aug_view_rows(originals, sizes, flip, keep_range=None):
+    """The per-image records of one view for det_aug_collect.  originals: (H, W) per image, sizes: (oh, ow) of the resized images (the
+    frame the view's candidates are in), flip: the view ran on the mirrored images, keep_range: TEST.RANGES' (min, max) or None.
+    The ratios are BoxList.resize's (bounding_box.py:110): computed in double, compared in double, applied as fp32."""
+    rows = []
+    for (H, W), (oh, ow) in zip(originals, sizes):
+        rw, rh = float(W) / float(ow), float(H) / float(oh)
+        lo, hi = (0.0, 0.0) if keep_range is None else (float(keep_range[0] * keep_range[0]), float(keep_range[1] * keep_range[1]))
+        rows.append((float(ow), rw, rh, int(rw == rh), int(bool(flip)), int(keep_range is not None), lo, hi))
+    return rows
+
+
+def _det_aug_check_classes(classes, dev, what):
+    if classes.dim() != 1 or classes.dtype != torch.int32 or classes.device != dev:
+        raise ValueError(f"{what}: classes {tuple(classes.shape)} {classes.dtype} on {classes.device}: an ascending int32 [C] table on {dev}")
+
+
+def _det_aug_collect_host(boxes, scores, labels, source, table, classes, out, offset, view):
+    """fiber_det_aug_collect on CPU tensors, in numpy (fp32 throughout, the kernel's operation order)"""
+    import numpy as np
+    bx, sc, lb, sr = boxes.detach().float().numpy(), scores.detach().float().numpy(), labels.numpy(), source.numpy()
+    ob, osc, ol, osr, ov = (t.numpy() for t in out)
+    Nv = sc.shape[1]
+    one = np.float32(1)
+    for b, p in enumerate(table):
+        x1, y1, x2, y2 = (bx[b, :, i].copy() for i in range(4))
+        live = (sc[b] >= 0) & np.isin(lb[b], classes.numpy())
+        if p["flip"]:
+            x1, x2 = p["scaled_w"] - x2 - one, p["scaled_w"] - x1 - one
+        if p["has_range"]:
+            area = (x2 - x1 + one) * (y2 - y1 + one)
+            live &= (area > p["min2"]) & (area < p["max2"])
+        ry = p["ratio_w"] if p["equal"] else p["ratio_h"]
+        box = np.stack((x1 * p["ratio_w"], y1 * ry, x2 * p["ratio_w"], y2 * ry), axis=1).astype(np.float32)
+        at = slice(offset, offset + Nv)
+        ob[b, at] = np.where(live[:, None], box, np.float32(0))
+        osc[b, at], ol[b, at] = np.where(live, sc[b], np.float32(-1)), np.where(live, lb[b], 0)
+        osr[b, at], ov[b, at] = np.where(live, sr[b], -1), np.where(live, view, -1)
+
+
+def det_aug_collect(boxes, scores, labels, source, rows, classes, out, offset, view):
+    """One view's candidates (ATSSPostProcessor.candidates: boxes fp32 [B, Nv, 4] in the view's resized frame, scores fp32 [B, Nv] with
+    -1 padding, labels / source int32 [B, Nv]) -> the slots [offset, offset + Nv) of out = (boxes [B, T, 4], scores, labels, source, view
+    [B, T]) in place: un-flipped, range-filtered in the resized frame, resized to the original frame (box_aug.py: im_detect_bbox_hflip,
+    remove_boxes, add_preds_t).  rows: det_aug_view_rows(...) (host); classes: ascending int32 [C], labels outside it are dropped.
+    Dropped and padding slots get box 0, score -1, label 0, source -1, view -1.  One launch, no synchronisation; on CPU tensors numpy."""
+    import numpy as np
+    if boxes.dim() != 3 or scores.dim() != 2:
+        raise ValueError(f"det_aug_collect: boxes {tuple(boxes.shape)}, scores {tuple(scores.shape)}: [B, Nv, 4] and [B, Nv]")
+    B, Nv = scores.shape
+    if boxes.shape != (B, Nv, 4) or labels.shape != (B, Nv) or source.shape != (B, Nv) or len(rows) != B:
+        raise ValueError(f"det_aug_collect: boxes {tuple(boxes.shape)}, labels {tuple(labels.shape)}, source {tuple(source.shape)}, "
+                         f"{len(rows)} rows for scores {tuple(scores.shape)}")
+    if boxes.dtype != torch.float32 or scores.dtype != torch.float32 or labels.dtype != torch.int32 or source.dtype != torch.int32:
+        raise ValueError("det_aug_collect: boxes / scores fp32, labels / source int32")
+    dev = scores.device
+    _det_aug_check_classes(classes, dev, "det_aug_collect")
+    if len(out) != 5:
+        raise ValueError("det_aug_collect: out is (boxes, scores, labels, source, view)")
+    T = int(out[1].shape[1]) if out[1].dim() == 2 else -1
+    shapes = (((B, T, 4), torch.float32), ((B, T), torch.float32), ((B, T), torch.int32), ((B, T), torch.int32), ((B, T), torch.int32))
+    if any(t.shape != s or t.dtype != dt or t.device != dev or not t.is_contiguous() for t, (s, dt) in zip(out, shapes)):
+        raise ValueError(f"det_aug_collect: out must be five contiguous tensors on {dev} of {shapes}")
+    if any(t.device != dev for t in (boxes, labels, source)):
+        raise ValueError("det_aug_collect: the tensors lie on different devices")
+    offset, view = int(offset), int(view)
+    if T > DET_AUG_MAX_CANDIDATES or offset < 0 or offset + Nv > T or view < 0:
+        raise ValueError(f"det_aug_collect: slots [{offset}, {offset + Nv}) of view {view} in buffers of {T} (capacity "
+                         f"{DET_AUG_MAX_CANDIDATES} candidates per image)")
+    table = np.zeros(B, _det_aug_view_dtype())
+    for i, r in enumerate(rows):
+        table[i] = tuple(r)
+    if B == 0 or Nv == 0:
+        return out
+    if not scores.is_cuda:
+        _det_aug_collect_host(boxes, scores, labels, source, table, classes, out, offset, view)
+        return out
+    d_table = torch.from_numpy(table.view(np.uint8).copy()).to(dev, non_blocking=True)
+    lib.call("fiber_det_aug_collect", lib.ptr(_c(boxes)), lib.ptr(_c(scores)), lib.ptr(_c(labels)), lib.ptr(_c(source)), lib.ptr(d_table),
+             lib.ptr(_c(classes)), *(lib.ptr(t) for t in out), B, Nv, T, offset, view, int(classes.numel()))
+    return out
+
+
+def _det_aug_iou(a, c):
+    """IoU of box a [4] with boxes c [n, 4], fp32, +1 widths, nms.cu's operation order"""
+    import numpy as np
+    one, zero = np.float32(1), np.float32(0)
+    w = np.maximum(np.minimum(a[2], c[:, 2]) - np.maximum(a[0], c[:, 0]) + one, zero)
+    h = np.maximum(np.minimum(a[3], c[:, 3]) - np.maximum(a[1], c[:, 1]) + one, zero)
+    inter = w * h
+    sa = (a[2] - a[0] + one) * (a[3] - a[1] + one)
+    sb = (c[:, 2] - c[:, 0] + one) * (c[:, 3] - c[:, 1] + one)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return inter / (sa + sb - inter)
+
+
+def _det_aug_merge_host(boxes, scores, labels, source, view, classes, thresh, mode, D):
+    """det_aug_merge on CPU tensors, in numpy: per image and class the leader loop of the kernel, then the cut"""
+    import numpy as np
+    bx, sc, lb = boxes.detach().float().numpy(), scores.detach().float().numpy(), labels.numpy()
+    sr, vw, cls = source.numpy(), view.numpy(), classes.numpy()
+    B, T = sc.shape
+    ob, osc = np.zeros((B, D, 4), np.float32), np.full((B, D), -1, np.float32)
+    ol, osr, ov, cnt = np.zeros((B, D), np.int32), np.full((B, D), -1, np.int32), np.full((B, D), -1, np.int32), np.zeros(B, np.int32)
+    th = np.float32(thresh)
+    for b in range(B):
+        live = np.nonzero((sc[b] >= 0) & np.isin(lb[b], cls))[0]
+        kept_slot, kept_box = [], []
+        for c in np.unique(lb[b, live]):
+            seg = live[lb[b, live] == c]
+            seg = seg[np.argsort(-sc[b, seg].astype(np.float64), kind="stable")]          # score descending, then slot ascending
+            while len(seg):
+                lead, c_box = seg[0], bx[b, seg]
+                if not thresh > 0:
+                    hit = np.zeros(len(seg), bool)
+                else:
+                    iou = _det_aug_iou(bx[b, lead], c_box)
+                    hit = iou >= th if mode else iou > th
+                hit[0] = True
+                box = bx[b, lead]
+                if mode and hit.sum() > 1:
+                    s = sc[b, seg[hit]]
+                    box = (c_box[hit] * s[:, None]).sum(axis=0, dtype=np.float32) / s.sum(dtype=np.float32)
+                kept_slot.append(lead), kept_box.append(box)
+                seg = seg[~hit]
+        if not kept_slot:
+            continue
+        slot, kb = np.array(kept_slot), np.stack(kept_box).astype(np.float32)
+        order = np.lexsort((slot, lb[b, slot], -sc[b, slot].astype(np.float64)))[:D]       # score descending, label, slot
+        n = len(order)
+        s = slot[order]
+        ob[b, :n], osc[b, :n], ol[b, :n], osr[b, :n], ov[b, :n], cnt[b] = kb[order], sc[b, s], lb[b, s], sr[b, s], vw[b, s], n
+    return tuple(torch.from_numpy(x) for x in (ob, osc, ol, osr, ov, cnt))
+
+
+def det_aug_merge(boxes, scores, labels, source, view, classes, thresh, mode, top_n):
+    """merge_result_from_multi_scales (box_aug.py:175-214) of each image's concatenated candidates as det_aug_collect leaves them: boxes
+    fp32 [B, T, 4], scores fp32 [B, T] (< 0 = dead slot), labels / source / view int32 [B, T]; classes: ASCENDING int32 [C] WITHOUT
+    repeats (TEST.SELECT_CLASSES, or 1 .. NUM_CLASSES - 1), candidates of other labels are dropped.  Per class boxlist_nms(thresh,
+    nms_type=mode): "none" = greedy NMS, suppress iff IoU > thresh; "vote" = bbox_vote, cluster iff IoU >= thresh to the leader, box =
+    sum(score * box) / sum(score) in fp32 under the leader's score, source and view the leader's; thresh <= 0: nothing is suppressed.
+    Then the cut to top_n over all classes.
+    -> (boxes [B, D, 4], scores [B, D], labels, source, view [B, D], count [B]), D = top_n: score descending, then the smaller label, then
+    the earlier slot (= the earlier view, then the earlier slot within it); past count the padding of nms_ml and view -1.
+    On the device: one int64 sort by (label, score), fiber_det_aug_merge (grid classes x images), one sort by score and gathers; nothing
+    is read back.  On CPU tensors the same in numpy."""
+    if mode in ("soft-nms", "soft-vote"):
+        raise NotImplementedError(f"det_aug_merge: TEST.SPECIAL_NMS {mode!r} is out of scope (soft-nms is a sequential CPU op in the "
+                                  "reference; soft-vote appends decayed copies and changes the output size); \"none\" and \"vote\" are built")
+    if mode not in DET_AUG_MODES:
+        raise ValueError(f"det_aug_merge: mode {mode!r}: \"none\" or \"vote\"")
+    if boxes.dim() != 3 or scores.dim() != 2:
+        raise ValueError(f"det_aug_merge: boxes {tuple(boxes.shape)}, scores {tuple(scores.shape)}: [B, T, 4] and [B, T]")
+    B, T = scores.shape
+    if boxes.shape != (B, T, 4) or labels.shape != (B, T) or source.shape != (B, T) or view.shape != (B, T):
+        raise ValueError(f"det_aug_merge: boxes {tuple(boxes.shape)}, labels {tuple(labels.shape)}, source {tuple(source.shape)}, view "
+                         f"{tuple(view.shape)} for scores {tuple(scores.shape)}")
+    if boxes.dtype != torch.float32 or scores.dtype != torch.float32 or labels.dtype != torch.int32 or source.dtype != torch.int32 or \
+            view.dtype != torch.int32:
+        raise ValueError("det_aug_merge: boxes / scores fp32, labels / source / view int32")
+    dev = scores.device
+    _det_aug_check_classes(classes, dev, "det_aug_merge")
+    if any(t.device != dev for t in (boxes, labels, source, view)):
+        raise ValueError("det_aug_merge: the tensors lie on different devices")
+    if T > DET_AUG_MAX_CANDIDATES:
+        raise ValueError(f"det_aug_merge: {T} candidates per image exceed the capacity of {DET_AUG_MAX_CANDIDATES}")
+    D = int(top_n)
+    if D <= 0:
+        raise ValueError(f"det_aug_merge: top_n {top_n}: the result has the fixed size [B, top_n]")
+    thresh, m = float(thresh), DET_AUG_MODES[mode]
+    if not scores.is_cuda:
+        return _det_aug_merge_host(boxes, scores, labels, source, view, classes, thresh, m, D)
+    if B == 0 or T == 0:
+        return (torch.zeros((B, D, 4), dtype=torch.float32, device=dev), torch.full((B, D), -1.0, dtype=torch.float32, device=dev),
+                torch.zeros((B, D), dtype=torch.int32, device=dev), torch.full((B, D), -1, dtype=torch.int32, device=dev),
+                torch.full((B, D), -1, dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev))
+    live = scores >= 0
+    # one key per slot: label in the high word, the score's bits (monotonic for scores >= 0) inverted in the low one; the stable ascending
+    # sort then gives label ascending, score descending, slot ascending, dead slots last
+    bits = scores.contiguous().view(torch.int32).clamp_min(0).long()
+    key = torch.where(live, (labels.long() << 32) | (0x7FFFFFFF - bits), torch.full_like(bits, _DET_AUG_DEAD << 32))
+    key, order = torch.sort(key, dim=1, stable=True)
+    s_labels = (key >> 32).to(torch.int32).contiguous()
+    s_boxes = torch.gather(boxes, 1, order[:, :, None].expand(-1, -1, 4)).contiguous()
+    s_scores = torch.gather(scores, 1, order).contiguous()
+    if thresh > 0 and classes.numel() > 0:
+        state = torch.zeros((B, T), dtype=torch.int32, device=dev)
+        m_boxes = torch.empty((B, T, 4), dtype=torch.float32, device=dev)                # written where state == 1 only
+        lib.call("fiber_det_aug_merge", lib.ptr(s_boxes), lib.ptr(s_scores), lib.ptr(s_labels), lib.ptr(_c(classes)), lib.ptr(state),
+                 lib.ptr(m_boxes), B, T, int(classes.numel()), thresh, m)
+        kept = state == 1
+    elif classes.numel() > 0:                                # no suppression: every live candidate of a listed class is kept
+        at = torch.searchsorted(classes, s_labels).clamp_(max=classes.numel() - 1)
+        kept, m_boxes = torch.gather(live, 1, order) & (classes[at] == s_labels), s_boxes
+    else:
+        kept, m_boxes = torch.zeros_like(live), s_boxes
+    # the cut: the sorted order is (label, score, slot), so a stable sort by score leaves equal scores by label, then slot
+    f_scores, pick = torch.sort(torch.where(kept, s_scores, torch.full_like(s_scores, -1.0)), dim=1, descending=True, stable=True)
+    f_scores, pick = f_scores[:, :D], pick[:, :D]
+    ok = f_scores >= 0
+    slot = torch.gather(order, 1, pick)
+    o_boxes = torch.where(ok[:, :, None], torch.gather(m_boxes, 1, pick[:, :, None].expand(-1, -1, 4)), torch.zeros((), device=dev))
+    o_labels = torch.where(ok, torch.gather(s_labels, 1, pick), torch.zeros((), dtype=torch.int32, device=dev))
+    neg = torch.full((), -1, dtype=torch.int32, device=dev)
+    o_source = torch.where(ok, torch.gather(source, 1, slot), neg)
+    o_view = torch.where(ok, torch.gather(view, 1, slot), neg)
+    count = ok.sum(dim=1, dtype=torch.int32)
+    if T < D:                                                # fewer slots than the result holds: nms_ml's padding
+        pad = D - T
+        F = torch.nn.functional
+        o_boxes, f_scores = F.pad(o_boxes, (0, 0, 0, pad)), F.pad(f_scores, (0, pad), value=-1.0)
+        o_labels, o_source, o_view = F.pad(o_labels, (0, pad)), F.pad(o_source, (0, pad), value=-1), F.pad(o_view, (0, pad), value=-1)
+    return o_boxes.contiguous(), f_scores.contiguous(), o_labels.contiguous(), o_source.contiguous(), o_view.contiguous(), count
+
+
 # ---- grounding evaluation: recall@k of Detections against per-phrase ground truth (csrc/geval.hip) -----------------------------------
 def ground_recall(boxes, labels, count, gt, gt_count, cat_mask, topk, positives, totals, thresh, mode, num_categories=64):
     """One launch of fiber_ground_recall, no host synchronisation.  boxes fp32 [B, D, 4] in the original frame, labels int32 [B, D]

@@ -399,6 +399,33 @@ int fiber_det_nms_select(const float* boxes, const float* scores, const int* lab
                          float* out_boxes, float* out_scores, int* out_labels, int* out_source, int* out_count, int B, int N, int D,
                          fiber_stream_t stream);
 
+/* Multi-scale test-time augmentation (TEST.USE_MULTISCALE; data/datasets/evaluation/box_aug.py): the merge of the un-cut candidates of up
+ * to 24 views of an image, far past the N x N mask of fiber_det_nms_mask.  Fixed shapes, no atomics, no host synchronisation.
+ * fiber_det_aug_collect (one launch per view) replaces im_detect_bbox_hflip's BoxList.transpose(0) (structures/bounding_box.py:138-170),
+ * remove_boxes (box_aug.py:159-172) and add_preds_t's BoxList.resize (bounding_box.py:102-136), in that order: the view's candidates
+ * (boxes fp32 [B,Nv,4] in the resized frame, scores fp32 (< 0 = padding), labels / source int32 [B,Nv]) go to the slots
+ * [offset, offset+Nv) of the image's buffers [B,T,..] with `view` beside them.  table: B records {float scaled_w, ratio_w, ratio_h;
+ * int32 equal_ratio, flip, has_range; float min2, max2} (32 bytes): when flip, (x1, x2) = (scaled_w - x2 - 1, scaled_w - x1 - 1); when
+ * has_range the box lives iff min2 < (x2-x1+1)*(y2-y1+1) < max2, both strict; then x *= ratio_w, y *= (equal_ratio ? ratio_w : ratio_h).
+ * classes: ascending int32 [C]; a label outside it, a failed range test and padding are written as box 0, score -1, label 0,
+ * source -1, view -1.
+ * fiber_det_aug_merge replaces merge_result_from_multi_scales' per-class boxlist_nms (box_aug.py:175-246) for nms_type "nms" (mode 0:
+ * greedy, suppress iff IoU > thresh, csrc/cuda/nms.cu:15-23) and "vote" (mode 1: bbox_vote, box_aug.py:249-295: the best remaining
+ * candidate and every remaining one with IoU >= thresh TO IT leave as one cluster; a cluster of more than one becomes
+ * sum(score * box) / sum(score) in fp32 under the leader's score).  Input: each image's candidates SORTED by (label ascending, score
+ * descending), dead slots under a label >= 2^30; classes ascending without repeats; state int32 [B,T] ZEROED by the caller.  One
+ * workgroup per (class, image) finds its segment by binary search and loops once per kept box or cluster.  Output: state 1 = kept (its
+ * box in out_boxes fp32 [B,T,4], written for kept slots only), 2 = suppressed or merged away, 0 = not of any class in the table.
+ * The reduction order is fixed: two runs give the same bits.  thresh <= 0 (no suppression: the caller skips the launch), mode outside
+ * {0, 1}, T > fiber_det_aug_max_candidates(), B > 65535, NULL or misaligned pointers -> 1; B, T, Nv or C == 0 -> 0 without a launch.
+ * NaN scores or unsorted input give an unspecified result, never an out-of-bounds access. */
+int fiber_det_aug_max_candidates(void);
+int fiber_det_aug_collect(const float* boxes, const float* scores, const int* labels, const int* source, const void* table,
+                          const int* classes, float* out_boxes, float* out_scores, int* out_labels, int* out_source, int* out_view, int B,
+                          int Nv, int T, int offset, int view, int C, fiber_stream_t stream);
+int fiber_det_aug_merge(const float* boxes, const float* scores, const int* labels, const int* classes, int* state, float* out_boxes,
+                        int B, int T, int C, float thresh, int mode, fiber_stream_t stream);
+
 /* Phrase-grounding evaluation (csrc/geval.hip); file:line relative to the reference's fine_grained/maskrcnn_benchmark/.  One wave per
  * (image, phrase); nothing crosses to the host.  fiber_ground_recall replaces engine/inference.py:311-327 (flickr_post_process),
  * data/datasets/evaluation/flickr/flickr_eval.py:173-204 and :365-383 (box_iou, the recall@k tally), data/datasets/refexp.py:58-74
