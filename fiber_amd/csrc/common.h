@@ -195,6 +195,17 @@ __device__ __forceinline__ void lds_dma16(const void* base, unsigned lane_byte_o
   const unsigned m = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)(char*)lds_wave_base);
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m), "v"(lane_byte_off), "s"(base) : "memory");
 }
+// The same with the LDS address of the wave's 1 KB given as a number: no generic -> LDS pointer conversion (a null test and a select per
+// request) in a K loop that issues several of them per tile.
+__device__ __forceinline__ void lds_dma16_at(const void* base, unsigned lane_byte_off, unsigned lds_addr) {
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(lane_byte_off), "s"(base) : "memory");
+}
+// ... at lds_addr + OFF, OFF a compile-time constant: the add writes M0 directly (one scalar instruction per request)
+template <unsigned OFF>
+__device__ __forceinline__ void lds_dma16_at(const void* base, unsigned lane_byte_off, unsigned lds_addr) {
+  if constexpr (OFF == 0) lds_dma16_at(base, lane_byte_off, lds_addr);
+  else asm volatile("s_add_u32 m0, %0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(lane_byte_off), "s"(base), "n"(OFF) : "memory", "scc");
+}
 // The same with a 64-bit per-lane source address (used where lanes of one instruction read from unrelated buffers).
 __device__ __forceinline__ void lds_dma16_v(const void* lane_src, void* lds_wave_base) {
   const unsigned m = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) char*)(char*)lds_wave_base);

@@ -526,6 +526,18 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_wide_persist_kernel(Gemm
 // flight and is followed by a barrier before the NEXT phase reads what it retired (RAW rule of the guide: wait in phase p, read in
 // p+1; the group that runs one barrier behind passes its own wait before the leading group's read).  WAR: a half-tile is
 // re-staged two or three phases after its last ds_read.  Epilogue stores / residual loads only make the counted waits stricter.
+//
+// Loop structure (profiles/nt_lean_loop.md).  The four phases above are one body, ktile<SEEDED, STEADY>, instantiated three times per output
+// tile of nk K tiles:  K tile 0 seeded and general;  K tiles 1 .. nk - 3 in a steady loop of their own;  the last two (all of them for
+// nk <= 3) general.  With the cursor one and two K tiles ahead, the steady K tiles request only K tiles of their own output tile, so their
+// loop holds nothing that is known before it: no kt == 0 test, no end-of-tile test, no aim(), no past-the-end clamp.  What a request needs
+// is kept ready in scalar registers: two running 64-bit source pointers (+ BK per K tile) and the LDS addresses of the wave's units AS
+// NUMBERS, so a request is s_add_u32 m0 / s_nop / global_load_lds_dwordx4 (lds_dma16_at<OFF>, common.h) with no generic -> LDS pointer
+// conversion; the fragment reads take numeric addresses too (one add per k step and operand, the rest immediate offsets).  Steady K tile:
+// 18 scalar ALU instructions and 4 VALU beside 64 MFMAs, 24 ds_read_b128 and 8 requests (71 and 6 in the one general loop this replaces).  The general code steps the tile coordinates of the workgroup (ids advance by P) instead of dividing, and
+// recomputes the per-lane row offsets only into or out of a tile that is ragged in M or reaches past N: for a full tile aim() is two
+// pointer updates.  The stage parity is a toggled offset: the two-K-tile unroll with both stages as constants spills
+// (tools/experiments/gemm_nt_q8_unroll2.patch).
 template <int EPI, bool HAS_R, bool HAS_RS, bool TRACE = false>
 __global__ __launch_bounds__(512) void gemm_nt_q8_kernel(GemmArgs a) {
   constexpr int BM = 256, BN = 256, WN = 4;
@@ -553,39 +565,67 @@ __global__ __launch_bounds__(512) void gemm_nt_q8_kernel(GemmArgs a) {
   const int lr = lane >> 3;
   const unsigned csw = (unsigned)(((lane & 7) ^ (((wave & 1) << 2) + (lr >> 1))) << 4);     // swizzled 16-B chunk, same for all 8 units
   const int ra0 = wave * 8, rb0 = (wave >> 2) * 64 + (wave & 3) * 8;                          // unit base rows (half 0, unit 0)
-  const bf16* xbase; const bf16* wbase;                  // origins of the cursor's output tile
+  // The cursor (the K tile being requested) is kept as what a request needs, all wave-uniform: two running source pointers (the cursor's K
+  // tile of the X and W panels of its output tile) and the LDS addresses, as numbers, of the wave's first A and W unit in the cursor's stage.
+  // A request is then one scalar add into M0 (common.h lds_dma16_at<OFF>) and the DMA instruction.
+  constexpr unsigned STAGEB = STAGE * 2;                  // bytes per ring stage
+  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
+  const unsigned la = lds0 + ra0 * (BK * 2), lb = lds0 + (BM + rb0) * (BK * 2);
+  const bf16* px; const bf16* pw;
+  unsigned c_st = 0, c_la = la, c_lb = lb;               // cursor's stage (byte offset 0 / STAGEB) and unit addresses in it
   unsigned xo[2][2], wo[2][2];                           // per-lane byte offsets [half][unit]
-  int c_seq = 0, c_kt = 0, c_g = 0;                      // cursor: output tile, K tile in it, ring counter (buffer = c_g & 1)
+  int c_seq = 0, c_kt = 0;                               // cursor: output tile of this workgroup, K tile in it
+  // A workgroup's tile ids advance by P: (row tile, column tile) are stepped, not divided out.
+  const int stepM = P / tilesN, stepN = P % tilesN;
+  auto next_tile = [&](int& tm, int& tn) {
+    tm += stepM; tn += stepN;
+    if (tn >= tilesN) { tn -= tilesN; ++tm; }
+  };
+  int c_tm = first / tilesN, c_tn = first % tilesN;
+  bool c_clamped = true;                                  // xo / wo are not (yet) those of a full tile
   auto aim = [&]() {
-    const int id = first + c_seq * P;
-    const int m0 = (id / tilesN) * BM, n0 = (id % tilesN) * BN;
-    xbase = a.X + (size_t)m0 * a.ldx;
-    wbase = a.W + (size_t)n0 * a.ldw;
-    const int xlim = a.M - 1 - m0, wlim = a.N - 1 - n0;
+    const int m0 = c_tm * BM, n0 = c_tn * BN;
+    px = a.X + (size_t)m0 * a.ldx;
+    pw = a.W + (size_t)n0 * a.ldw;
+    // the per-lane offsets of all full tiles are the same: recomputed only into or out of a tile that is ragged in M or reaches past N
+    const bool ragged = m0 + BM > a.M || n0 + BN > a.N;
+    if (ragged || c_clamped) {
+      const int xlim = a.M - 1 - m0, wlim = a.N - 1 - n0;
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
+      for (int h = 0; h < 2; ++h)
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        xo[h][u] = (unsigned)(min(u * 128 + h * 64 + ra0 + lr, xlim) * a.ldx) * 2u + csw;
-        wo[h][u] = (unsigned)(min(u * 128 + h * 32 + rb0 + lr, wlim) * a.ldw) * 2u + csw;
-      }
+        for (int u = 0; u < 2; ++u) {
+          xo[h][u] = (unsigned)(min(u * 128 + h * 64 + ra0 + lr, xlim) * a.ldx) * 2u + csw;
+          wo[h][u] = (unsigned)(min(u * 128 + h * 32 + rb0 + lr, wlim) * a.ldw) * 2u + csw;
+        }
+    }
+    c_clamped = ragged;
   };
+  auto flip_stage = [&]() { c_st ^= STAGEB; c_la = la + c_st; c_lb = lb + c_st; };
   auto advance = [&]() {                                  // after the last half-tile (A1) of the cursor's K tile
-    ++c_g;
+    flip_stage();
     if (++c_kt == nk) {
-      if (c_seq + 1 < T) { c_kt = 0; ++c_seq; aim(); }
+      if (c_seq + 1 < T) { c_kt = 0; ++c_seq; next_tile(c_tm, c_tn); aim(); }
       else c_kt = nk - 1;                                 // past the end: keep re-requesting the last K tile into buffers that are
-    }                                                     // free by construction (no "anything left?" test in the phases)
+    } else {                                              // free by construction (no "anything left?" test in the phases)
+      px += BK; pw += BK;
+    }
   };
-  auto stageA = [&](int h) {
-    bf16* st = smem + (c_g & 1) * STAGE;
-    lds_dma16(xbase + c_kt * BK, xo[h][0], st + (h * 64 + ra0) * BK);
-    lds_dma16(xbase + c_kt * BK, xo[h][1], st + (128 + h * 64 + ra0) * BK);
+  auto advance_steady = [&]() {                           // the same where the next K tile is known to lie in the same output tile; the
+    flip_stage();                                         // caller steps c_kt once for the whole steady loop
+    px += BK; pw += BK;
   };
-  auto stageW = [&](int j) {
-    bf16* st = smem + (c_g & 1) * STAGE + BM * BK;
-    lds_dma16(wbase + c_kt * BK, wo[j][0], st + (j * 32 + rb0) * BK);
-    lds_dma16(wbase + c_kt * BK, wo[j][1], st + (128 + j * 32 + rb0) * BK);
+  constexpr std::integral_constant<int, 0> I0{};
+  constexpr std::integral_constant<int, 1> I1{};
+  auto stageA = [&](auto hc) {
+    constexpr unsigned h = decltype(hc)::value;
+    lds_dma16_at<h * 64 * BK * 2>(px, xo[h][0], c_la);
+    lds_dma16_at<(128 + h * 64) * BK * 2>(px, xo[h][1], c_la);
+  };
+  auto stageW = [&](auto jc) {
+    constexpr unsigned j = decltype(jc)::value;
+    lds_dma16_at<j * 32 * BK * 2>(pw, wo[j][0], c_lb);
+    lds_dma16_at<(128 + j * 32) * BK * 2>(pw, wo[j][1], c_lb);
   };
 
   // ---- MFMA side
@@ -597,19 +637,32 @@ __global__ __launch_bounds__(512) void gemm_nt_q8_kernel(GemmArgs a) {
   q8_acc_t acc[8][4];
   const int frow = lane & 15, fk = lane >> 4;
   bf16x8 fa[4][2], fb[2][4];                             // A half: [16-row tile][k step];  both W halves: [half][2 * k step + 16-column tile]
-  auto readA = [&](const bf16* sb, int h) {
+  // Read addresses as numbers too: swz(row0 + 16 t + frow, c) = swz(frow, c) + (row0 + 16 t) * BK for row0 a multiple of 16 (the swizzle term
+  // (row >> 1) & 7 is that of frow), so a lane needs one byte address per k step and operand, plus the stage being read; every other term is an
+  // immediate offset of the ds_read_b128.
+  typedef __attribute__((address_space(3))) const bf16x8 lds_bf16x8;
+  typedef __attribute__((address_space(3))) const char lds_char;
+  unsigned rda[2], rdw[2];
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
+  for (int ks = 0; ks < 2; ++ks) {
+    rda[ks] = lds0 + (unsigned)(wm * WTM * BK + swz(frow, ks * 4 + fk)) * 2u;
+    rdw[ks] = lds0 + (unsigned)((BM + wn * WTN) * BK + swz(frow, ks * 4 + fk)) * 2u;
+  }
+  auto readA = [&](unsigned stb, int h) {
 #pragma unroll
-      for (int it = 0; it < 4; ++it)
-        fa[it][ks] = *reinterpret_cast<const bf16x8*>(sb + swz(wm * WTM + h * 64 + it * 16 + frow, ks * 4 + fk));
+    for (int ks = 0; ks < 2; ++ks) {
+      lds_char* p = (lds_char*)(rda[ks] + stb);
+#pragma unroll
+      for (int it = 0; it < 4; ++it) fa[it][ks] = *(lds_bf16x8*)(p + (h * 64 + it * 16) * BK * 2);
+    }
   };
-  auto readW = [&](const bf16* sb, int j) {
+  auto readW = [&](unsigned stb, int j) {
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
+    for (int ks = 0; ks < 2; ++ks) {
+      lds_char* p = (lds_char*)(rdw[ks] + stb);
 #pragma unroll
-      for (int jt = 0; jt < 2; ++jt)
-        fb[j][ks * 2 + jt] = *reinterpret_cast<const bf16x8*>(sb + BM * BK + swz(wn * WTN + j * 32 + jt * 16 + frow, ks * 4 + fk));
+      for (int jt = 0; jt < 2; ++jt) fb[j][ks * 2 + jt] = *(lds_bf16x8*)(p + (j * 32 + jt * 16) * BK * 2);
+    }
   };
   // bias of column block j in accumulator layout (seed_sel below): scalar loads, a one-of-four select each
   // N need only be a multiple of 64 (a wave's 64 columns are then all inside or all outside): the waves of the last tile column
@@ -691,8 +744,8 @@ __global__ __launch_bounds__(512) void gemm_nt_q8_kernel(GemmArgs a) {
 
   // ---- prologue: K tile 0 complete, A0 / W0 of K tile 1 requested (what the steady state has issued before P1 of K tile 0)
   aim();
-  stageA(0); stageW(0); stageW(1); stageA(1); advance();
-  stageA(0); stageW(0);
+  stageA(I0); stageW(I0); stageW(I1); stageA(I1); advance();
+  stageA(I0); stageW(I0);
   asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
@@ -703,7 +756,7 @@ __global__ __launch_bounds__(512) void gemm_nt_q8_kernel(GemmArgs a) {
   // the two epilogues ran one after the other with one wave per SIMD (trace: 2 x 11.2 k ticks per GELU tile, K loop 27 k).
   const bool keep_stagger = (a.act & 0x4000) != 0;
   if (keep_stagger && wm == 1) { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
-  int g = 0;
+  unsigned r_st = 0;                                      // ring stage being read (byte offset 0 / STAGEB): flips per K tile
   // TRACE build (tools/gemm_trace.py q8): s_memtime ticks per wave summed over its K tiles -- for each of the four phases
   // [4p + 0] load half (reads + DMA issued AND the reads returned: s_memtime drains lgkmcnt)  [4p + 1] wait + first barrier
   // [4p + 2] MFMA issue  [4p + 3] second barrier;  [16] epilogue
@@ -719,85 +772,101 @@ __global__ __launch_bounds__(512) void gemm_nt_q8_kernel(GemmArgs a) {
       t0 = t;
     }
   };
+  // One K tile (four phases).  SEEDED: the first K tile of an output tile (its MFMAs take the bias seed as C).  STEADY: the cursor is known to
+  // stay inside its output tile (advance_steady).
+  int n0w = 0;                                            // first column of the wave in the output tile being computed
+  auto ktile = [&](auto seeded_c, auto steady_c) __attribute__((always_inline)) {
+    constexpr bool SEEDED = decltype(seeded_c)::value, STEADY = decltype(steady_c)::value;
+    const unsigned sb = r_st;
+    // P1: quadrant (0, 0)
+    readW(sb, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    readA(sb, 0);
+    stageW(I1);
+    mark(0);
+    if constexpr (SEEDED) {
+      const SeedRaw raw = seed_raw(n0w, 0);
+      bar_load(false);
+      mark(1);
+      mma_seeded(0, 0, seed_sel(raw));
+    } else {
+      bar_load(false);
+      mark(1);
+      mma(0, 0);
+    }
+    mark(2);
+    bar_math();
+    mark(3);
+    // P2: quadrant (0, 1)
+    readW(sb, 1);
+    stageA(I1);
+    if constexpr (STEADY) advance_steady(); else advance();
+    mark(4);
+    if constexpr (SEEDED) {
+      const SeedRaw raw = seed_raw(n0w, 1);
+      bar_load(true);
+      mark(5);
+      mma_seeded(0, 1, seed_sel(raw));
+    } else {
+      bar_load(true);
+      mark(5);
+      mma(0, 1);
+    }
+    mark(6);
+    bar_math();
+    mark(7);
+    // P3: quadrant (1, 1)
+    readA(sb, 1);
+    stageA(I0);
+    mark(8);
+    if constexpr (SEEDED) {
+      const SeedRaw raw = seed_raw(n0w, 1);
+      bar_load(false);
+      mark(9);
+      mma_seeded(1, 1, seed_sel(raw));
+    } else {
+      bar_load(false);
+      mark(9);
+      mma(1, 1);
+    }
+    mark(10);
+    bar_math();
+    mark(11);
+    // P4: quadrant (1, 0) -- W half 0 is still in registers
+    stageW(I0);
+    mark(12);
+    if constexpr (SEEDED) {
+      const SeedRaw raw = seed_raw(n0w, 0);
+      bar_load(true);
+      mark(13);
+      mma_seeded(1, 0, seed_sel(raw));
+    } else {
+      bar_load(true);
+      mark(13);
+      mma(1, 0);
+    }
+    mark(14);
+    bar_math();
+    mark(15);
+    r_st ^= STAGEB;
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  // With K tile kt in flight the cursor is kt + 1 in P1 / P2 and kt + 2 in P3 / P4: the K tiles 1 .. nk - 3 of an output tile request only K
+  // tiles of the same output tile and are never seeded.  They run in a loop of their own with nothing in it that is known before the loop; the
+  // first K tile and the last two keep the general code (nk <= 3 never enters the steady loop).
+  const int n_steady = max(nk - 3, 0);
+  int e_tm = first / tilesN, e_tn = first % tilesN;       // the output tile being computed
   for (int seq = 0; seq < T; ++seq) {
-    const int id = first + seq * P;
-    const int tm0 = (id / tilesN) * BM, tn0 = (id % tilesN) * BN;
-    const int n0w = tn0 + wn * WTN;
+    const int tm0 = e_tm * BM, tn0 = e_tn * BN;
+    n0w = tn0 + wn * WTN;
     if (!keep_stagger && wm == 1) { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
     if constexpr (TRACE) { kc0 = __builtin_amdgcn_s_memtime(); kr0 = __builtin_amdgcn_s_memrealtime(); }
-    for (int kt = 0; kt < nk; ++kt, ++g) {
-      const bf16* sb = smem + (g & 1) * STAGE;
-      // P1: quadrant (0, 0)
-      readW(sb, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      readA(sb, 0);
-      stageW(1);
-      mark(0);
-      if (kt == 0) {
-        const SeedRaw raw = seed_raw(n0w, 0);
-        bar_load(false);
-        mark(1);
-        mma_seeded(0, 0, seed_sel(raw));
-      } else {
-        bar_load(false);
-        mark(1);
-        mma(0, 0);
-      }
-      mark(2);
-      bar_math();
-      mark(3);
-      // P2: quadrant (0, 1)
-      readW(sb, 1);
-      stageA(1);
-      advance();
-      mark(4);
-      if (kt == 0) {
-        const SeedRaw raw = seed_raw(n0w, 1);
-        bar_load(true);
-        mark(5);
-        mma_seeded(0, 1, seed_sel(raw));
-      } else {
-        bar_load(true);
-        mark(5);
-        mma(0, 1);
-      }
-      mark(6);
-      bar_math();
-      mark(7);
-      // P3: quadrant (1, 1)
-      readA(sb, 1);
-      stageA(0);
-      mark(8);
-      if (kt == 0) {
-        const SeedRaw raw = seed_raw(n0w, 1);
-        bar_load(false);
-        mark(9);
-        mma_seeded(1, 1, seed_sel(raw));
-      } else {
-        bar_load(false);
-        mark(9);
-        mma(1, 1);
-      }
-      mark(10);
-      bar_math();
-      mark(11);
-      // P4: quadrant (1, 0) -- W half 0 is still in registers
-      stageW(0);
-      mark(12);
-      if (kt == 0) {
-        const SeedRaw raw = seed_raw(n0w, 0);
-        bar_load(true);
-        mark(13);
-        mma_seeded(1, 0, seed_sel(raw));
-      } else {
-        bar_load(true);
-        mark(13);
-        mma(1, 0);
-      }
-      mark(14);
-      bar_math();
-      mark(15);
-    }
+    ktile(yes, no);
+    for (int i = 0; i < n_steady; ++i) ktile(no, yes);
+    c_kt += n_steady;
+    for (int kt = 1 + n_steady; kt < nk; ++kt) ktile(no, no);
+    next_tile(e_tm, e_tn);
     if constexpr (TRACE) { kc += __builtin_amdgcn_s_memtime() - kc0; kr += __builtin_amdgcn_s_memrealtime() - kr0; }
     if (!keep_stagger && wm == 0) { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
     if constexpr (TRACE) t0 = __builtin_amdgcn_s_memtime();

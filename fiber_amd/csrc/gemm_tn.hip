@@ -72,12 +72,6 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* p, int hi_off) {
   return __builtin_bit_cast(bf16x8, o);
 }
 
-// lds_dma16 (common.h) with the LDS address of the wave's 1 KB given as a number: no generic -> LDS pointer conversion (a null test and a select
-// per request) in a loop that issues four of them per 32-row tile
-__device__ __forceinline__ void lds_dma16_at(const void* base, unsigned lane_byte_off, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(lane_byte_off), "s"(base) : "memory");
-}
-
 // TS: output tile edge (256: 8 waves, 128: 4 waves).  BKM: rows of dY / X per K tile.  NS: LDS stages.
 // STAG (TS = 256, BKM = 32, NS = 5): two wave groups one phase apart over the ring, one workgroup per CU (see the loop).
 // plain ring (TS = 128, BKM = 32, NS = 4): the narrow weights are pure streaming problems (2 x 256 B per row of M against 128 x 128

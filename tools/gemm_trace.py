@@ -30,6 +30,10 @@ def q8(M, N, K, act=0):
     print(f"in-kernel clock over the K loops: median {clk.median():.3f} GHz (min {clk.min():.3f}, max {clk.max():.3f}; 64 waves)")
 
 
-for shp in ((294912, 2048, 512), (294912, 512, 2048), (73728, 1024, 4096)):
-    q8(*shp, 0)
-q8(294912, 2048, 512, 1)
+if len(sys.argv) > 2:                                       # python tools/gemm_trace.py q8 M,N,K [M,N,K ...]
+    for arg in sys.argv[2:]:
+        q8(*(int(v) for v in arg.split(",")), 0)
+else:
+    for shp in ((294912, 2048, 512), (294912, 512, 2048), (73728, 1024, 4096)):
+        q8(*shp, 0)
+    q8(294912, 2048, 512, 1)
