@@ -176,12 +176,16 @@ extern "C" int fiber_fold_rows_f32(const float* part, float* out, int rows, int 
 
 // out[j] = sum over the rows r with labels[r] != ignore_index of x[r, j] (x: bf16 [rows, V], the dlogits fiber_ce_bwd_bf16 wrote: its other
 // rows are zero).  workspace: fp32 [fiber_colsum_labelled_slabs(rows) * V].
-extern "C" int fiber_colsum_labelled_slabs(int rows) { return rows >= 4096 ? 8 : rows >= 512 ? 4 : 1; }
+// A slab's row list lives in LDS (one int per row of the slab): fiber_colsum_labelled_max_rows() is the largest row count whose slab plan
+// fits; callers with more rows sum the columns another way (the entry point refuses them with FIBER_EINVAL).
+constexpr int LABELLED_LIST_ROWS = 60 * 1024 / (int)sizeof(int), LABELLED_MAX_SLABS = 8;
+extern "C" int fiber_colsum_labelled_slabs(int rows) { return rows >= 4096 ? LABELLED_MAX_SLABS : rows >= 512 ? 4 : 1; }
+extern "C" int fiber_colsum_labelled_max_rows(void) { return LABELLED_MAX_SLABS * LABELLED_LIST_ROWS; }
 extern "C" int fiber_colsum_labelled_bf16(const void* x, const long long* labels, float* out, float* workspace, int rows, int V,
                                           long long ignore_index, hipStream_t stream) {
   if (rows <= 0 || V <= 0) return FIBER_OK;
   const int slabs = fiber_colsum_labelled_slabs(rows), rps = cdiv(rows, slabs);
-  if ((size_t)rps * sizeof(int) > 60 * 1024) return FIBER_EINVAL;
+  if (rps > LABELLED_LIST_ROWS) return FIBER_EINVAL;
   float* part = slabs > 1 ? workspace : out;
   if (slabs > 1 && !workspace) return FIBER_EINVAL;
   hipLaunchKernelGGL(colsum_labelled_kernel, dim3(cdiv(V, 256), slabs), dim3(256), (size_t)rps * sizeof(int), stream, (const bf16*)x, labels, part,

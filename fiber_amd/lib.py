@@ -94,7 +94,7 @@ SIGNATURES = {
     "fiber_fpn_merge_bwd_bf16": [P, P, P, P, P, P, I, I, I, I, I, I],
 }
 # host-side helpers without a stream argument
-PLAIN = {"fiber_layernorm_bwd_grid": [I], "fiber_window_attn_bwd_slices": [I, I], "fiber_window_attn_colsum_rows": [I, I, I], "fiber_colsum_slabs": [I, I], "fiber_colsum_labelled_slabs": [I], "fiber_gemm_row_tile": [I, I, I], "fiber_gemm_tn_splits": [I, I, I],
+PLAIN = {"fiber_layernorm_bwd_grid": [I], "fiber_window_attn_bwd_slices": [I, I], "fiber_window_attn_colsum_rows": [I, I, I], "fiber_colsum_slabs": [I, I], "fiber_colsum_labelled_slabs": [I], "fiber_colsum_labelled_max_rows": [], "fiber_gemm_row_tile": [I, I, I], "fiber_gemm_tn_splits": [I, I, I],
          "fiber_adamw_chunk": [], "fiber_resample_ksize": [I, I], "fiber_resample_ksize_bilinear": [I, I], "fiber_dcn_dx_workspace": [I, I, I, I, I, I, I],
          "fiber_roberta_embed_bwd_workspace": [I, I, I], "fiber_ground_workspace": [I, I, I], "fiber_det_max_candidates": [], "fiber_det_merge_max_candidates": [], "fiber_det_aug_max_candidates": [],
          "fiber_ap_max_gt": [], "fiber_ap_chunk": [],

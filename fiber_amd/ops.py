@@ -382,15 +382,16 @@ class _LibLinear(torch.autograd.Function):
         x, w = ctx.saved_tensors
         dy2, x2 = dy.reshape(-1, dy.shape[-1]), x.reshape(-1, x.shape[-1])
         dx = dw = db = None
+        hint = _take_labelled_rows(dy2)                      # every backward empties the slot, with or without a bias to use it for
         with lib_gemm():
             if ctx.needs_input_grad[0]:
                 dx = torch.matmul(dy2, w).view(x.shape)
             if ctx.needs_input_grad[1]:
                 dw = torch.matmul(dy2.t(), x2)
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            hint = _take_labelled_rows(dy2)
-            if hint is not None:                             # dlogits of _CrossEntropy: its ignored rows are zero, only the labelled ones are read
-                lab, ignore = hint
+            # (more rows than the labelled-row kernel's slab plan holds: the plain sum, asked before any launch)
+            if hint is not None and dy2.is_cuda and dy2.dtype == BF16 and dy2.shape[0] <= lib.plain("fiber_colsum_labelled_max_rows"):
+                lab, ignore = hint                           # dlogits of _CrossEntropy: its ignored rows are zero, only the labelled ones are read
                 M, N = dy2.shape
                 slabs = lib.plain("fiber_colsum_labelled_slabs", M)
                 db32 = torch.empty(N, dtype=torch.float32, device=dy2.device)
@@ -403,18 +404,29 @@ class _LibLinear(torch.autograd.Function):
 
 
 # _CrossEntropy.backward -> the linear that produced the logits: "the rows of this gradient whose label is the ignore index are zero".
+# The statement is about the bytes the producer wrote, so it holds for the gradient a consumer receives only if that is the producer's
+# tensor UNCHANGED: same address and shape, and the version counter the tensor had at the offer.  Autograd's fan-in adds another
+# consumer's gradient into the first one in place, and a caller may write into a leaf's .grad (which is the producer's tensor): both
+# bump the counter (views share it), and the offer is void.  Like the column-sum slot below, an offer never outlives the backward
+# pass it was made in, and every _LibLinear.backward empties the slot; a missed hand-over only costs the plain column sum.
 _rows_tls = threading.local()
 
 
+def _clear_labelled_rows():
+    _rows_tls.slot = None
+
+
 def _offer_labelled_rows(dx, labels, ignore):
-    _rows_tls.slot = (dx.data_ptr(), tuple(dx.shape), labels, ignore)
+    """Called from inside a backward()."""
+    _rows_tls.slot = (dx.data_ptr(), tuple(dx.shape), dx._version, labels, ignore)
+    torch.autograd.Variable._execution_engine.queue_callback(_clear_labelled_rows)
 
 
 def _take_labelled_rows(t2d):
     h = getattr(_rows_tls, "slot", None)
     _rows_tls.slot = None
-    if h is not None and t2d.is_cuda and t2d.dtype == BF16 and t2d.is_contiguous() and h[0] == t2d.data_ptr() and h[1] == tuple(t2d.shape):
-        return h[2], h[3]
+    if h is not None and t2d.is_contiguous() and h[0] == t2d.data_ptr() and h[1] == tuple(t2d.shape) and h[2] == t2d._version:
+        return h[3], h[4]
     return None
 
 
@@ -618,8 +630,10 @@ def droppath_foldable(rows, rowscale, rs_value):
 
 # Column sums that a backward kernel produced together with its output (window attention: the qkv bias gradient).  The
 # producer leaves (data_ptr, shape, sums) here; the NEXT linear backward takes the slot -- and uses it only if it is about
-# the very tensor it received as dY.  Every linear backward clears the slot, so it can never be matched against a later
-# tensor that happens to reuse the address; a missed hand-over only costs the separate column-sum pass.
+# the very tensor it received as dY, unchanged: same address, same shape and the version counter it had at the offer (the
+# fan-in add of a second consumer's gradient happens in place, keeps the address and bumps the counter; see the labelled-rows
+# slot above).  Every linear backward clears the slot, so it can never be matched against a later tensor that happens to
+# reuse the address; a missed hand-over only costs the separate column-sum pass.
 _hint_tls = threading.local()          # one hand-over slot per autograd thread (one per device): no cross-thread coupling
 
 
@@ -629,15 +643,15 @@ def _clear_colsum():
 
 def _offer_colsum(t2d, sums):
     """Called from inside a backward(): the offer never outlives the autograd pass it was made in."""
-    _hint_tls.slot = (t2d.data_ptr(), tuple(t2d.shape), sums)
+    _hint_tls.slot = (t2d.data_ptr(), tuple(t2d.shape), t2d._version, sums)
     torch.autograd.Variable._execution_engine.queue_callback(_clear_colsum)
 
 
 def _take_colsum(t2d):
     h = getattr(_hint_tls, "slot", None)
     _hint_tls.slot = None
-    if h is not None and h[0] == t2d.data_ptr() and h[1] == tuple(t2d.shape):
-        return h[2]
+    if h is not None and h[0] == t2d.data_ptr() and h[1] == tuple(t2d.shape) and h[2] == t2d._version:
+        return h[3]
     return None
 
 

@@ -206,8 +206,10 @@ int fiber_ce_bwd_bf16(const void* logits, const long long* labels, const float* 
 /* pred (nullable, int32 [rows]) of fiber_ce_fwd_bf16: arg max of every labelled row, smallest index among equal maxima as torch.argmax has
  * it, -1 on ignored rows -- the MLM accuracy of the step (gadgets/my_metrics.py:5-28 via fiber_utils.py) without an argmax pass over all rows.
  * fiber_colsum_labelled_bf16: the decoder's bias gradient, column sums of dlogits over the labelled rows only (fiber_ce_bwd_bf16 wrote zeros into
- * the others; heads.py:47-62 MLMHead.bias); workspace fp32 [fiber_colsum_labelled_slabs(rows) * V]. */
+ * the others; heads.py:47-62 MLMHead.bias); workspace fp32 [fiber_colsum_labelled_slabs(rows) * V].  rows above
+ * fiber_colsum_labelled_max_rows() are refused with FIBER_EINVAL (a slab's row list would not fit in LDS). */
 int fiber_colsum_labelled_slabs(int rows);
+int fiber_colsum_labelled_max_rows(void);
 int fiber_colsum_labelled_bf16(const void* x, const long long* labels, float* out, float* workspace, int rows, int V,
                                long long ignore_index, fiber_stream_t stream);
 
