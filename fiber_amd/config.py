@@ -45,7 +45,7 @@ def make_config(**over):
 
 
 # Named task configs of the path built here (reference config.py:95-110 pre-training with / without ITC, :134-150 VQAv2,
-# :235-250 COCO caption fine-tuning, :273-291 its CIDEr-optimisation stage).
+# :153-231 the four retrieval fine-tunes, :235-250 COCO caption fine-tuning, :273-291 its CIDEr-optimisation stage).
 NAMED = {
     "task_pretrain_mlm_itm": dict(
         exp_name="mlm_itm", loss_names={"itm": 1, "mlm": 1}, draw_false_image=1, batch_size=4096, max_steps=100000,
@@ -67,6 +67,26 @@ NAMED = {
         max_steps=None, warmup_steps=0.1, learning_rate=1e-6, lr_mult_cross_modal=5, lr_mult_head=5, max_text_len=50,
         train_transform_keys=["albef_randaug"], val_transform_keys=["albef"], image_size=576, resolution_before=576,
         pretrained_vit=False, cider_path="coco-train-words.p"),
+    # retrieval fine-tunes (reference config.py:153-231); their metric is the recall of modules/retrieval_eval.py (get_recall_metric=True)
+    "task_finetune_irtr_itc_coco": dict(
+        exp_name="finetune_irtr_itc_coco", datasets=["coco"], loss_names={"itc": 1}, batch_size=1024, max_epoch=10, max_steps=None,
+        warmup_steps=0.1, learning_rate=2e-5, lr_mult_cross_modal=5, lr_mult_head=5, max_text_len=50,
+        train_transform_keys=["albef_randaug"], val_transform_keys=["albef"], image_size=576, pretrained_vit=False),
+    "task_finetune_irtr_itc_f30k": dict(
+        exp_name="finetune_irtr_itc_f30k", datasets=["f30k"], loss_names={"itc": 1}, batch_size=1024, max_epoch=10, max_steps=None,
+        warmup_steps=0.1, learning_rate=2e-5, lr_mult_cross_modal=5, lr_mult_head=5, max_text_len=50,
+        train_transform_keys=["albef_randaug"], val_transform_keys=["albef"], image_size=576, pretrained_vit=False,
+        resolution_before=576),
+    "task_finetune_irtr_itm_coco": dict(
+        exp_name="finetune_irtr_itm_coco", datasets=["coco"], loss_names={"itm": 1}, draw_false_image=1, batch_size=1024, max_epoch=10,
+        max_steps=None, warmup_steps=0.1, learning_rate=2e-5, lr_mult_cross_modal=5, lr_mult_head=5, max_text_len=50,
+        train_transform_keys=["albef_randaug"], val_transform_keys=["albef"], image_size=384, get_recall_metric_itc=False,
+        pretrained_vit=False),
+    "task_finetune_irtr_itm_f30k": dict(
+        exp_name="finetune_irtr_itm_f30k", datasets=["f30k"], loss_names={"itm": 1}, draw_false_image=1, batch_size=1024, max_epoch=10,
+        max_steps=None, warmup_steps=0.1, learning_rate=2e-5, lr_mult_cross_modal=5, lr_mult_head=5, max_text_len=50,
+        train_transform_keys=["albef_randaug"], val_transform_keys=["albef"], image_size=384, get_recall_metric_itc=False,
+        pretrained_vit=False),
 }
 
 

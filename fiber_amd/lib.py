@@ -82,6 +82,7 @@ SIGNATURES = {
     "fiber_det_aug_collect": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I],
     "fiber_det_aug_merge": [P, P, P, P, P, P, I, I, I, F, I],
     "fiber_ground_recall": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, DBL, I],
+    "fiber_retrieval_ranks": [P, P, P, P, P, P, P, I, I, C.c_longlong, I],
     "fiber_ap_match": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I],
     "fiber_ap_accumulate": [P, P, P, P, P, P, P, C.c_longlong, I, I, I, I],
     "fiber_atss_candidates_f32": [P, P, I, P, P, P, P, I, I, I, I],

@@ -6,7 +6,9 @@ configure_optimizers (:522).  Parameter names / shapes equal the reference's so 
 (`load_path`, ITC queue keys dropped as at :141-146).  Captioning: caption_mle training, beam-search decoding (infer_caption
 :369-429, on the causal attention kernels) and caption_cider, the CIDEr-optimisation stage (sampled decoding and the sequence
 log-probability loss on HIP, CIDEr-D scored on the host: modules/cider.py; it needs config["cider_path"]); caption_gold and NLVR2 raise if
-requested.
+requested.  Retrieval evaluation (modules/retrieval_eval.py) scores the image x text grid through encode_image_prefix / encode_text_prefix /
+score_pairs: the part of the fused branch below the first fusion block once per image and per text, the rest (_fused_blocks, which infer
+runs too) once per pair.
 """
 import os
 import types
@@ -300,15 +302,6 @@ class FIBERTransformerSS(LightningModule):
         # (no inter-workgroup waits), the library is left with the heads, which run after the join.  Parameter gradients are
         # accumulated by autograd on the parameters' own stream behind event waits, so DDP's bucket hooks see finished
         # gradients.  Not used while a hipGraph is being captured.
-        num_pre_text = self.num_text_layer - self.num_fuse_block
-
-        def text_prefix():
-            t = txt.embeddings(input_ids=text_ids)
-            e = txt.get_extended_attention_mask(text_masks, text_masks.size(), t.device)
-            for layer in txt.encoder.layer[:num_pre_text]:
-                t = layer(t, e)[0]
-            return t, e
-
         side = None
         if (self.config.get("overlap_text_stream", True) and not os.environ.get("FIBER_NO_OVERLAP")
                 and text_ids.is_cuda and not torch.cuda.is_current_stream_capturing()):
@@ -318,14 +311,89 @@ class FIBERTransformerSS(LightningModule):
             object.__setattr__(self, "_main_stream", main)     # parallel.wrap_ddp's comm hook orders buckets behind both streams
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                text_embeds, ext = text_prefix()
+                text_embeds, ext = self._text_prefix(text_ids, text_masks)
         else:
-            text_embeds, ext = text_prefix()
+            text_embeds, ext = self._text_prefix(text_ids, text_masks)
 
+        image_embeds = self._image_prefix(img)
+        image_embeds, text_embeds = self._fused_blocks(image_embeds, text_embeds, ext, side, main if side is not None else None)
+        text_embeds, image_embeds, cls_feats = self._cross_modal_heads(image_embeds, text_embeds)
+        return {"text_feats": text_embeds, "image_feats": image_embeds, "cls_feats": cls_feats, "text_labels": text_labels,
+                "text_ids": text_ids, "text_masks": text_masks, "image": img}
+
+    # ---- the fused branch in its pair-independent and pair-dependent parts: infer runs them back to back, the retrieval grid
+    # (encode_image_prefix / encode_text_prefix / score_pairs) runs the first two once per image / text and the rest once per pair
+    def _text_prefix(self, text_ids, text_masks):
+        """Embeddings and text layers 0 .. num_pre_text - 1 -> (tokens [T, S, Ht], extended attention mask)"""
+        txt = self.text_transformer
+        t = txt.embeddings(input_ids=text_ids)
+        e = txt.get_extended_attention_mask(text_masks, text_masks.size(), t.device)
+        for layer in txt.encoder.layer[:self.num_text_layer - self.num_fuse_block]:
+            t = layer(t, e)[0]
+        return t, e
+
+    def _image_prefix(self, img):
+        """Patch embedding, Swin stages 0-1 and stage-2 blocks 0 .. num_pre_block - 1 -> tokens [G, L2, C2]"""
+        vit = self.vit_model
         image_embeds = vit.patch_embed(img)
         for layer in vit.layers[:2]:
             image_embeds = layer(image_embeds)
+        blocks = vit.layers[2].blocks                        # (indexed, not sliced: a slice of a ModuleList builds a new module)
+        for i in range(min(8 + self.num_text_layer - self.num_fuse_block, len(blocks))):
+            image_embeds = blocks[i](image_embeds)
+        return image_embeds
 
+    def _cross_modal_heads(self, image_embeds, text_embeds):
+        """The two cross-modal transforms and poolers (fiber_module.py:348-361) -> (text_feats, image_feats, cls_feats)"""
+        text_embeds = ops.linear(text_embeds, self.cross_modal_text_transform.weight, self.cross_modal_text_transform.bias)
+        image_embeds = ops.linear(image_embeds, self.cross_modal_image_transform.weight, self.cross_modal_image_transform.bias)
+        cls_feats_text = self.cross_modal_text_pooler(text_embeds)
+        avg_image_feats = image_embeds.float().mean(1, keepdim=True)
+        cls_feats_image = self.cross_modal_image_pooler(avg_image_feats)
+        return text_embeds, image_embeds, torch.cat([cls_feats_text, cls_feats_image], dim=-1)
+
+    def _eval_only(self, what):
+        if self.training:
+            raise ValueError(f"{what} is evaluation-only (dropout and DropPath draw per batch row): call .eval() first")
+
+    def encode_image_prefix(self, img):
+        """Evaluation only.  img [G, 3, H, W] -> the image tokens [G, L2, C2] after stage-2 block num_pre_block - 1: everything of the
+        image stack that does not depend on the text it is paired with (14 of the 18 stage-2 blocks in the base model)."""
+        self._eval_only("encode_image_prefix")
+        return self._image_prefix(img)
+
+    def encode_text_prefix(self, text_ids, text_masks):
+        """Evaluation only.  -> (text tokens [T, S, Ht] after layer num_pre_text - 1, extended attention mask [T, 1, 1, S]): everything
+        of the text stack that does not depend on the image."""
+        self._eval_only("encode_text_prefix")
+        return self._text_prefix(text_ids, text_masks)
+
+    def score_pairs(self, image_prefix, text_prefix, ext, img_idx, txt_idx):
+        """Evaluation only.  ITM ranking score of the P pairs (image_prefix[img_idx[p]], text_prefix[txt_idx[p]]): the fusion blocks, the
+        cross-modal transforms and poolers on the gathered prefixes, then rank_output(cls_feats)[:, 0] (objectives.py:451-460) -> fp32 [P].
+        img_idx / txt_idx: int64 [P] on the prefixes' device."""
+        self._eval_only("score_pairs")
+        if not hasattr(self, "rank_output"):
+            raise ValueError("score_pairs needs the ITM head (itm_score / rank_output): config['loss_names']['itm'] > 0")
+        if img_idx.dim() != 1 or img_idx.shape != txt_idx.shape:
+            raise ValueError(f"score_pairs: img_idx {tuple(img_idx.shape)}, txt_idx {tuple(txt_idx.shape)}: two [P] index vectors")
+        image_embeds = image_prefix.index_select(0, img_idx)
+        text_embeds, e = text_prefix.index_select(0, txt_idx), ext.index_select(0, txt_idx)
+        image_embeds, text_embeds = self._fused_blocks(image_embeds, text_embeds, e)
+        cls_feats = self._cross_modal_heads(image_embeds, text_embeds)[2]
+        return self.rank_score(cls_feats)
+
+    def rank_score(self, cls_feats):
+        """rank_output(cls_feats)[:, 0] (objectives.py:451-460): the "match" row of the ITM classifier (fiber_module.py:112-114), in fp32 on
+        the library GEMM like the ITM head itself -> fp32 [P]"""
+        return ops.lib_linear(cls_feats.float(), self.rank_output.weight, self.rank_output.bias)[:, 0]
+
+    def _fused_blocks(self, image_embeds, text_embeds, ext, side=None, main=None):
+        """The pair-dependent part of the fused branch (fiber_module.py:327-346): stage-2 blocks num_pre_block.. with text layers
+        num_pre_text.., the stage-2 downsample, stage 3 with the top two text layers, and the join of the second stream.  image_embeds:
+        the tokens after stage-2 block num_pre_block - 1; text_embeds / ext: the text prefix (on `side` when one is given).  infer and
+        score_pairs both run this."""
+        vit, txt = self.vit_model, self.text_transformer
         # Fusion blocks: image block (reads the text tokens) and text layer (reads the image tokens) of one step are
         # independent of each other (fiber_module.py:327-346 evaluates both from the previous step's pair), so the text layer
         # runs on the second stream next to the much larger image block; two event waits per step keep the pair in lock step.
@@ -352,14 +420,12 @@ class FIBERTransformerSS(LightningModule):
                 new_text = layer(text_embeds, ext, encoder_hidden_states=image_embeds, image_alias_sink=sink, **kw)[0]
             return blk(sink[0] if sink else image_embeds, text_embeds, ext), new_text
 
-        num_pre_block = 8 + num_pre_text
-        for blk_cnt, blk in enumerate(vit.layers[2].blocks):
-            if blk_cnt == num_pre_block and side is not None:
-                ext.record_stream(main)
-            if blk_cnt < num_pre_block:
-                image_embeds = blk(image_embeds)
-            else:
-                image_embeds, text_embeds = fused_step(blk, txt.encoder.layer[blk_cnt - 8], image_embeds, text_embeds)
+        num_pre_block = 8 + self.num_text_layer - self.num_fuse_block
+        blocks = vit.layers[2].blocks
+        if len(blocks) > num_pre_block and side is not None:
+            ext.record_stream(main)
+        for blk_cnt in range(num_pre_block, len(blocks)):
+            image_embeds, text_embeds = fused_step(blocks[blk_cnt], txt.encoder.layer[blk_cnt - 8], image_embeds, text_embeds)
         if vit.layers[2].downsample is not None:
             image_embeds = vit.layers[2].downsample(image_embeds)
 
@@ -372,15 +438,7 @@ class FIBERTransformerSS(LightningModule):
             main.wait_stream(side)
             text_embeds.record_stream(main)
             ext.record_stream(main)
-
-        text_embeds = ops.linear(text_embeds, self.cross_modal_text_transform.weight, self.cross_modal_text_transform.bias)
-        image_embeds = ops.linear(image_embeds, self.cross_modal_image_transform.weight, self.cross_modal_image_transform.bias)
-        cls_feats_text = self.cross_modal_text_pooler(text_embeds)
-        avg_image_feats = image_embeds.float().mean(1, keepdim=True)
-        cls_feats_image = self.cross_modal_image_pooler(avg_image_feats)
-        cls_feats = torch.cat([cls_feats_text, cls_feats_image], dim=-1)
-        return {"text_feats": text_embeds, "image_feats": image_embeds, "cls_feats": cls_feats, "text_labels": text_labels,
-                "text_ids": text_ids, "text_masks": text_masks, "image": img}
+        return image_embeds, text_embeds
 
     def _text_stream(self, ref):
         """Second HIP stream for the text prefix (one per module, created on first use)."""

@@ -110,16 +110,29 @@ def set_metrics(pl_module):
 _EPOCH_VALUES = {"vqa": (("score", "score"),), "itc": (("i2t_accuracy", "i2t_accuracy"), ("t2i_accuracy", "t2i_accuracy"))}
 
 
+RECALL_TAGS = ("ir_r1", "ir_r5", "ir_r10", "tr_r1", "tr_r5", "tr_r10")      # the reference's return order
+
+
 def epoch_wrapup(pl_module):
     """End-of-epoch bookkeeping (reference fiber_utils.py:44-140): per active task log `<task>/<phase>/<metric>_epoch` and
     `<task>/<phase>/loss_epoch`, reset the running metrics, and log their sum as `<phase>/the_metric` -- the quantity
-    run.py:29-35's ModelCheckpoint monitors.  Retrieval recall (compute_itc_recall / compute_itm_recall) is outside the
-    fused-backbone path built here."""
+    run.py:29-35's ModelCheckpoint monitors.  With config["get_recall_metric"], outside training (fiber_utils.py:48-60): the retrieval
+    recalls of `pl_module.retrieval_data` (modules/retrieval_eval.py: by ITC features when config["get_recall_metric_itc"], else by the ITM
+    ranking score) are logged as `recalls/ir_r1 .. recalls/tr_r10`, and ir_r1 + tr_r1 enters `the_metric` -- as a device tensor, nothing is
+    read back here."""
     cfg = pl_module.hparams.config
     phase = "train" if pl_module.training else "val"
-    if cfg.get("get_recall_metric") and not pl_module.training:
-        raise NotImplementedError("retrieval-recall evaluation (objectives.py:266-499) is outside the hot path built here")
     the_metric = 0
+    if cfg.get("get_recall_metric") and not pl_module.training:
+        from . import retrieval_eval
+        data = getattr(pl_module, "retrieval_data", None)
+        if data is None:
+            raise ValueError("config['get_recall_metric'] needs the retrieval set attached as pl_module.retrieval_data "
+                             "(modules/retrieval_eval.py: RetrievalData / pack_retrieval_data)")
+        recalls = retrieval_eval.evaluate_retrieval(pl_module, data)
+        for tag, value in zip(RECALL_TAGS, recalls):
+            pl_module.log(f"recalls/{tag}", value)
+        the_metric = the_metric + recalls[0] + recalls[3]
     for task, weight in cfg["loss_names"].items():
         if weight <= 0:
             continue

@@ -2402,6 +2402,61 @@ def ground_recall(boxes, labels, count, gt, gt_count, cat_mask, topk, positives,
     return hit, best
 
 
+# ---- retrieval evaluation: rank of the first matching candidate per query and the recall@k tallies (csrc/retrieval.hip) ---------------
+RETRIEVAL_MAX_K = 8
+
+
+def _retrieval_ranks_host(scores, iids, tiids, ks):
+    """fiber_retrieval_ranks on CPU tensors, in torch: a stable descending sort per direction, then the position of the first match"""
+    def first_match(s, qid, cid):                            # s [Q, N], qid [Q], cid [N] -> int32 [Q]
+        Q, N = s.shape
+        if N == 0:
+            return torch.zeros(Q, dtype=torch.int32)
+        order = torch.sort(s, dim=1, descending=True, stable=True).indices
+        same = cid[order] == qid[:, None]
+        pos = torch.where(same, torch.arange(N)[None, :], torch.full((), N))
+        return pos.min(dim=1).values.to(torch.int32)
+    rank_tr = first_match(scores, iids, tiids)
+    rank_ir = first_match(scores.t(), tiids, iids)
+    hits = torch.stack([(rank_ir[:, None] < ks[None, :]).sum(0), (rank_tr[:, None] < ks[None, :]).sum(0)]).to(torch.int32)
+    return rank_tr, rank_ir, hits
+
+
+def retrieval_ranks(scores, iids, tiids, ks=(1, 5, 10)):
+    """Ranks and recall@k tallies of an image-text score matrix (objectives.py:361-383, :477-497 without topk).  scores fp32 [Ni, Nt]
+    (row = image, column = text; any row stride, unit column stride), iids int32 [Ni], tiids int32 [Nt]: the image id of each caption;
+    ks: up to 8 cut-offs (a sequence or an int32 tensor).  A query's candidates are ordered by descending score, equal scores by
+    ascending index; rank = position of the first candidate with the query's id (N when there is none), hit@k = rank < k.
+    -> (rank_tr int32 [Ni], rank_ir int32 [Nt], hits int32 [2, nk]: row 0 image retrieval, row 1 text retrieval).  Recall = hits / N (on the
+    device form it in fp64 and round once: torch's fp32 division there is not the correctly rounded one).  Two launches, no synchronisation; on CPU tensors the same in torch."""
+    if scores.dim() != 2 or scores.dtype != torch.float32:
+        raise ValueError(f"retrieval_ranks: scores {tuple(scores.shape)} {scores.dtype}: fp32 [Ni, Nt]")
+    Ni, Nt = scores.shape
+    dev = scores.device
+    if not isinstance(ks, torch.Tensor):
+        ks = torch.tensor([int(k) for k in ks], dtype=torch.int32, device=dev)
+    if iids.shape != (Ni,) or tiids.shape != (Nt,) or ks.dim() != 1 or iids.dtype != torch.int32 or tiids.dtype != torch.int32 or \
+            ks.dtype != torch.int32:
+        raise ValueError(f"retrieval_ranks: iids {tuple(iids.shape)} {iids.dtype}, tiids {tuple(tiids.shape)} {tiids.dtype}, ks "
+                         f"{tuple(ks.shape)} {ks.dtype} for scores {tuple(scores.shape)}: int32 [Ni], [Nt], [nk]")
+    nk = ks.numel()
+    if nk > RETRIEVAL_MAX_K:
+        raise ValueError(f"retrieval_ranks: {nk} cut-offs exceed the kernel's {RETRIEVAL_MAX_K}")
+    if any(t.device != dev for t in (iids, tiids, ks)):
+        raise ValueError("retrieval_ranks: the tensors lie on different devices")
+    if not scores.is_cuda:
+        return _retrieval_ranks_host(scores, iids, tiids, ks)
+    if Nt > 1 and scores.stride(1) != 1 or (Ni > 1 and scores.stride(0) < Nt):
+        scores = scores.contiguous()
+    ld = scores.stride(0) if Ni > 1 else max(Nt, 1)
+    rank_tr = torch.empty((Ni,), dtype=torch.int32, device=dev)
+    rank_ir = torch.empty((Nt,), dtype=torch.int32, device=dev)
+    hits = torch.empty((2, nk), dtype=torch.int32, device=dev)
+    lib.call("fiber_retrieval_ranks", lib.ptr(scores), lib.ptr(_c(iids)), lib.ptr(_c(tiids)), lib.ptr(_c(ks)), lib.ptr(rank_tr),
+             lib.ptr(rank_ir), lib.ptr(hits), Ni, Nt, int(ld), nk)
+    return rank_tr, rank_ir, hits
+
+
 # ---- box average precision: LVIS-protocol matching and precision / recall tables (csrc/apeval.hip) -----------------------------------
 def ap_max_gt():
     return int(lib.plain("fiber_ap_max_gt"))

@@ -448,6 +448,18 @@ int fiber_ground_recall(const float* boxes, const int* labels, const int* count,
                         const unsigned long long* cat_mask, const int* topk, int* hit, double* best, long long* positives, long long* totals,
                         int B, int D, int P, int G, int K, int ncat, double thresh, int mode, fiber_stream_t stream);
 
+/* Image-text retrieval evaluation (csrc/retrieval.hip); file:line relative to the reference's coarse_grained/fiber/modules/objectives.py.
+ * fiber_retrieval_ranks replaces :361-383 and :477-497 (six topk calls, the id gathers and the recall means) for one score matrix.
+ * scores fp32 [Ni,Nt] with row stride ld >= Nt elements (row = image, column = text), iids int32 [Ni], tiids int32 [Nt] (the image id of
+ * each caption), ks int32 [nk], nk <= 8.  A query orders its N candidates by descending score, equal scores by ascending candidate
+ * index; rank = 0-based position of the first candidate whose id equals the query's, N when none matches; hit@k = rank < k, also for
+ * k > N.  Comparisons with NaN are false.  rank_tr int32 [Ni] (an image against the captions), rank_ir int32 [Nt] (a caption against
+ * the images), hits int32 [2,nk]: row 0 = image retrieval, row 1 = text retrieval, OVERWRITTEN (zeroed on the stream, then integer
+ * atomic adds: two runs give the same bits).  Every element is written.  Two launches, nothing synchronises the host.
+ * nk > 8, negative sizes, ld < Nt, NULL or misaligned pointers -> 1. */
+int fiber_retrieval_ranks(const float* scores, const int* iids, const int* tiids, const int* ks, int* rank_tr, int* rank_ir, int* hits,
+                          int Ni, int Nt, long long ld, int nk, fiber_stream_t stream);
+
 /* Box average precision by the LVIS protocol (csrc/apeval.hip); file:line relative to the reference's
  * fine_grained/maskrcnn_benchmark/data/datasets/evaluation/lvis/lvis_eval.py.  Nothing crosses to the host.
  * fiber_ap_match replaces, for one batch, :137-148 (limit_dets_per_image), :237-241 (the federated filter), :293-317 (compute_iou) and
