@@ -31,6 +31,11 @@ DEFAULTS = dict(
     # (detached), the RL pass (repeated per beam; autograd sums the beams) and the MLE term, instead of the reference's 1 + beam + 1 samples
     # per image.  Each image then gets one DropPath draw instead of seven (beam 5), so the default keeps the reference's passes
     caption_cider_share_image=False,
+    # not a reference key: True = caption_test_step and the sampling half of compute_caption_cider decode through a KV cache
+    # (modules/caption_decode.py): one new token per step instead of the whole sequence, image keys / values projected once per image.
+    # The same function in evaluation up to bf16 rounding; in training mode the cached sampler draws WITHOUT dropout where the reference
+    # samples with the module in train mode, so the default keeps the reference's full recompute
+    caption_decode_cache=False,
 )
 
 

@@ -37,6 +37,8 @@ SIGNATURES = {
     "fiber_mha_causal_fwd_bf16": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, F, F, U64, P],
     "fiber_mha_bwd_bf16": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, F, F, U64, P],
     "fiber_mha_causal_bwd_bf16": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, F, F, U64, P],
+    "fiber_mha_decode_self_bf16": [P, P, P, P, I, I, I, I, I, I, I, F],
+    "fiber_mha_decode_cross_bf16": [P, P, P, I, I, I, I, I, I, I, F],
     "fiber_roberta_embed_fwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, F, U64, P],
     "fiber_roberta_embed_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, U64, P],
     "fiber_im2col_patch4": [P, P, I, I, I],

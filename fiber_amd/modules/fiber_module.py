@@ -232,14 +232,12 @@ class FIBERTransformerSS(LightningModule):
         attention kernels); layers 0..num_fuse-1 plain, the fusion layers below the top two cross-attend to their
         cross_modal_att_layers projection of the image tokens (DIM_IMG / 2 wide), the top two to the image tokens; every layer
         ends in its output LayerNorm."""
-        vit, txt = self.vit_model, self.text_transformer
+        txt = self.text_transformer
         if image_embeds is None:
             if img is None:
                 imgkey = f"image_{image_token_type_idx - 1}" if f"image_{image_token_type_idx - 1}" in batch else "image"
                 img = batch[imgkey][0]
-            image_embeds = vit.patch_embed(img)              # (absolute_pos_embed is None and pos_drop the identity in every FIBER config)
-            for layer in vit.layers:
-                image_embeds = layer(image_embeds)
+            image_embeds = self.caption_image_embeds(img)
         do_mlm = "_mlm" if mask_text else ""
         text_ids, text_labels, text_masks = batch[f"text_ids{do_mlm}"], batch[f"text_labels{do_mlm}"], batch["text_masks"]
         text_embeds = txt.embeddings(input_ids=text_ids)
@@ -257,6 +255,20 @@ class FIBERTransformerSS(LightningModule):
         cls_feats = self.cross_modal_text_pooler(text_embeds)
         return {"text_feats": text_embeds, "image_embeds": image_embeds, "cls_feats": cls_feats, "text_labels": text_labels,
                 "text_ids": text_ids, "text_masks": text_masks, "image": img}
+
+    def caption_image_embeds(self, img):
+        """The image side of infer_caption alone: the whole Swin stack without text -> tokens [B, Li, C_img]"""
+        vit = self.vit_model
+        image_embeds = vit.patch_embed(img)                  # (absolute_pos_embed is None and pos_drop the identity in every FIBER config)
+        for layer in vit.layers:
+            image_embeds = layer(image_embeds)
+        return image_embeds
+
+    def caption_decoder(self, image_embeds, rows_per_image):
+        """A KV-cached single-token decoder over infer_caption's text side for `rows_per_image` rows (beams) per image of image_embeds
+        [bs, Li, C_img] (modules/caption_decode.py): evaluation arithmetic whatever the module's mode."""
+        from .caption_decode import CaptionDecoder
+        return CaptionDecoder(self, image_embeds, rows_per_image)
 
     def infer(self, batch, mask_text=False, mask_image=False, image_token_type_idx=1, img=None, text_only=False,
               image_only=False):

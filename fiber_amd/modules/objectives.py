@@ -331,25 +331,50 @@ def _caption_cider_scores(scorer, tok, text_ids, gt_txt, beam_size):
     return scorer.compute_score(gts, res)[1]
 
 
+def _cached_feats(pl_module, image_embeds, beam_size):
+    """The per-step features of the two decoding loops from a KV-cached decoder -- anything with .step(tokens [N], parent [N] or None) ->
+    [N, H] -- instead of infer_caption on the ids so far: feats_at(i, ids, parent) -> [rows, 1, H] of position i.  Step 0 feeds ids[:, 0]
+    ([CLS]) to all bs * beam rows and hands back the first row of each image, as the loops expect bs rows there (beam - 1 redundant
+    single-token rows per image, once); later steps feed column i of the already reordered ids, with the reorder as `parent`."""
+    decoder = pl_module.caption_decoder(image_embeds, beam_size)
+
+    def feats_at(i, ids, parent):
+        if i == 0:
+            return decoder.step(ids[:, 0].repeat_interleave(beam_size, 0))[::beam_size, None]
+        return decoder.step(ids[:, i], parent)[:, None]
+    return feats_at
+
+
 @torch.no_grad()
 def _caption_sample(pl_module, tok, image, image_embeds, beam_size, max_len):
     """objectives.py:730-796: beam_size sampled continuations per image, [bs * beam, max_len] ids laid out image-major.  Step 0 runs on the
     two-token prefix [cls, pad] (with the image tower unless image_embeds is handed in) and draws beam_size tokens per image with replacement;
     every later step re-runs the causal text stack on the ids so far and draws one token per beam, ended beams are padded, and the loop stops
-    once all have ended.  The draws are ops.sample_rows (Gumbel-max on the dropout key stream) instead of softmax + torch.multinomial."""
+    once all have ended.  The draws are ops.sample_rows (Gumbel-max on the dropout key stream) instead of softmax + torch.multinomial.
+
+    config["caption_decode_cache"]: every step feeds ONE token per beam to pl_module.caption_decoder (an object with .step(tokens, parent),
+    modules/caption_decode.py) instead of re-running infer_caption on the ids so far.  The decoder is evaluation arithmetic: in training mode
+    the reference samples with dropout on (the module is in train mode), the cached sampler draws from the model WITHOUT dropout -- a stated
+    difference, like caption_cider_share_image, and the reason the flag is off by default."""
     bs, dev = image.size(0), image.device
     pad, sep, mask_id = tok.pad_token_id, tok.sep_token_id, tok.mask_token_id
     text_ids = torch.full((bs, max_len), pad, device=dev, dtype=torch.long)
     text_ids[:, 0] = tok.cls_token_id
-    b = {"image": [image], "text_ids": text_ids[:, :2], "text_labels": None, "text_masks": text_ids[:, :2] != pad}
-    first = pl_module.infer_caption(b, mask_text=False, mask_image=False, image_embeds=image_embeds)
-    image_embeds = first["image_embeds"].repeat_interleave(beam_size, 0)
-    b["text_masks"] = None
+    if pl_module.hparams.config.get("caption_decode_cache", False):
+        feats_at = _cached_feats(pl_module, pl_module.caption_image_embeds(image) if image_embeds is None else image_embeds, beam_size)
+    else:
+        b = {"image": [image], "text_ids": text_ids[:, :2], "text_labels": None, "text_masks": text_ids[:, :2] != pad}
+        first = pl_module.infer_caption(b, mask_text=False, mask_image=False, image_embeds=image_embeds)
+        image_embeds = first["image_embeds"].repeat_interleave(beam_size, 0)
+        b["text_masks"] = None
+
+        def feats_at(i, ids, parent):
+            b["text_ids"] = ids
+            infer = first if i == 0 else pl_module.infer_caption(b, mask_text=False, mask_image=False, image_embeds=image_embeds)
+            return infer["text_feats"][:, i:i + 1]
     end_seq = None
     for i in range(max_len - 1):
-        b["text_ids"] = text_ids
-        infer = first if i == 0 else pl_module.infer_caption(b, mask_text=False, mask_image=False, image_embeds=image_embeds)
-        logits = _head_logits_2d(pl_module, infer["text_feats"][:, i:i + 1])
+        logits = _head_logits_2d(pl_module, feats_at(i, text_ids, None))
         if i == 0:
             tokens, _, end_seq = ops.sample_rows(logits, beam_size, mask_id, pad_id=pad, sep_id=sep)      # [bs, beam]
             text_ids = text_ids.repeat_interleave(beam_size, 0)
@@ -429,7 +454,10 @@ def caption_test_step(pl_module, batch, output, beam_size=5):
     (text_masks None) and scores one position, the [MASK] logit forced to -10000; candidates are ranked by length-normalised
     log-probability, and the search stops early once every beam has ended.  Returns the captions (tokenizer.decode of beam 0, sep /
     cls -> pad, pad removed) and, not in the reference, the ids beam 0 generated (sep kept, padding after it) under `caption_ids`
-    ([B, max_text_len - 1])."""
+    ([B, max_text_len - 1]).
+
+    config["caption_decode_cache"]: one image pass, then one token per beam and step through pl_module.caption_decoder (_cached_feats) with
+    the beam reorder `top_prev` as its `parent`; the bookkeeping below is the same.  The same function up to bf16 rounding."""
     captions = []
     if pl_module.training:
         return {"image_ids": batch["iid"], "captions": captions, "caption_ids": None}
@@ -441,13 +469,21 @@ def caption_test_step(pl_module, batch, output, beam_size=5):
     text_ids[:, 0] = tok.cls_token_id
     search = bs * beam_size
     end_seq = torch.zeros(bs, dtype=torch.bool, device=dev)
-    first = pl_module.infer_caption(batch, mask_text=False, mask_image=False)
-    image_embeds = first["image_embeds"]
-    batch["text_masks"] = None
+    cached = bool(pl_module.hparams.config.get("caption_decode_cache", False))
+    if cached:
+        feats_at = _cached_feats(pl_module, pl_module.caption_image_embeds(batch["image_0" if "image_0" in batch else "image"][0]), beam_size)
+    else:
+        first = pl_module.infer_caption(batch, mask_text=False, mask_image=False)
+        image_embeds = first["image_embeds"]
+        batch["text_masks"] = None
+
+        def feats_at(i, ids, parent):
+            batch["text_ids"] = ids
+            infer = first if i == 0 else pl_module.infer_caption(batch, mask_text=False, mask_image=False, image_embeds=image_embeds)
+            return infer["text_feats"][:, i:i + 1]
+    parent = None
     for i in range(max_len - 1):
-        batch["text_ids"] = text_ids
-        infer = first if i == 0 else pl_module.infer_caption(batch, mask_text=False, mask_image=False, image_embeds=image_embeds)
-        logits = pl_module.mlm_score(infer["text_feats"][:, i:i + 1]).float()
+        logits = pl_module.mlm_score(feats_at(i, text_ids, parent)).float()
         logits[:, 0, tok.mask_token_id] = -10000
         logp = torch.log_softmax(logits, dim=-1)                                  # [N, 1, V]
         if i == 0:
@@ -457,8 +493,9 @@ def caption_test_step(pl_module, batch, output, beam_size=5):
             head_lengths = torch.ones_like(head_logp)
             text_ids = text_ids.view(bs, 1, -1).repeat(1, beam_size, 1).view(search, -1)
             padded = torch.full((search, 1), tok.pad_token_id, dtype=torch.long, device=dev)
-            hs = image_embeds.size(-1)
-            image_embeds = image_embeds.view(bs, 1, -1, hs).repeat(1, beam_size, 1, 1).view(search, -1, hs)
+            if not cached:
+                hs = image_embeds.size(-1)
+                image_embeds = image_embeds.view(bs, 1, -1, hs).repeat(1, beam_size, 1, 1).view(search, -1, hs)
         else:
             lengths = 1.0 - end_seq.to(logp.dtype)                                # ended beams add nothing
             logp = (logp * lengths[:, :, None] + head_logp[:, :, None]).view(bs, beam_size, 1, -1).permute(0, 2, 1, 3)
@@ -475,6 +512,7 @@ def caption_test_step(pl_module, batch, output, beam_size=5):
             prev_ended = end_seq.gather(0, top_prev).to(torch.long)
             tgt = (1 - prev_ended) * top_tokens + prev_ended * padded
             text_ids = text_ids.gather(0, top_prev.repeat(1, text_ids.size(1)))
+            parent = top_prev.view(-1)
         text_ids[:, i + 1] = tgt.view(-1)
         end_seq = (tgt == tok.sep_token_id) | (tgt == tok.pad_token_id)
         if i > 0 and bool(end_seq.all()):

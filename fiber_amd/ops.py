@@ -1423,6 +1423,115 @@ def mha_kv_packed(q, kv, kmask, B, heads, scale, p_drop=0.0, seed=0):
     return _MHAPacked.apply(q, kv, kmask, 1, B, heads, float(scale), float(p_drop), int(seed))
 
 
+# ---- single-token attention of the KV-cached caption decoder (csrc/attn_decode.hip): forward only -------------------------------------
+DECODE_MAX_LEN = 64          # the causal kernels' own limit
+DECODE_MAX_ROWS = 16         # rows (beams) per image the cross kernel serves from one K/V fetch
+
+
+def _decode_check(name, x, heads, what):
+    if x.dim() != 2 or x.stride(1) != 1 or heads < 1 or x.shape[1] % heads or x.shape[1] // heads not in (32, 64):
+        raise ValueError(f"{name}: {what} {tuple(x.shape)} strides {x.stride()} for {heads} heads: 2-D rows of heads * (32 | 64) channels")
+
+
+def _softmax_v(q, K, V, heads, scale, out_dtype, live=None):
+    """softmax(scale q.K^T) V per head for one query per row: q [N, C], K / V [N, L, C] -> [N, C]; live bool [N, L]: the keys that count (a
+    row without one gives 0) (host restatements)"""
+    N, L, C = K.shape
+    ct = torch.promote_types(q.dtype, torch.float32)
+    q, K, V = (x.to(ct).reshape(*x.shape[:-1], heads, C // heads) for x in (q, K, V))
+    s = torch.einsum("nhd,nlhd->nhl", q, K) * scale
+    if live is not None:
+        s = s.masked_fill(~live[:, None, :], float("-inf"))
+        V = torch.where(live[:, :, None, None], V, torch.zeros_like(V))
+    p = torch.softmax(s, -1)
+    if live is not None:
+        p = torch.where(live.any(1)[:, None, None], p, torch.zeros_like(p))
+    return torch.einsum("nhl,nlhd->nhd", p, V).reshape(N, C).to(out_dtype)
+
+
+def _mha_decode_self_host(qkv, cache, anc, t, heads, scale):
+    """fiber_mha_decode_self_bf16 on CPU tensors, in torch, the in-place cache append included"""
+    N, C = qkv.shape[0], cache.shape[2] // 2
+    slots = anc[:, :t].long() if anc is not None else torch.arange(N)[:, None].expand(N, t)
+    live = None
+    if anc is not None:                                                          # an entry outside [0, N): no key, never dereferenced
+        live = (anc[:, :t + 1] >= 0) & (anc[:, :t + 1] < N)
+        slots = torch.where(live[:, :t], slots, torch.arange(N)[:, None].expand(N, t))
+    past = cache[slots, torch.arange(t)[None, :]]                                # [N, t, 2C]: position j from slot anc[n, j]
+    new = qkv[:, C:3 * C]
+    kv = torch.cat([past, new[:, None].to(cache.dtype)], 1)                      # position t: the row's own k | v
+    o = _softmax_v(qkv[:, :C], kv[..., :C], kv[..., C:], heads, scale, qkv.dtype, live)
+    cache[:, t] = new.to(cache.dtype)
+    return o
+
+
+def mha_decode_self(qkv, cache, anc, t, heads, scale):
+    """Causal self-attention of ONE new token per row against that row's cache.  qkv [N, 3C] = [q | k | v] of the token at position t
+    (linear_packed; any row stride that is a multiple of 8), cache [N slots, Lmax, 2C] = [k | v] per position (one per layer, contiguous),
+    anc int32 [N, Lmax] or None.  Stores row n's k | v to cache[n, t] IN PLACE and returns softmax(scale q.K[0..t]).V [N, C], the key and
+    value of position j < t read from slot anc[n, j] (slot n without anc), position t taken from qkv: a beam reorder gathers the small anc
+    table, never a cache.  A position j <= t whose anc[n, j] is outside [0, N) (-1) is no key, as a padded key under infer_caption's text_masks:
+    it is skipped, position t itself included (its k | v are appended all the same); a live position t has anc[n, t] = n; a row without any
+    key gives 0.  Nothing beyond position t is read.  Lmax <= 64, head width 32 or 64; no gradient.  On CPU tensors the same in torch."""
+    t = int(t)
+    if cache.dim() != 3 or cache.shape[2] % 2:
+        raise ValueError(f"mha_decode_self: cache {tuple(cache.shape)}: [N, Lmax, 2C]")
+    N, Lmax, C = cache.shape[0], cache.shape[1], cache.shape[2] // 2
+    if qkv.dim() != 2 or qkv.shape != (N, 3 * C) or qkv.dtype != cache.dtype or qkv.device != cache.device:
+        raise ValueError(f"mha_decode_self: qkv {tuple(qkv.shape)} {qkv.dtype} for cache {tuple(cache.shape)} {cache.dtype}: [N, 3C], same type and device")
+    _decode_check("mha_decode_self", qkv[:, :C], heads, "q")
+    if not 0 <= t < Lmax or Lmax > DECODE_MAX_LEN:
+        raise ValueError(f"mha_decode_self: position {t} of {Lmax} (the kernel serves 0 <= t < Lmax <= {DECODE_MAX_LEN})")
+    if anc is not None and (anc.shape != (N, Lmax) or anc.dtype != torch.int32 or anc.device != cache.device):
+        raise ValueError(f"mha_decode_self: anc {tuple(anc.shape)} {anc.dtype}: int32 [N, Lmax] beside the cache")
+    if not cache.is_contiguous():
+        raise ValueError("mha_decode_self: the cache is appended in place and must be contiguous")
+    if not cache.is_cuda:
+        return _mha_decode_self_host(qkv, cache, anc, t, heads, scale)
+    if qkv.dtype != BF16:
+        raise ValueError(f"mha_decode_self: {qkv.dtype} on the device (bf16)")
+    if qkv.stride(0) % 8 or qkv.data_ptr() % 16:
+        qkv = _c(qkv)
+    if cache.data_ptr() % 16:
+        raise ValueError("mha_decode_self: the cache must start on a 16-byte boundary")
+    o = torch.empty((N, C), dtype=BF16, device=qkv.device)
+    lib.call("fiber_mha_decode_self_bf16", lib.ptr(qkv), lib.ptr(cache), lib.ptr(_c(anc) if anc is not None else None), lib.ptr(o), N, heads,
+             C // heads, t, Lmax, qkv.stride(0) if N > 1 else 3 * C, C, float(scale))
+    return o
+
+
+def _mha_decode_cross_host(q, kv, R, heads, scale):
+    """fiber_mha_decode_cross_bf16 on CPU tensors, in torch: row n against the K / V of image n // R"""
+    C = q.shape[1]
+    rep = kv.repeat_interleave(R, 0)
+    return _softmax_v(q, rep[..., :C], rep[..., C:], heads, scale, q.dtype)
+
+
+def mha_decode_cross(q, kv, rows_per_image, heads, scale):
+    """Text->image cross-attention of one new token per row: q [N = G * R, C] (any row stride that is a multiple of 8), kv [G, Lk, 2C] =
+    [k | v] of each image's tokens as linear_packed(image_tokens, [key, value]) lays it out, image-major and NOT repeated per beam; row n
+    belongs to image n // R, R = rows_per_image <= 16.  No mask (the reference passes none at this site), no gradient.  An image's K / V is
+    read once for its R rows; a row's output depends neither on R nor on the other rows.  On CPU tensors the same in torch."""
+    R = int(rows_per_image)
+    _decode_check("mha_decode_cross", q, heads, "q")
+    N, C = q.shape
+    if kv.dim() != 3 or kv.shape[2] != 2 * C or kv.shape[1] < 1 or kv.dtype != q.dtype or kv.device != q.device:
+        raise ValueError(f"mha_decode_cross: kv {tuple(kv.shape)} {kv.dtype} for q {tuple(q.shape)} {q.dtype}: [G, Lk >= 1, 2C], same type and device")
+    if not 1 <= R <= DECODE_MAX_ROWS or N != kv.shape[0] * R:
+        raise ValueError(f"mha_decode_cross: {N} rows, {kv.shape[0]} images, {R} rows per image (1 <= R <= {DECODE_MAX_ROWS}, N = G * R)")
+    if not q.is_cuda:
+        return _mha_decode_cross_host(q, kv, R, heads, scale)
+    if q.dtype != BF16:
+        raise ValueError(f"mha_decode_cross: {q.dtype} on the device (bf16)")
+    if q.stride(0) % 8 or q.data_ptr() % 16:
+        q = _c(q)
+    kv = _c(kv)
+    o = torch.empty((N, C), dtype=BF16, device=q.device)
+    lib.call("fiber_mha_decode_cross_bf16", lib.ptr(q), lib.ptr(kv), lib.ptr(o), N, R, heads, kv.shape[1], C // heads,
+             q.stride(0) if N > 1 else C, C, float(scale))
+    return o
+
+
 _DOT_PARTS = 512      # workspace floats of fiber_dot_bf16 / the d alpha of fiber_stream_add_bwd (FIBER_DOT_PARTS, csrc/common.h)
 
 

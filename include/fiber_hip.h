@@ -139,6 +139,21 @@ int fiber_mha_causal_bwd_bf16(const void* q, const void* k, const void* v, const
                               const float* lse, void* dq, void* dk, void* dv, float* delta_ws, int B, int heads, int Lq, int Lk,
                               int D, int ldq, int ldk, int ldv, int ldo, int lddo, int lddq, int lddk, int lddv, float scale,
                               float p_drop, uint64_t seed, const uint64_t* seed_base, fiber_stream_t stream);
+/* Single-token attention of a KV-cached caption decoder (csrc/attn_decode.hip): forward only, no dropout, no lse.  D in {32,64}, C = heads*D.
+ * fiber_mha_decode_self_bf16: qkv bf16 [N, ldqkv], row n = [q | k | v] of the token at position t; kv_cache bf16 [N slots, Lmax, 2C],
+ * [k | v] per position; anc int32 [N, Lmax] or NULL.  Stores row n's k | v to kv_cache[n, t] and writes o[n] = softmax(scale q.K[0..t]).V
+ * (o bf16 [N, ldo]), the key and value of position j < t read from slot anc[n, j] (slot n when anc is NULL), position t taken from qkv.
+ * A position j <= t whose anc[n, j] lies outside [0, N) is no key (padding under a key mask) and is skipped; anc[n, t] = n otherwise; a row
+ * without any key gives 0.  Positions < t are only read, positions > t never (anc[n, j > t] neither); 0 <= t < Lmax <= 64.
+ * fiber_mha_decode_cross_bf16: q bf16 [N = G*R, ldq], row n belongs to image n / R, 1 <= R <= 16; kv bf16 [G, Lk, 2C] = [k | v] per image
+ * token, Lk >= 1, no mask; o bf16 [N, ldo].  An image's K/V is read once for its R rows; a row's output does not depend on R or on the
+ * other rows.
+ * D, t >= Lmax, Lmax > 64, R > 16, N % R != 0, a leading dimension that is not a multiple of 8 or narrower than its row, NULL or
+ * misaligned (16 bytes; anc: 4) pointers -> 1. */
+int fiber_mha_decode_self_bf16(const void* qkv, void* kv_cache, const int* anc, void* o, int N, int heads, int D, int t, int Lmax,
+                               int ldqkv, int ldo, float scale, fiber_stream_t stream);
+int fiber_mha_decode_cross_bf16(const void* q, const void* kv, void* o, int N, int R, int heads, int Lk, int D, int ldq, int ldo,
+                                float scale, fiber_stream_t stream);
 
 /* RobertaEmbeddings.forward (roberta.py:169-199, 877-888) and its backward: dword / dpos rows of the ids / positions present and dtype row 0,
  * dgamma, dbeta are overwritten (the caller zeroes the other table rows), every sum in a fixed order; workspace: the floats
