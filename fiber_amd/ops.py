@@ -5,7 +5,8 @@ weights it needs to bf16 once per parameter version.  Forward GEMMs with fused e
 cores, embeddings and the element-wise glue are hand-written HIP kernels, and so are both backward GEMMs of every linear:
 dX = dY.W on the NT kernel (transposed bf16 working copy of W), dW = dY^T.X (+ the bias gradient) on the TN kernel
 (csrc/gemm_tn.hip).  Only the caller-side heads (vocabulary decoder, 2-way ITM, VQA classifier) use the library GEMM.
-Nothing here runs on the CPU: tensors must live on a HIP device.
+The kernels need tensors on a HIP device; the detection, retrieval and decode ops also have host paths, and the accessors of the
+derived weight copies are plain torch.
 
 The derived weight copies (`_wcache`, `_packs`) follow their fp32 masters through a stamp, `_stamp(w)` = (version counter,
 generation, storage address).  What changes one of the three is seen by itself: an in-place op on the parameter (`copy_`, `mul_`,
@@ -89,13 +90,28 @@ def bf16_weight_t(w):
         wt.copy_(wb.t())                                 # same storage: pointer tables built on it stay valid
     else:
         wt = wb.t().contiguous()
-        _t_registry_version[0] += 1
     _cache_put(key, _stamp(w), wt, w)
     return wt
 
 
-_t_registry_version = [0]            # bumped whenever a transposed copy gets new storage
-_t_table = {}                        # device -> (registry version, members, device table, tiles)
+_tables = {}                         # (kernel, device) -> (what the rows hold: pointers AND shapes, device table, tiles)
+
+
+def _launch_rows(kernel, by_dev, resolve=None):
+    """One launch of a multi-tensor `kernel` per device over by_dev[device] = [(the pointers of one table row, N, K)].  The device
+    table is kept and rebuilt when anything its rows hold changed; only then resolve(pointers, device) -> pointers runs."""
+    for dev, want in by_dev.items():
+        want = tuple(want)
+        tab = _tables.get((kernel, dev))
+        if tab is None or tab[0] != want:
+            rows, tile0 = [], 0
+            for ptrs, N, K in want:
+                tk = -(-K // 64)
+                rows.append((resolve(ptrs, dev) if resolve else ptrs) + (N | (K << 32), tile0 | (tk << 32)))
+                tile0 += -(-N // 64) * tk
+            tab = _tables[(kernel, dev)] = (want, torch.tensor(rows, dtype=torch.int64).to(dev), tile0)
+        with torch.cuda.device(dev):
+            lib.call(kernel, lib.ptr(tab[1]), len(want), tab[2])
 
 
 def refresh_transposed_copies():
@@ -103,7 +119,7 @@ def refresh_transposed_copies():
     ONE kernel launch and mark it current.  Called by FiberAdamW.step() after it restamped the plain copies."""
     if not _wcache:
         return
-    by_dev = {}
+    by_dev, done = {}, []                                # done: (the `_wcache` key or the pack, its masters)
     for key, (stamp, wt, ref) in list(_wcache.items()):
         if not (isinstance(key, tuple) and key[0] == "T"):
             continue
@@ -115,44 +131,34 @@ def refresh_transposed_copies():
             continue                                     # plain copy stale or gone: the lazy path rebuilds both
         if (wt.shape[0] % 8) or (wt.shape[1] % 8):
             continue
-        by_dev.setdefault(wt.device, []).append((key, w, plain[1], wt, ref))
+        by_dev.setdefault(wt.device, []).append(((plain[1].data_ptr(), wt.data_ptr()), wt.shape[1], wt.shape[0]))
+        done.append((key, (w,)))
     for pk in list(_packs.values()):                      # packed projections (linear_packed): ONE descriptor per pack
-        ws = [r() for r in pk["refs"]]
-        if any(w is None for w in ws) or not pk["plain"].is_cuda:
+        ws, plain = [r() for r in pk["refs"]], pk["plain"]
+        if any(w is None for w in ws) or not plain.is_cuda:
             continue
         hits = [_cache_get(id(w), w) for w in ws]
         if any(h is None or h[0] != _stamp(w) for h, w in zip(hits, ws)) or not _pack_views_ok(pk, ws):
             continue                                         # some member stale: the lazy path (_pack_get) refreshes
-        by_dev.setdefault(pk["plain"].device, []).append((None, pk, pk["plain"], pk["t"], None))
-    for dev, items in by_dev.items():
-        members = tuple((p.data_ptr(), t.data_ptr()) for _, _, p, t, _ in items)
-        ent = _t_table.get(dev)
-        if ent is None or ent[0] != members:
-            rows, tile0 = [], 0
-            for _, _, p, t, _ in items:
-                N, K = p.shape
-                tk = -(-K // 64)
-                rows.append((p.data_ptr(), t.data_ptr(), N | (K << 32), tile0 | (tk << 32)))
-                tile0 += -(-N // 64) * tk
-            ent = (members, torch.tensor(rows, dtype=torch.int64).to(dev), tile0)
-            _t_table[dev] = ent
-        with torch.cuda.device(dev):
-            lib.call("fiber_transpose_multi_bf16", lib.ptr(ent[1]), len(items), ent[2])
-        for key, w, _, wt, ref in items:
-            if key is None:
-                w["t_stamp"] = tuple(_stamp(r()) for r in w["refs"])     # a pack: its transposed copy is current
-            else:
-                _wcache[key] = (_stamp(w), wt, ref)
+        by_dev.setdefault(plain.device, []).append(((plain.data_ptr(), pk["t"].data_ptr()), plain.shape[0], plain.shape[1]))
+        done.append((pk, ws))
+    _launch_rows("fiber_transpose_multi_bf16", by_dev)
+    for target, ws in done:
+        if isinstance(target, dict):
+            target["t_stamp"] = tuple(_stamp(w) for w in ws)         # a pack: its transposed copy is current
+        else:
+            _wcache[target] = (_stamp(ws[0]),) + _wcache[target][1:]
 
 
-_hm_table = {}                       # device -> (members, device table, tiles)
+def _hm_row(ptrs, dev):
+    return ptrs[:1] + (_qkv_perm32(*ptrs[1], dev).data_ptr(),) + ptrs[2:]
 
 
 def refresh_head_major_copies():
     """Rewrite every cached head-major qkv working copy (permuted bf16 weight, its transpose, permuted fp32 bias: _LinearQKVHeadMajor) from the
     fp32 parameters in ONE launch and mark it current.  Called by FiberAdamW.step() after the parameter update, like refresh_transposed_copies();
     copies the optimizer did not touch are rewritten too (same values)."""
-    by_dev = {}
+    by_dev, done = {}, []
     for key, (stamp, val, ref) in list(_wcache.items()):
         if not (isinstance(key, tuple) and key[0] == "HM"):
             continue
@@ -162,24 +168,13 @@ def refresh_head_major_copies():
             continue
         if (w.shape[0] % 8) or (w.shape[1] % 8):
             continue
-        by_dev.setdefault(w.device, []).append((key, w, b, val, ref))
-    for dev, items in by_dev.items():
-        members = tuple((w.data_ptr(), b.data_ptr(), v[0].data_ptr(), v[1].data_ptr(), v[2].data_ptr()) for _, w, b, v, _ in items)
-        ent = _hm_table.get(dev)
-        if ent is None or ent[0] != members:
-            rows, tile0 = [], 0
-            for _, w, b, v, _ in items:
-                N, K = w.shape
-                tk = -(-K // 64)
-                pm = _qkv_perm32(K, v[4], dev)
-                rows.append((w.data_ptr(), pm.data_ptr(), v[0].data_ptr(), v[2].data_ptr(), b.data_ptr(), v[1].data_ptr(), N | (K << 32), tile0 | (tk << 32)))
-                tile0 += -(-N // 64) * tk
-            ent = (members, torch.tensor(rows, dtype=torch.int64).to(dev), tile0)
-            _hm_table[dev] = ent
-        with torch.cuda.device(dev):
-            lib.call("fiber_rowperm_cast_multi_bf16", lib.ptr(ent[1]), len(items), ent[2])
-        for key, w, b, v, ref in items:
-            _wcache[key] = ((_stamp(w), _stamp(b)), v, ref)
+        # the second pointer is the row permutation's: it stands here as (K, heads) and becomes an address when the table is built
+        by_dev.setdefault(w.device, []).append(((w.data_ptr(), (w.shape[1], val[4]), val[0].data_ptr(), val[2].data_ptr(), b.data_ptr(), val[1].data_ptr()),
+                                                w.shape[0], w.shape[1]))
+        done.append((key, (w, b)))
+    _launch_rows("fiber_rowperm_cast_multi_bf16", by_dev, _hm_row)
+    for key, (w, b) in done:
+        _wcache[key] = ((_stamp(w), _stamp(b)),) + _wcache[key][1:]
 
 
 def bf16_copy_if_cached(w):
@@ -207,7 +202,7 @@ def cast_bf16(w):
 def clear_weight_cache():
     _wcache.clear()
     _packs.clear()
-    _hm_table.clear()
+    _tables.clear()
 
 
 def _rows(x):
@@ -328,8 +323,6 @@ def colsum(x2):
     lib.call("fiber_colsum_bf16", lib.ptr(x2), lib.ptr(out), lib.ptr(ws), M, N, x2.stride(0))
     return out
 
-
-_bmm_fp32 = [None]
 
 # ---- library GEMMs are kept in ONE global order across HIP streams ------------------------------------------------
 # hipBLASLt picks stream-K kernels for many of these shapes (…_SK3_… in the rocprof traces): persistent grids whose
@@ -1146,6 +1139,18 @@ def _qkv_perm32(C, heads, device):
     return _perm_cache[key]
 
 
+def _head_major_weights(weight, bias, heads):
+    """(wp, bp, wpt): the bf16 weight of a qkv projection with its rows in [heads][3][32] order, the fp32 bias in that order, the transpose
+    of the first.  The entry remembers (weakly) WHICH bias it was built from: a replaced one is a miss, like a changed one."""
+    key = ("HM", id(weight))
+    hit = _cache_get(key, weight)
+    if hit is None or hit[0] != (_stamp(weight), _stamp(bias)) or hit[1][3]() is not bias or hit[1][0].device != weight.device:
+        perm = _qkv_perm(weight.shape[1], heads, weight.device)[0]
+        wp = weight.detach()[perm].to(BF16).contiguous()
+        _cache_put(key, (_stamp(weight), _stamp(bias)), (wp, bias.detach()[perm].contiguous(), wp.t().contiguous(), weakref.ref(bias), heads), weight)
+    return _wcache[key][1][:3]
+
+
 class _LinearQKVHeadMajor(torch.autograd.Function):
     """qkv = x . W^T + b with the OUTPUT channels reordered to [heads][3][32]: q|k|v of one head become one contiguous
     192-byte run per token, so the per-head gathers of the window-attention kernels use 3/4 of every cache line they touch
@@ -1155,15 +1160,7 @@ class _LinearQKVHeadMajor(torch.autograd.Function):
     def forward(ctx, x, weight, bias, heads):
         shp = x.shape
         x2 = _c(x).view(-1, shp[-1])
-        C = weight.shape[1]
-        perm, inv = _qkv_perm(C, heads, x.device)
-        key = ("HM", id(weight))
-        hit = _cache_get(key, weight)
-        if hit is None or hit[0] != (_stamp(weight), _stamp(bias)) or hit[1][3]() is not bias or hit[1][0].device != weight.device:
-            wp = weight.detach()[perm].to(BF16).contiguous()
-            _cache_put(key, (_stamp(weight), _stamp(bias)), (wp, bias.detach()[perm].contiguous(), wp.t().contiguous(), weakref.ref(bias), heads), weight)
-            _hm_table.clear()                                # (new storage: the one-launch refresh rebuilds its descriptor table)
-        wp, bp = _wcache[key][1][:2]
+        wp, bp, _ = _head_major_weights(weight, bias, heads)
         y, _ = gemm_nt(x2, wp, bp)
         ctx.save_for_backward(x2, weight)
         ctx.shp, ctx.heads = shp, heads
@@ -1220,7 +1217,6 @@ def _pack_get(weights, biases):
               "refs": [weakref.ref(w, lambda _r, k=key: _packs.pop(k, None)) for w in weights], "Ns": Ns, "K": K, "t_stamp": None,
               "bias": None}
         _packs[key] = pk
-        _t_registry_version[0] += 1
     if not _pack_views_ok(pk, weights):                     # (re-)register the members' working copies as views of the pack
         off = 0
         for w, n in zip(weights, pk["Ns"]):
@@ -1845,6 +1841,17 @@ class ImagePair:
         return torch.cat([self.img, torch.where(self.sel.view(-1, 1, 1, 1), self.img, self.alt)], 0)
 
 
+def _patch_embed_weight(weight):
+    """[Cout, 3, 4, 4] fp32 parameter -> bf16 [Cout, 64]: the 48 im2col columns, then zeros (the GEMM's K is a multiple of 64)."""
+    key = ("pe", id(weight))
+    hit = _cache_get(key, weight)
+    if hit is None or hit[0] != _stamp(weight) or hit[1].device != weight.device:
+        wp = torch.zeros((weight.shape[0], 64), dtype=BF16, device=weight.device)
+        wp[:, :48] = weight.detach().reshape(weight.shape[0], 48).to(BF16)
+        _cache_put(key, _stamp(weight), wp, weight)
+    return _wcache[key][1]
+
+
 class _PatchEmbedProj(torch.autograd.Function):
     """Conv2d(3->C, k=4, s=4) + bias as im2col + MFMA GEMM (no input gradient: the image is data)."""
 
@@ -1864,14 +1871,7 @@ class _PatchEmbedProj(torch.autograd.Function):
             rows = B * (H // 4) * (W // 4)
             cols = torch.empty((rows, 64), dtype=BF16, device=img.device)
             lib.call("fiber_im2col_patch4", lib.ptr(img), lib.ptr(cols), B, H, W)
-        key = ("pe", id(weight))
-        hit = _cache_get(key, weight)
-        if hit is None or hit[0] != _stamp(weight) or hit[1].device != img.device:
-            wp = torch.zeros((Cout, 64), dtype=BF16, device=img.device)
-            wp[:, :48] = weight.detach().reshape(Cout, 48).to(BF16)
-            _cache_put(key, _stamp(weight), wp, weight)
-        wp = _wcache[key][1]
-        y, _ = gemm_nt(cols, wp, bias)
+        y, _ = gemm_nt(cols, _patch_embed_weight(weight), bias)
         ctx.save_for_backward(cols)
         ctx.wshape = weight.shape
         return y.view(B, rows // B, Cout)

@@ -1,7 +1,8 @@
 """Host: the derived weight copies of fiber_amd/ops.py follow their fp32 masters through every way a parameter changes
 (tests/weight_cache_cases.py has the expected values, the audit, the cases and the writers).  The kinds whose accessors are
-plain torch run here: plain, transposed, the LayerNorm-folded Mlp set, conv rows and their transpose, the 2-D view of a 1x1
-conv.  The consuming ops are HIP kernels, so here "the op" is its accessor calls; tests/test_hip_weight_cache.py runs the ops."""
+plain torch run here, which is all of them: plain, transposed, head-major qkv, packs, the LayerNorm-folded Mlp
+set, the patch embedding, conv rows and their transpose, the 2-D view of a 1x1 conv.  The consuming ops are HIP
+kernels, so here "the op" is its accessor calls; tests/test_hip_weight_cache.py runs the ops."""
 import pytest
 import torch
 
@@ -44,12 +45,15 @@ def test_host_copies_follow_the_writer(name, writer):
         ent = ops._cache_get(key, w)
         if ent is None:
             continue                                     # (gone with the view it belonged to: rebuilt from nothing)
-        if isinstance(key, tuple) and key[0] == "LNMLP":
+        if isinstance(key, tuple) and key[0] == "HM":
+            assert not wc.is_current(ops, key, w, case.groups[0].b), f"{name} / {writer}: HM entry still current"
+        elif isinstance(key, tuple) and key[0] == "LNMLP":
             assert ent[0] != tuple(ops._stamp(t) for t in case.groups[0].five), f"{name} / {writer}: LNMLP entry still current"
         else:
             # (a copy that belongs to the 2-D view of a 1x1 conv is also out of use when the view no longer is the parameter's storage)
             orphan = name == "conv1x1" and w.data_ptr() != case.params[0].data_ptr()
             assert orphan or ent[0] != ops._stamp(w), f"{name} / {writer}: {key!r} still called current"
+    assert not any(wc.pack_is_current(ops, s) for s in case.groups if isinstance(s, wc.Pack)), f"{name} / {writer}: pack still called current"
     # ... and the next accessor call must hand out the expected copy of the NEW master
     # (a 1x1 conv whose storage moved gets a NEW 2-D view; the old view's copies went with it)
     assert wc.audit(case.audit_args()) >= case.kinds - ({"V2plain", "T"} if name == "conv1x1" else set())

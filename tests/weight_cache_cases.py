@@ -109,11 +109,15 @@ class PE:
 
 
 def _touch_hm(ops, s):
+    if not s.w.is_cuda:                                  # (the op is a HIP kernel: on the host, its accessor)
+        return ops._head_major_weights(s.w, s.b, s.heads)
     with torch.no_grad():
         ops.linear_qkv_head_major(torch.zeros(64, s.w.shape[1], dtype=BF, device=s.w.device), s.w, s.b, s.heads)
 
 
 def _touch_pe(ops, s):
+    if not s.w.is_cuda:
+        return ops._patch_embed_weight(s.w)
     with torch.no_grad():
         ops.patch_embed_proj(torch.zeros(1, 3, 32, 32, device=s.w.device), s.w, s.b)
 
@@ -292,7 +296,7 @@ class Case:
 
 
 def make_cases(device, names=None):
-    """name -> Case on `device`.  On the host only the kinds whose accessors are plain torch (plain, T, LNMLP, KC / KCT, V2)."""
+    """name -> Case on `device`.  On the host run is None (the consumers are HIP kernels) and host() calls the bare accessors."""
     from fiber_amd import ops
     gpu = torch.device(device).type == "cuda"
     g = torch.Generator().manual_seed(1234)
@@ -352,34 +356,33 @@ def make_cases(device, names=None):
         ops.bf16_weight(v), ops.bf16_weight_t(v)
     out["conv1x1"] = Case("conv1x1", [wv, bv], [], {"V2", "V2plain", "T"}, (lambda: fb(lambda x_: ops.conv1x1(x_, wv, bv), xv)) if gpu else None, v2_host)
 
-    if gpu:
-        Cq, heads = 64, 2
-        wq, bq = _p(g, 3 * Cq, Cq, std=Cq ** -0.5, device=device), _p(g, 3 * Cq, device=device)
-        xq = xin(2, 9, Cq)
-        out["qkv64"] = Case("qkv64", [wq, bq], [HM(wq, bq, heads)], {"HM"}, lambda: fb(lambda x_: ops.linear_qkv_head_major(x_, wq, bq, heads), xq),
-                            None, fast=[(("HM", id(wq)), wq, bq)], launches={"fiber_rowperm_cast_multi_bf16"})
+    Cq, heads = 64, 2
+    wq, bq = _p(g, 3 * Cq, Cq, std=Cq ** -0.5, device=device), _p(g, 3 * Cq, device=device)
+    xq = xin(2, 9, Cq)
+    out["qkv64"] = Case("qkv64", [wq, bq], [HM(wq, bq, heads)], {"HM"}, (lambda: fb(lambda x_: ops.linear_qkv_head_major(x_, wq, bq, heads), xq)) if gpu else None,
+                        lambda: ops._head_major_weights(wq, bq, heads), fast=[(("HM", id(wq)), wq, bq)], launches={"fiber_rowperm_cast_multi_bf16"})
 
-        ws = [_p(g, 64, 64, std=0.125, device=device) for _ in range(3)]
-        bs = [_p(g, 64, device=device) for _ in range(3)]
-        xp = xin(37, 64)
-        out["pack3"] = Case("pack3", ws + bs, [Pack(ws, bs)], {"pack", "plain"},
-                            lambda: fb(lambda x_: ops.linear_packed(x_, list(zip(ws, bs))), xp), None,
-                            fast=[(id(w), w, None) for w in ws], launches={"fiber_transpose_multi_bf16"})
+    ws = [_p(g, 64, 64, std=0.125, device=device) for _ in range(3)]
+    bs = [_p(g, 64, device=device) for _ in range(3)]
+    xp = xin(37, 64)
+    out["pack3"] = Case("pack3", ws + bs, [Pack(ws, bs)], {"pack", "plain"},
+                        (lambda: fb(lambda x_: ops.linear_packed(x_, list(zip(ws, bs))), xp)) if gpu else None, lambda: ops._pack_get(ws, bs),
+                        fast=[(id(w), w, None) for w in ws], launches={"fiber_transpose_multi_bf16"})
 
-        wpe, bpe = _p(g, 32, 3, 4, 4, device=device), _p(g, 32, device=device)
-        img = torch.randn(2, 3, 8, 8, generator=g).to(device)
-        def pe_run():
-            y = ops.patch_embed_proj(img, wpe, bpe)
-            y.backward(torch.ones_like(y))
-            return y.detach().clone(), None                  # the image is data: there is no input gradient
-        out["patch_embed"] = Case("patch_embed", [wpe, bpe], [PE(wpe, bpe)], {"pe"}, pe_run, None)
+    wpe, bpe = _p(g, 32, 3, 4, 4, device=device), _p(g, 32, device=device)
+    img = torch.randn(2, 3, 8, 8, generator=g).to(device)
+    def pe_run():
+        y = ops.patch_embed_proj(img, wpe, bpe)
+        y.backward(torch.ones_like(y))
+        return y.detach().clone(), None                  # the image is data: there is no input gradient
+    out["patch_embed"] = Case("patch_embed", [wpe, bpe], [PE(wpe, bpe)], {"pe"}, pe_run if gpu else None, lambda: ops._patch_embed_weight(wpe))
     if names is not None:
         out = {k: out[k] for k in names}
     return out
 
 
-HOST_CASES = ("linear64", "linear40x24", "odd20x12", "lnmlp128", "conv27", "conv16", "conv1x1")
-GPU_CASES = HOST_CASES + ("qkv64", "pack3", "patch_embed")
+GPU_CASES = ("linear64", "linear40x24", "odd20x12", "lnmlp128", "conv27", "conv16", "conv1x1", "qkv64", "pack3", "patch_embed")
+HOST_CASES = GPU_CASES                               # every kind has a plain-torch accessor: all of them run on the host too
 
 
 def pack_is_current(ops, s):
