@@ -381,3 +381,275 @@ extern "C" int fiber_mlm_mask_i64(const long long* ids, long long* ids_mlm, long
   FIBER_CHECK_LAUNCH();
   return FIBER_OK;
 }
+
+// ---- training image transform: RandomResizedCrop + RandomHorizontalFlip + RandomAugment(N, M) + ToTensor + Normalize ------------------
+// coarse_grained/fiber/transforms/transform.py:20-45 `albef_transform_randaug` with transforms/randaug.py.  Every random choice is made on
+// the host (fiber_amd/data.py DeviceRandAugTransform.plan); the kernels below execute a plan:
+//   crop + resize + flip : the bicubic resampler above on a sub-view (ImgDesc.src points at the crop's first pixel, the row stride is the
+//                          source's), with a second pass that writes uint8 HWC and mirrors the output column;
+//   per slot             : randaug_tables_kernel (one workgroup per image: histograms -> the slot's three 256-entry tables, only where the
+//                          slot's op is AutoContrast / Equalize; Brightness needs no statistics) then one apply kernel that dispatches per
+//                          image on the op code.  Table ops run in place; Sharpness and the affine gather read one uint8 image and write
+//                          the other (RaSlot.src says which one holds the image when the slot starts: the host tracks the ping-pong).
+//                          The last slot's apply writes ToTensor + Normalize in fp32 CHW instead of bytes.
+// The statistics of slot k + 1 are those of slot k's OUTPUT: the launches are stream-ordered, one tables + one apply kernel per slot.
+namespace {
+
+enum RaOp : int { RA_IDENTITY = 0, RA_AUTOCONTRAST = 1, RA_EQUALIZE = 2, RA_BRIGHTNESS = 3, RA_SHARPNESS = 4, RA_SHEAR_X = 5,
+                  RA_SHEAR_Y = 6, RA_TRANSLATE_X = 7, RA_TRANSLATE_Y = 8, RA_ROTATE = 9 };      // < 0: the slot was not applied
+
+struct RaSlot {                                 // one per image and slot, built by the host (fiber_amd/data.py)
+  int op;                                       // RaOp, or negative when the slot's coin said skip
+  int src;                                      // which of the two uint8 images (0 / 1) holds this sample when the slot starts
+  float factor;                                 // Brightness / Sharpness
+  int pad;
+  double m[6];                                  // the five geometric ops: the INVERSE affine map (dst -> src), as cv2.warpAffine inverts it
+};
+static_assert(sizeof(RaSlot) == 64, "RaSlot is mirrored by fiber_amd/data.py");
+
+// pass 2 of the crop-resize, to bytes: out[b][yy][flip ? S-1-xx : xx][c] = clip8(sum_y tmp[ymin + y][xx][c] * k[y])
+__global__ __launch_bounds__(256) void resample_v_u8_flip_kernel(const ImgDesc* descs, const int* flips, const int* coef,
+                                                                 const unsigned char* tmp, unsigned char* out, int S, size_t pitch) {
+  const ImgDesc d = descs[blockIdx.z];
+  const int xx = blockIdx.x * 256 + threadIdx.x, yy = blockIdx.y;
+  if (xx >= S) return;
+  const int* row = coef + d.coef_v_off + (size_t)yy * (2 + d.ksize_v);
+  const int ymin = row[0], ymax = row[1];
+  const unsigned char* tp = tmp + d.tmp_off + ((size_t)ymin * S + xx) * 3;
+  int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
+  for (int y = 0; y < ymax; ++y) {
+    const int k = row[2 + y];
+    const unsigned char* p = tp + (size_t)y * S * 3;
+    s0 += p[0] * k; s1 += p[1] * k; s2 += p[2] * k;
+  }
+  unsigned char* o = out + blockIdx.z * pitch + ((size_t)yy * S + (flips[blockIdx.z] ? S - 1 - xx : xx)) * 3;
+  o[0] = (unsigned char)clip8(s0); o[1] = (unsigned char)clip8(s1); o[2] = (unsigned char)clip8(s2);
+}
+
+// One workgroup per image.  AutoContrast (randaug.py:13-43, cutoff 0) and Equalize (:46-67) need the three channel histograms of the
+// image as it stands when the slot starts; Brightness (:119-125) only its factor.  luts: uint8 [n][3][256].
+// Histograms: 16 waves, 16-byte loads (pitch is a multiple of 16; byte k of the image is channel k % 3 and 16 = 1 mod 3), LDS atomics on
+// four copies (a wave uses copy wave % 4) so that a flat image does not serialise all 1024 lanes on one counter.
+__global__ __launch_bounds__(1024) void randaug_tables_kernel(const RaSlot* slots, const unsigned char* buf0, const unsigned char* buf1,
+                                                              size_t pitch, unsigned char* luts, int S) {
+#pragma clang fp contract(off)
+  const RaSlot sl = slots[blockIdx.x];
+  if (sl.op < RA_AUTOCONTRAST || sl.op > RA_BRIGHTNESS) return;                          // block-uniform
+  const int t = threadIdx.x;
+  unsigned char* lut = luts + (size_t)blockIdx.x * 768;
+  if (sl.op == RA_BRIGHTNESS) {
+    if (t < 256) {
+      float v = (float)t * sl.factor;
+      v = v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v);
+      const unsigned char b = (unsigned char)(int)v;
+      lut[t] = b; lut[256 + t] = b; lut[512 + t] = b;
+    }
+    return;
+  }
+  __shared__ unsigned hist[4][768];
+  __shared__ unsigned pre[768];                 // exclusive prefix sums of the histogram, per channel
+  __shared__ int stat[3][3];                    // lo, hi, step
+  for (int i = t; i < 4 * 768; i += 1024) (&hist[0][0])[i] = 0u;
+  __syncthreads();
+  const unsigned char* img = (sl.src ? buf1 : buf0) + blockIdx.x * pitch;
+  const int nbytes = S * S * 3, nvec = nbytes >> 4;
+  unsigned* h = hist[(t >> 6) & 3];
+  const uint4* vp = reinterpret_cast<const uint4*>(img);
+  for (int j = t; j < nvec; j += 1024) {
+    const uint4 q = vp[j];
+    const unsigned w[4] = {q.x, q.y, q.z, q.w};
+    int c = j % 3;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      atomicAdd(&h[c * 256 + ((w[k >> 2] >> (8 * (k & 3))) & 0xffu)], 1u);
+      c = c == 2 ? 0 : c + 1;
+    }
+  }
+  for (int k = (nvec << 4) + t; k < nbytes; k += 1024) atomicAdd(&h[(k % 3) * 256 + img[k]], 1u);
+  __syncthreads();
+  if (t < 768) hist[0][t] += hist[1][t] + hist[2][t] + hist[3][t];
+  __syncthreads();
+  if (t < 3) {                                  // 256 bins per channel: a serial scan is shorter than its own reduction tree's barriers
+    const unsigned* hc = hist[0] + t * 256;
+    int lo = -1, hi = 0;
+    unsigned acc = 0;
+    for (int i = 0; i < 256; ++i) {
+      pre[t * 256 + i] = acc;
+      const unsigned v = hc[i];
+      acc += v;
+      if (v) { if (lo < 0) lo = i; hi = i; }
+    }
+    stat[t][0] = lo; stat[t][1] = hi;
+    stat[t][2] = (int)((acc - hc[hi]) / 255u);  // Equalize: the non-zero bins except the LAST non-zero one, // 255
+  }
+  __syncthreads();
+  if (t < 768) {
+    const int c = t >> 8, i = t & 255, lo = stat[c][0], hi = stat[c][1], step = stat[c][2];
+    int v = i;
+    if (sl.op == RA_AUTOCONTRAST) {
+      if (hi > lo) {                            // fp64, every operation rounded on its own (numpy does not fuse)
+        const double scale = 255.0 / (double)(hi - lo);
+        const double offset = -(double)lo * scale;
+        const double prod = (double)i * scale;
+        double x = prod + offset;
+        x = x < 0.0 ? 0.0 : (x > 255.0 ? 255.0 : x);
+        v = (int)x;
+      }
+    } else if (step > 0) {
+      const unsigned q = ((unsigned)(step >> 1) + pre[t]) / (unsigned)step;
+      v = q > 255u ? 255 : (int)q;
+    }
+    lut[t] = (unsigned char)v;
+  }
+}
+
+// One output pixel of one slot: o[c] from the image `img` (uint8 [S][S][3]) as it stands when the slot starts.
+__device__ __forceinline__ void randaug_pixel(const RaSlot& sl, const unsigned char* img, const unsigned char* lut, const short* wtab,
+                                              int S, int x, int y, int (&o)[3]) {
+#pragma clang fp contract(off)
+  const unsigned char* p = img + ((size_t)y * S + x) * 3;
+  if (sl.op < RA_AUTOCONTRAST) {                // Identity, or not applied
+    o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
+  } else if (sl.op <= RA_BRIGHTNESS) {          // the three table ops
+    o[0] = lut[p[0]]; o[1] = lut[256 + p[1]]; o[2] = lut[512 + p[2]];
+  } else if (sl.op == RA_SHARPNESS) {
+    // randaug.py:128-146: degenerate = cv2.filter2D(img, -1, [[1,1,1],[1,5,1],[1,1,1]] / 13) rounded to uint8 = (2 T + 13) / 26 (T / 13 is
+    // never a half); out = uint8(degenerate + factor * (img - degenerate)) in fp32 on the interior, the outermost ring keeps the input.
+    // .astype(np.uint8) WRAPS (no clamp): the low 8 bits of the value truncated toward zero.
+    if (x == 0 || y == 0 || x == S - 1 || y == S - 1) {
+      o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
+    } else {
+      const size_t rs = (size_t)S * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const unsigned char* q = p + c;
+        const int T = q[-(ptrdiff_t)rs - 3] + q[-(ptrdiff_t)rs] + q[-(ptrdiff_t)rs + 3] + q[-3] + 5 * q[0] + q[3] + q[rs - 3] + q[rs] + q[rs + 3];
+        const float deg = (float)((2 * T + 13) / 26);
+        const float d = (float)q[0] - deg;
+        const float r = deg + sl.factor * d;
+        o[c] = (int)r & 255;
+      }
+    }
+  } else {
+    // cv2.warpAffine(INTER_LINEAR, BORDER_CONSTANT (128, 128, 128)), the generic fixed-point path: source coordinates in 1/1024, rounded
+    // half-even from fp64, reduced to 1/32; 2 x 2 taps weighted by int16 weights that sum to 2^15 (wtab[fy * 32 + fx][k1 * 2 + k2]).
+    const double AB = 1024.0;
+    // every fp64 operation rounded on its own (contraction is off in this function), then round-half-even to int32
+    const double ax = sl.m[0] * (double)x, bx = sl.m[3] * (double)x, ay = sl.m[1] * (double)y, by = sl.m[4] * (double)y;
+    const double xr = ay + sl.m[2], yr = by + sl.m[5];
+    const int ad = (int)rint(ax * AB), bd = (int)rint(bx * AB);
+    const int X0 = (int)rint(xr * AB) + 16, Y0 = (int)rint(yr * AB) + 16;
+    const int X = (X0 + ad) >> 5, Y = (Y0 + bd) >> 5;
+    const int sx = X >> 5, sy = Y >> 5;
+    if (sx >= S || sx + 1 < 0 || sy >= S || sy + 1 < 0) {
+      o[0] = o[1] = o[2] = 128;
+    } else {
+      const short* w = wtab + (((Y & 31) << 5) + (X & 31)) * 4;
+      int a0 = 16384, a1 = 16384, a2 = 16384;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int yy = sy + (k >> 1), xx = sx + (k & 1), wk = w[k];
+        int p0 = 128, p1 = 128, p2 = 128;
+        if (yy >= 0 && yy < S && xx >= 0 && xx < S) {
+          const unsigned char* q = img + ((size_t)yy * S + xx) * 3;
+          p0 = q[0]; p1 = q[1]; p2 = q[2];
+        }
+        a0 += wk * p0; a1 += wk * p1; a2 += wk * p2;
+      }
+      a0 >>= 15; a1 >>= 15; a2 >>= 15;
+      o[0] = a0 < 0 ? 0 : (a0 > 255 ? 255 : a0);
+      o[1] = a1 < 0 ? 0 : (a1 > 255 ? 255 : a1);
+      o[2] = a2 < 0 ? 0 : (a2 > 255 ? 255 : a2);
+    }
+  }
+}
+
+// A slot that is not the last: bytes to bytes.  Blocks of an image whose slot does nothing return at once.
+__global__ __launch_bounds__(256) void randaug_apply_u8_kernel(const RaSlot* slots, unsigned char* buf0, unsigned char* buf1, size_t pitch,
+                                                               const unsigned char* luts, const short* wtab, int S) {
+  const RaSlot sl = slots[blockIdx.y];
+  if (sl.op < RA_AUTOCONTRAST) return;                                                   // block-uniform
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  if (pix >= S * S) return;
+  unsigned char* src = (sl.src ? buf1 : buf0) + blockIdx.y * pitch;
+  unsigned char* dst = sl.op <= RA_BRIGHTNESS ? src : (sl.src ? buf0 : buf1) + blockIdx.y * pitch;      // table ops: in place
+  int o[3];
+  randaug_pixel(sl, src, luts + (size_t)blockIdx.y * 768, wtab, S, pix % S, pix / S, o);
+  unsigned char* q = dst + (size_t)pix * 3;
+  q[0] = (unsigned char)o[0]; q[1] = (unsigned char)o[1]; q[2] = (unsigned char)o[2];
+}
+
+// The last slot, fused with ToTensor + Normalize: out[b][c][y][x] = (v / 255 - mean[c]) / std[c], the fp32 expression of
+// resample_v_norm_kernel, evaluated once per (byte, channel) and block.  out_u8 (optional): the byte image [n][S][S][3] before ToTensor.
+__global__ __launch_bounds__(256) void randaug_apply_norm_kernel(const RaSlot* slots, const unsigned char* buf0, const unsigned char* buf1,
+                                                                 size_t pitch, const unsigned char* luts, const short* wtab, int S,
+                                                                 float* out, unsigned char* out_u8, float m0, float m1, float m2,
+                                                                 float d0, float d1, float d2) {
+#pragma clang fp contract(off)
+  __shared__ float norm[3][256];
+  {
+    const float f = (float)threadIdx.x / 255.0f;
+    norm[0][threadIdx.x] = (f - m0) / d0;
+    norm[1][threadIdx.x] = (f - m1) / d1;
+    norm[2][threadIdx.x] = (f - m2) / d2;
+  }
+  __syncthreads();
+  const RaSlot sl = slots[blockIdx.y];
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  if (pix >= S * S) return;
+  int o[3];
+  randaug_pixel(sl, (sl.src ? buf1 : buf0) + blockIdx.y * pitch, luts + (size_t)blockIdx.y * 768, wtab, S, pix % S, pix / S, o);
+  const size_t plane = (size_t)S * S;
+  float* q = out + (size_t)blockIdx.y * 3 * plane + pix;
+  q[0] = norm[0][o[0]]; q[plane] = norm[1][o[1]]; q[2 * plane] = norm[2][o[2]];
+  if (out_u8) {
+    unsigned char* u = out_u8 + ((size_t)blockIdx.y * plane + pix) * 3;
+    u[0] = (unsigned char)o[0]; u[1] = (unsigned char)o[1]; u[2] = (unsigned char)o[2];
+  }
+}
+
+}  // namespace
+
+// RandomResizedCrop + RandomHorizontalFlip to bytes.  descs: n ImgDesc whose src / H / W describe the CROP (src = first pixel of the box,
+// src_stride = the source's row stride); flips: device int32 [n]; out_u8: uint8, image b at b * pitch as [S][S][3] (pitch >= 3 S^2, a
+// multiple of 16).  coef / tmp / max_h as fiber_resize_bicubic_norm_u8 (max_h = tallest crop).  3 kernels.
+extern "C" int fiber_crop_resize_flip_u8(const void* descs, const int* flips, int n, int* coef, void* tmp, void* out_u8, long long pitch,
+                                         int S, int max_h, hipStream_t stream) {
+  if (n <= 0) return FIBER_OK;
+  if (S <= 0 || S > 16384 || max_h <= 0 || max_h > 65535 || n > 65535 || !descs || !flips || !coef || !tmp || !out_u8) return FIBER_EINVAL;
+  if (pitch < 3ll * S * S || (pitch & 15) || fiber_misaligned(16, out_u8)) return FIBER_EINVAL;
+  const ImgDesc* d = reinterpret_cast<const ImgDesc*>(descs);
+  hipLaunchKernelGGL(resample_coeffs_kernel, dim3(cdiv(2 * S, 128), n), dim3(128), 0, stream, d, coef, S);
+  hipLaunchKernelGGL(resample_h_kernel, dim3(cdiv(S, 256), max_h, n), dim3(256), 0, stream, d, coef,
+                     reinterpret_cast<unsigned char*>(tmp), S);
+  hipLaunchKernelGGL(resample_v_u8_flip_kernel, dim3(cdiv(S, 256), S, n), dim3(256), 0, stream, d, flips, coef,
+                     reinterpret_cast<const unsigned char*>(tmp), reinterpret_cast<unsigned char*>(out_u8), S, (size_t)pitch);
+  FIBER_CHECK_LAUNCH();
+  return FIBER_OK;
+}
+
+// One RandomAugment slot over the batch.  slots: n RaSlot (64 bytes each: int32 op, src; float factor; int32 pad; double m[6]); buf0 /
+// buf1: the two uint8 images per sample (layout of fiber_crop_resize_flip_u8's out_u8); luts: uint8 [n][3][256] workspace; wtab: int16
+// [1024][4] bilinear weights.  out == NULL: a slot that is not the last (bytes to bytes).  out != NULL: the last slot, fp32 [n,3,S,S] =
+// Normalize(ToTensor(.)) with mean / std (HOST pointers to 3 floats), and out_u8 (or NULL): uint8 [n,S,S,3], the image before ToTensor.
+// 2 kernels whatever the ops are.
+extern "C" int fiber_randaug_slot_u8(const void* slots, int n, void* buf0, void* buf1, long long pitch, void* luts, const void* wtab,
+                                     int S, float* out, void* out_u8, const float* mean, const float* std, hipStream_t stream) {
+  if (n <= 0) return FIBER_OK;
+  if (S <= 0 || S > 16384 || n > 65535 || !slots || !buf0 || !buf1 || !luts || !wtab) return FIBER_EINVAL;
+  if (pitch < 3ll * S * S || (pitch & 15) || fiber_misaligned(16, buf0, buf1)) return FIBER_EINVAL;
+  if (out && (!mean || !std)) return FIBER_EINVAL;
+  const RaSlot* s = reinterpret_cast<const RaSlot*>(slots);
+  const unsigned char *b0 = reinterpret_cast<unsigned char*>(buf0), *b1 = reinterpret_cast<unsigned char*>(buf1);
+  unsigned char* l = reinterpret_cast<unsigned char*>(luts);
+  const short* w = reinterpret_cast<const short*>(wtab);
+  hipLaunchKernelGGL(randaug_tables_kernel, dim3(n), dim3(1024), 0, stream, s, b0, b1, (size_t)pitch, l, S);
+  if (out)
+    hipLaunchKernelGGL(randaug_apply_norm_kernel, dim3(cdiv(S * S, 256), n), dim3(256), 0, stream, s, b0, b1, (size_t)pitch, l, w, S, out,
+                       reinterpret_cast<unsigned char*>(out_u8), mean[0], mean[1], mean[2], std[0], std[1], std[2]);
+  else
+    hipLaunchKernelGGL(randaug_apply_u8_kernel, dim3(cdiv(S * S, 256), n), dim3(256), 0, stream, s, const_cast<unsigned char*>(b0),
+                       const_cast<unsigned char*>(b1), (size_t)pitch, l, w, S);
+  FIBER_CHECK_LAUNCH();
+  return FIBER_OK;
+}

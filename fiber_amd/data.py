@@ -3,6 +3,9 @@ the H2D copy of the RAW sample bytes.
 
   * `DeviceImageTransform` = `albef_transform(size)` of coarse_grained/fiber/transforms/transform.py:10-17 (PIL bicubic Resize ->
     ToTensor -> Normalize), bit-identical to PIL + torchvision on uint8 RGB input (csrc/input.hip restates Pillow's resampler);
+  * `DeviceRandAugTransform` = `albef_transform_randaug(size)` of transform.py:20-45, the TRAINING transform of every configuration
+    (RandomResizedCrop -> RandomHorizontalFlip -> RandomAugment(2, 7) -> ToTensor -> Normalize): `plan` draws on the host, `apply` runs
+    7 kernels on the device; `keys_to_transforms` maps config["train_transform_keys"] / ["val_transform_keys"] to the two transforms;
   * `mlm_mask` = the masking rule of `DataCollatorForLanguageModeling(mlm_probability)` used by BaseDataModule
     (datamodules/datamodule_base.py:52) -> `text_ids_mlm`, `text_labels_mlm` of the batch schema (base_dataset.py:223-243).
 
@@ -15,6 +18,8 @@ What stays on the host: JPEG decode (`Image.open(...).convert("RGB")`, base_data
 workers hand over uint8 [H, W, 3] arrays and int64 token ids; everything after that is stream-ordered device work, so at
 ~800 images/s per GPU the loader no longer resizes and normalises 2 x 384^2 fp32 images per sample on CPU cores.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -316,3 +321,251 @@ def device_collate_grounding(samples, transform, cfg, seed=None, pad_id=1):
     lib.call("fiber_det_boxes_f32", lib.ptr(targets.boxes), lib.ptr(table), len(samples), int(targets.boxes.shape[1]))
     images._keep = table
     return images, targets, tok
+
+
+# ---- the coarse-grained model's TRAINING transform -----------------------------------------------------------------------------------
+RANDAUG_OPS = ("Identity", "AutoContrast", "Equalize", "Brightness", "Sharpness", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate")
+RANDAUG_SKIPPED = -1                                                     # op code of a slot whose coin said "do not apply"
+_RANDAUG_UNBUILT = ("Solarize", "Color", "Contrast", "Posterize")        # in randaug.py's func_dict, in no training transform
+_RA_SLOT = np.dtype([("op", "<i4"), ("src", "<i4"), ("factor", "<f4"), ("pad", "<i4"), ("m", "<f8", (6,))])
+assert _RA_SLOT.itemsize == 64
+_RA_CROP_ATTEMPTS = 10
+
+
+def randaug_forward_matrix(op, arg, size):
+    """The 2 x 3 matrix the reference hands to cv2.warpAffine for geometric op `op` (a name of RANDAUG_OPS) with signed argument `arg` on a
+    size x size image, as six doubles: shear_x_func / shear_y_func / translate_x_func / translate_y_func build it with np.float32 (the
+    entries are float32 widened), rotate_func takes cv2.getRotationMatrix2D((W / 2, H / 2), degree, 1), which is fp64."""
+    f = float(np.float32(arg))
+    if op == "ShearX":
+        return (1.0, f, 0.0, 0.0, 1.0, 0.0)
+    if op == "ShearY":
+        return (1.0, 0.0, 0.0, f, 1.0, 0.0)
+    if op == "TranslateX":
+        return (1.0, 0.0, -f, 0.0, 1.0, 0.0)
+    if op == "TranslateY":
+        return (1.0, 0.0, 0.0, 0.0, 1.0, -f)
+    if op != "Rotate":
+        raise ValueError(f"{op} is not a geometric op")
+    angle = float(arg) * (math.pi / 180.0)
+    a, b = math.cos(angle), math.sin(angle)
+    cx = cy = float(np.float32(size / 2))
+    return (a, b, (1 - a) * cx - b * cy, -b, a, b * cx + (1 - a) * cy)
+
+
+def warp_affine_inverse(M):
+    """cv2.warpAffine's inversion of a forward 2 x 3 matrix (no WARP_INVERSE_MAP), in its order of fp64 operations -> (M0 .. M5), dst -> src."""
+    M0, M1, M2, M3, M4, M5 = (float(v) for v in M)
+    D = M0 * M4 - M1 * M3
+    D = 1.0 / D if D != 0 else 0.0
+    A11, A22 = M4 * D, M0 * D
+    M0 = A11
+    M1 *= -D
+    M3 *= -D
+    M4 = A22
+    b1 = -M0 * M2 - M1 * M5
+    b2 = -M3 * M2 - M4 * M5
+    return (M0, M1, b1, M3, M4, b2)
+
+
+def bilinear_weight_table():
+    """cv2's INTER_LINEAR remap weights: int16 [1024, 4], row fy * 32 + fx, column ky * 2 + kx.  The four fp32 products wy[ky] * wx[kx], w =
+    (1 - f / 32, f / 32), times 2^15 rounded half-even to a saturating int16 (1 * 1 -> 32767); what the four lack of 2^15 goes to the
+    [1][1] tap."""
+    f = np.arange(32, dtype=np.float32) * np.float32(1.0 / 32)
+    w = np.stack([np.float32(1.0) - f, f], 1)                             # [32, 2]
+    tab = (w[:, None, :, None] * w[None, :, None, :]).astype(np.float32)  # [fy, fx, ky, kx]
+    it = np.clip(np.rint(tab * np.float32(32768.0)), -32768, 32767).astype(np.int32)
+    it[:, :, 1, 1] += 32768 - it.sum((2, 3))
+    assert it.min() >= 0 and it.max() <= 32767 and (it.sum((2, 3)) == 32768).all()
+    return np.ascontiguousarray(it.reshape(1024, 4).astype(np.int16))
+
+
+class DeviceRandAugTransform:
+    """`albef_transform_randaug(size)` of coarse_grained/fiber/transforms/transform.py:20-45 on the device: RandomResizedCrop(size, scale,
+    BICUBIC) -> RandomHorizontalFlip -> RandomAugment(N, M, augs) (transforms/randaug.py) -> ToTensor -> Normalize.  images: list of uint8
+    [H, W, 3] RGB device tensors (ragged, row-strided views allowed) -> fp32 [B, 3, size, size].
+
+    `plan(shapes, seed)` draws everything on the host, `apply(images, plan)` is the device work; nothing is read back from the device.
+    Draw k of sample i of the batch keyed `seed` is hash_u32(seed, i * (41 + 3 N) + k) / 2^32: k = 4 a .. 4 a + 3 the area, log-ratio, top
+    and left of crop attempt a < 10; k = 40 the flip; k = 41 + 3 s .. + 2 slot s's op, its apply coin and its sign.  These streams are NOT
+    the reference's (np.random / torch.rand in each loader worker); the distributions are: torchvision's RandomResizedCrop.get_params
+    (10 attempts, then the ratio-clamped centre crop), ops uniform with replacement from `augs`, each applied with probability 0.5,
+    shear / translate negated when the draw is > 0.5 (randaug.py:212-229), rotate when it is < 0.5 (:260-267).
+
+    What is bit-exact to what: crop + resize + flip equal PIL's `crop(box).resize((size, size), BICUBIC)` / `transpose(FLIP_LEFT_RIGHT)`;
+    AutoContrast and Equalize equal PIL.ImageOps (as randaug.py's docstrings promise: the tables are built with `offset = -lo * scale` on
+    integers widened to fp64); Brightness and Sharpness restate randaug.py's fp32 arithmetic, Sharpness INCLUDING the wrap of its
+    `.astype(np.uint8)` (no clamp: a value below 0 or above 255 keeps its low 8 bits); ShearX / ShearY / TranslateX / TranslateY / Rotate
+    follow the arithmetic of OpenCV's generic warpAffine / remap path for 8-bit 3-channel INTER_LINEAR with constant border (128, 128, 128)
+    (1/1024 fixed-point coordinates reduced to 1/32, int16 weights summing to 2^15), restated in tests/randaug_cases.py.  Parity of the five
+    geometric ops with a particular cv2 build has not been measured by anyone: cv2 is not a dependency of this project.
+
+    Launches per batch, whatever ops were drawn: 1 H2D copy of the plan tables and 3 + 2 max(N, 1) kernels through 1 + max(N, 1) ABI calls
+    (fiber_crop_resize_flip_u8: coefficient tables, horizontal pass, vertical pass + flip to bytes; fiber_randaug_slot_u8 per slot: the
+    slot's statistics / tables, then its apply, the last one fused with ToTensor + Normalize) -- 7 kernels, 3 calls for N = 2.  The int16
+    weight table is uploaded once per transform and device."""
+
+    def __init__(self, size=384, scale=(0.5, 1.0), ratio=(3 / 4, 4 / 3), flip_prob=0.5, N=2, M=7, augs=RANDAUG_OPS, mean=IMAGENET_MEAN,
+                 std=IMAGENET_STD):
+        self.size, self.N, self.M = int(size), int(N), M
+        self.scale, self.ratio = (float(scale[0]), float(scale[1])), (float(ratio[0]), float(ratio[1]))
+        self.log_ratio = (math.log(self.ratio[0]), math.log(self.ratio[1]))
+        self.flip_threshold = int(float(flip_prob) * 2 ** 32)
+        for a in augs:
+            if a in _RANDAUG_UNBUILT:
+                raise NotImplementedError(f"{a}: this RandomAugment op is not built (no training transform of the reference uses it)")
+            if a not in RANDAUG_OPS:
+                raise ValueError(f"{a}: not an op of transforms/randaug.py")
+        if len(augs) < 1 or self.N < 0 or self.size < 1:
+            raise ValueError("DeviceRandAugTransform needs at least one op, N >= 0 and size >= 1")
+        self.augs = tuple(augs)
+        self.codes = tuple(RANDAUG_OPS.index(a) for a in self.augs)
+        self.mean = (lib.C.c_float * 3)(*mean)
+        self.std = (lib.C.c_float * 3)(*std)
+        self.draws = 4 * _RA_CROP_ATTEMPTS + 1 + 3 * self.N
+        self.plan_dtype = np.dtype([("top", "<i4"), ("left", "<i4"), ("h", "<i4"), ("w", "<i4"), ("flip", "<i4"),
+                                    ("op", "<i4", (self.N,)), ("arg", "<f8", (self.N,))])
+        self._wtab = {}
+
+    def level_arg(self, op, negate):
+        """randaug.py's arg_dict[op](M) (MAX_LEVEL = 10, translate_const = 10) with the sign draw already made"""
+        level = self.M / 10
+        if op in ("Brightness", "Sharpness"):
+            return level * 1.8 + 0.1
+        if op in ("ShearX", "ShearY"):
+            level = level * 0.3
+        elif op in ("TranslateX", "TranslateY"):
+            level = level * float(10)
+        elif op == "Rotate":
+            level = level * 30
+        else:
+            return 0.0
+        return -level if negate else level
+
+    def crop_box(self, seed, index, H, W):
+        """torchvision RandomResizedCrop.get_params for sample `index` -> (top, left, h, w)"""
+        base = index * self.draws
+        area = H * W
+        for a in range(_RA_CROP_ATTEMPTS):
+            u = [hash_u32(seed, base + 4 * a + k) / 2.0 ** 32 for k in range(4)]
+            target = area * (self.scale[0] + (self.scale[1] - self.scale[0]) * u[0])
+            aspect = math.exp(self.log_ratio[0] + (self.log_ratio[1] - self.log_ratio[0]) * u[1])
+            w = int(round(math.sqrt(target * aspect)))
+            h = int(round(math.sqrt(target / aspect)))
+            if 0 < w <= W and 0 < h <= H:
+                return int(u[2] * (H - h + 1)), int(u[3] * (W - w + 1)), h, w
+        in_ratio = float(W) / float(H)
+        if in_ratio < min(self.ratio):
+            w = W
+            h = int(round(w / min(self.ratio)))
+        elif in_ratio > max(self.ratio):
+            h = H
+            w = int(round(h * max(self.ratio)))
+        else:
+            w, h = W, H
+        return (H - h) // 2, (W - w) // 2, h, w
+
+    def plan(self, shapes, seed):
+        """shapes: (H, W) per image -> a numpy record array, one row per image: the crop box `top, left, h, w`, `flip`, and per slot `op`
+        (index into RANDAUG_OPS, RANDAUG_SKIPPED when the slot's coin said no) and `arg` (the signed magnitude of a geometric op, the factor
+        of Brightness / Sharpness, else 0).  A pure function of (shapes, seed)."""
+        seed = int(seed) & _M64
+        p = np.zeros(len(shapes), self.plan_dtype)
+        for i, (H, W) in enumerate(shapes):
+            H, W = int(H), int(W)
+            base = i * self.draws + 4 * _RA_CROP_ATTEMPTS
+            p[i]["top"], p[i]["left"], p[i]["h"], p[i]["w"] = self.crop_box(seed, i, H, W)
+            p[i]["flip"] = int(hash_u32(seed, base) < self.flip_threshold)
+            for s in range(self.N):
+                pick, coin, sign = (hash_u32(seed, base + 1 + 3 * s + k) for k in range(3))
+                name = self.augs[(pick * len(self.augs)) >> 32]
+                if coin >= 2 ** 31:                                          # `if np.random.random() > prob: continue`
+                    p[i]["op"][s] = RANDAUG_SKIPPED
+                    continue
+                negate = sign < 2 ** 31 if name == "Rotate" else sign >= 2 ** 31
+                p[i]["op"][s] = RANDAUG_OPS.index(name)
+                p[i]["arg"][s] = self.level_arg(name, negate)
+        return p
+
+    def __call__(self, images, seed=None):
+        if seed is None:
+            seed = ops.collate_seed()
+        return self.apply(images, self.plan([(int(im.shape[0]), int(im.shape[1])) for im in images], seed))
+
+    def apply(self, images, plan, return_u8=False):
+        """The device work for a plan (of `plan`, or hand-written with `plan_dtype`): -> fp32 [B, 3, size, size]; with return_u8 also the
+        uint8 [B, size, size, 3] image as it stood just before ToTensor."""
+        S, n, dev = self.size, len(images), images[0].device
+        K = max(self.N, 1)
+        if len(plan) != n or plan.dtype != self.plan_dtype:
+            raise ValueError(f"DeviceRandAugTransform.apply: a plan of {len(plan)} rows ({plan.dtype}) for {n} images")
+        desc, slots = np.zeros(n, _DESC), np.zeros((K, n), _RA_SLOT)
+        slots["op"] = RANDAUG_SKIPPED
+        tmp_off = coef_off = 0
+        for i, (im, p) in enumerate(zip(images, plan)):
+            if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or im.stride(2) != 1 or im.stride(1) != 3:
+                raise ValueError("DeviceRandAugTransform needs uint8 [H, W, 3] images with packed pixels")
+            H, W = int(im.shape[0]), int(im.shape[1])
+            top, left, h, w = int(p["top"]), int(p["left"]), int(p["h"]), int(p["w"])
+            if not (0 <= top and 0 <= left and 0 < h and 0 < w and top + h <= H and left + w <= W):
+                raise ValueError(f"DeviceRandAugTransform.apply: crop box {(top, left, h, w)} outside image {i} ({H} x {W})")
+            stride = int(im.stride(0))
+            kh, kv = lib.plain("fiber_resample_ksize", w, S), lib.plain("fiber_resample_ksize", h, S)
+            desc[i] = (lib.ptr(im) + top * stride + left * 3, h, w, stride, kh, kv, tmp_off, coef_off, coef_off + S * (2 + kh))
+            tmp_off += (h * S * 3 + 15) // 16 * 16
+            coef_off += S * (2 + kh) + S * (2 + kv)
+            cur = 0                                                          # which byte image holds the sample: the ping-pong
+            for s in range(K):
+                sl = slots[s, i]
+                sl["src"] = cur                                              # a skipped LAST slot still reads the sample to normalise it
+                op = int(p["op"][s]) if s < self.N else RANDAUG_SKIPPED
+                if op < 0:
+                    continue
+                if op >= len(RANDAUG_OPS):
+                    raise ValueError(f"DeviceRandAugTransform.apply: op code {op} in slot {s} of image {i}")
+                sl["op"] = op
+                name = RANDAUG_OPS[op]
+                if name in ("Brightness", "Sharpness"):
+                    sl["factor"] = p["arg"][s]
+                elif op >= RANDAUG_OPS.index("ShearX"):
+                    sl["m"] = warp_affine_inverse(randaug_forward_matrix(name, float(p["arg"][s]), S))
+                if op >= RANDAUG_OPS.index("Sharpness") and s < K - 1:
+                    cur ^= 1                                                 # Sharpness and the gather write the other image
+        if tmp_off >= 2 ** 31 or coef_off >= 2 ** 31:
+            raise ValueError("batch too large for one call (intermediate images exceed 2 GiB): split it")
+        pitch = (S * S * 3 + 15) // 16 * 16
+        blob = np.concatenate([slots.reshape(-1).view(np.uint8), desc.view(np.uint8), plan["flip"].astype("<i4").view(np.uint8)])
+        d_blob = torch.from_numpy(blob).to(dev, non_blocking=True)
+        p_slots = lib.ptr(d_blob)
+        p_desc = p_slots + K * n * 64
+        p_flip = p_desc + n * 40
+        key = (dev.type, dev.index)
+        if key not in self._wtab:
+            self._wtab[key] = torch.from_numpy(bilinear_weight_table()).to(dev)
+        wtab = self._wtab[key]
+        coef = torch.empty(coef_off, dtype=torch.int32, device=dev)
+        tmp = torch.empty(tmp_off, dtype=torch.uint8, device=dev)
+        bufs = torch.empty(2 * n * pitch, dtype=torch.uint8, device=dev)
+        luts = torch.empty(n * 768, dtype=torch.uint8, device=dev)
+        out = torch.empty((n, 3, S, S), dtype=torch.float32, device=dev)
+        u8 = torch.empty((n, S, S, 3), dtype=torch.uint8, device=dev) if return_u8 else None
+        b0 = lib.ptr(bufs)
+        b1 = b0 + n * pitch
+        lib.call("fiber_crop_resize_flip_u8", p_desc, p_flip, n, lib.ptr(coef), lib.ptr(tmp), b0, pitch, S, int(desc["H"].max()))
+        for s in range(K):
+            last = s == K - 1
+            lib.call("fiber_randaug_slot_u8", p_slots + s * n * 64, n, b0, b1, pitch, lib.ptr(luts), lib.ptr(wtab), S,
+                     lib.ptr(out) if last else None, lib.ptr(u8) if last else None, self.mean, self.std)
+        self._keep = (images, d_blob)          # the sources / tables must outlive the (asynchronous) kernels of this call
+        return (out, u8) if return_u8 else out
+
+
+def keys_to_transforms(keys, size=384):
+    """coarse_grained/fiber/transforms/__init__.py:12 for the device transforms: config["train_transform_keys"] / ["val_transform_keys"] ->
+    a list of transforms for `device_collate`."""
+    table = {"albef": DeviceImageTransform, "albef_randaug": DeviceRandAugTransform}
+    for k in keys:
+        if k not in table:
+            raise KeyError(f"{k}: no device transform of that name (known: {sorted(table)})")
+    return [table[k](size=size) for k in keys]

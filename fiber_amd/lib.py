@@ -68,6 +68,8 @@ SIGNATURES = {
     "fiber_mlm_mask_i64": [P, P, P, L, U64, C.c_uint, I, I, I, I],
     "fiber_det_resize_norm_pad_u8": [P, I, P, P, P, I, I, I, I, I, I, I, P, P],
     "fiber_det_boxes_f32": [P, P, I, I],
+    "fiber_crop_resize_flip_u8": [P, P, I, P, P, P, C.c_longlong, I, I],
+    "fiber_randaug_slot_u8": [P, I, P, P, C.c_longlong, P, P, I, P, P, P, P],
     "fiber_transpose_multi_bf16": [P, I, I],
     "fiber_rowperm_cast_multi_bf16": [P, I, I],
     "fiber_dcn_gather_bf16": [P, P, P, P, I, I, I, I, I, I, I, I, I, I],

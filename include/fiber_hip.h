@@ -322,6 +322,27 @@ int fiber_resample_ksize_bilinear(int in_size, int out_size);
 int fiber_det_resize_norm_pad_u8(const void* descs, int n, int* coef, void* tmp, float* out, int Hp, int Wp, int max_h, int max_oh,
                                  int max_ow, int bgr, int times255, const float* mean, const float* std, fiber_stream_t stream);
 int fiber_det_boxes_f32(float* boxes, const void* params, int B, int G, fiber_stream_t stream);
+/* The coarse-grained model's TRAINING transform, transforms/transform.py:20-45 `albef_transform_randaug`: RandomResizedCrop(BICUBIC) ->
+ * RandomHorizontalFlip -> RandomAugment(N, M) (transforms/randaug.py) -> ToTensor -> Normalize.  Every draw is made on the host
+ * (data.DeviceRandAugTransform.plan); these entry points execute a plan.
+ * fiber_crop_resize_flip_u8 = PIL `img.crop(box).resize((S, S), BICUBIC)` then `transpose(FLIP_LEFT_RIGHT)` where flips[b], bit for bit: the
+ * resampler of fiber_resize_bicubic_norm_u8 on a sub-view (descs: the same 40-byte records with src = the box's first pixel, H / W = the
+ * box, src_stride = the source's row stride; coef / tmp / max_h as there, for the boxes).  flips: device int32 [n].  out_u8: image b as uint8
+ * [S][S][3] at byte b * pitch (pitch >= 3 S^2, a multiple of 16; out_u8 16-byte aligned).  3 kernels.
+ * fiber_randaug_slot_u8 = one RandomAugment slot over the batch, 2 kernels whatever the ops are.  slots: device array of n 64-byte records
+ * {int32 op, src; float factor; int32 pad; double m[6]}: op = 0 Identity, 1 AutoContrast, 2 Equalize, 3 Brightness, 4 Sharpness, 5 ShearX,
+ * 6 ShearY, 7 TranslateX, 8 TranslateY, 9 Rotate, negative = not applied; src = which of buf0 / buf1 (layout of out_u8 above) holds the
+ * sample when the slot starts -- the table ops (1-3) run in place, 4-9 write the other buffer; factor: Brightness / Sharpness; m: the
+ * inverse affine map of ops 5-9 as cv2.warpAffine inverts it.  luts: uint8 [n][3][256] workspace (the slot's AutoContrast / Equalize /
+ * Brightness tables, from the image as it stands when the slot starts).  wtab: int16 [1024][4], cv2's INTER_LINEAR weight table
+ * ([fy * 32 + fx][ky * 2 + kx], sum 2^15).  Sharpness keeps the low 8 bits of its truncated fp32 result (the reference's astype(uint8)
+ * wraps); the geometric ops follow the generic fixed-point remap path for 8UC3 with constant border 128.  out == NULL: bytes to bytes.
+ * out != NULL (the LAST slot): fp32 [n,3,S,S] = (v / 255 - mean[c]) / std[c] as fiber_resize_bicubic_norm_u8 rounds it, and, when out_u8 is
+ * not NULL, uint8 [n,S,S,3]: the image before ToTensor.  mean / std: HOST pointers to 3 floats (read when out != NULL). */
+int fiber_crop_resize_flip_u8(const void* descs, const int* flips, int n, int* coef, void* tmp, void* out_u8, long long pitch, int S,
+                              int max_h, fiber_stream_t stream);
+int fiber_randaug_slot_u8(const void* slots, int n, void* buf0, void* buf1, long long pitch, void* luts, const void* wtab, int S,
+                          float* out, void* out_u8, const float* mean, const float* std, fiber_stream_t stream);
 
 /* Modulated deformable convolution (DCNv2) of the fine-grained model's DyHead: the sampling half of
  * layers/deform_conv.py:300-353 `ModulatedDeformConv` (csrc/cuda/deform_conv_kernel_cuda.cu:578-640 im2col, :643-700 col2im,
