@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+// The C ABI: every extern "C" definition in these files is checked against its declaration there, and the return codes,
+// FIBER_DOT_PARTS and the FIBER_ACT_ bits are defined there once for C and Python.
+#include "../../include/fiber_hip.h"
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -9,13 +12,6 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-#define FIBER_OK 0
-#define FIBER_EINVAL 1
-#define FIBER_ELAUNCH 2
-
-// Workspace floats of fiber_dot_bf16 and of fiber_stream_add_bwd's d alpha: one partial per workgroup, at most this many workgroups
-#define FIBER_DOT_PARTS 512
 
 #define FIBER_CHECK_LAUNCH()                          \
   do {                                                \

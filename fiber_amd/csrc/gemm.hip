@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
           const float4 b = *reinterpret_cast<const float4*>(a.bias + n);
           v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
         }
-        if ((a.act & 0xff) == 1) {
+        if ((a.act & 0xff) == FIBER_ACT_GELU) {
           if (a.Ypre) {
             bf16x4 o;
 #pragma unroll
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] *= rsc;
         }
-        if (a.act & 0x800) {                              // fp32 residual stream (EPI 3 of gemm_epilogue.h): branch rounded once
+        if (a.act & FIBER_ACT_STREAM_F32) {   // fp32 residual stream (EPI 3 of gemm_epilogue.h): branch rounded once
           const float4 r = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.R) + (size_t)m * a.ldr + n);
           const float4 o = {bf2f(f2bf(v[0])) + r.x, bf2f(f2bf(v[1])) + r.y, bf2f(f2bf(v[2])) + r.z, bf2f(f2bf(v[3])) + r.w};
           *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.Ypre) + (size_t)m * a.ldy + n) = o;
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs a) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] += bf2f(r[e]);
         }
-        if (a.act & 0x100) {                              // fp32 output (narrow heads whose consumers need full precision)
+        if (a.act & FIBER_ACT_OUT_F32) {   // fp32 output (narrow heads whose consumers need full precision)
           *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.Y) + (size_t)m * a.ldy + n) = float4{v[0], v[1], v[2], v[3]};
           continue;
         }
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_glds_kernel(GemmArgs a) 
   stage_bias<BN>(a, bias_s, tn0);
   const int nk = a.K / BK;
   const int frow = lane & 31, fk = lane >> 5;
-  const bool dbg_nodma = a.act & 0x100;                // ablation switch (tools/gemm_probe.py)
+  const bool dbg_nodma = a.act & FIBER_ACT_OUT_F32;   // ablation switch (tools/gemm_probe.py)
   constexpr int KS = BK / 16;
   constexpr int DPK = (PA + PB + KS - 2) / (KS - 1);   // DMA instructions issued per k-step (spread over the first KS-1 steps)
   // K-tile body, software pipelined inside the wave: fragments of k-step ks+1 are requested and a slice of the NEXT
@@ -751,10 +751,10 @@ __global__ __launch_bounds__(512) void gemm_nt_q8_kernel(GemmArgs a) {
   asm volatile("" ::: "memory");
   // Group 1 runs one barrier behind group 0 INSIDE a tile's K loop.  Round 4: the stagger is taken down at the end of every K loop
   // (one extra barrier for group 0) and put up again at the start of the next (one for group 1), so that both groups enter their
-  // wave-private epilogues together.  With the stagger kept across tiles (round 3; act bit 0x4000 = that form, for A/B runs) group 1
+  // wave-private epilogues together.  With the stagger kept across tiles (round 3; FIBER_ACT_KEEP_STAGGER = that form, for A/B runs) group 1
   // sat at its last P4 barrier for the whole of group 0's epilogue and group 0 at its first P1 barrier for the whole of group 1's:
   // the two epilogues ran one after the other with one wave per SIMD (trace: 2 x 11.2 k ticks per GELU tile, K loop 27 k).
-  const bool keep_stagger = (a.act & 0x4000) != 0;
+  const bool keep_stagger = (a.act & FIBER_ACT_KEEP_STAGGER) != 0;
   if (keep_stagger && wm == 1) { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
   unsigned r_st = 0;                                      // ring stage being read (byte offset 0 / STAGEB): flips per K tile
   // TRACE build (tools/gemm_trace.py q8): s_memtime ticks per wave summed over its K tiles -- for each of the four phases
@@ -932,13 +932,13 @@ static GemmPlan gemm_plan(int M, int N, int K, int ldy, int ldr, bool has_r, boo
   const long huge = (long)cdiv(M, 256) * cdiv(N, 128);
   const long wide = (long)cdiv(M, 256) * cdiv(N, 256);
   const int mode = act & 0xff;
-  const int epi = (act & 0x800) ? 3 : (mode == 1 || mode == 2) ? mode : 0;     // the EPI the entry point instantiates
-  const bool trace = (act & 0x1000) != 0;                 // tools/gemm_trace.py: built for whole tile columns only
+  const int epi = (act & FIBER_ACT_STREAM_F32) ? 3 : (mode == FIBER_ACT_GELU || mode == FIBER_ACT_GELU_BWD) ? mode : 0;     // the EPI the entry point instantiates
+  const bool trace = (act & FIBER_ACT_TRACE) != 0;   // tools/gemm_trace.py: built for whole tile columns only
   const bool v2 = (K % 64 == 0) && (N % 8 == 0) && (ldy % 8 == 0) && (!has_r || ldr % 8 == 0) && !getenv("FIBER_GEMM_V1");
   const bool wide_ok = v2 && !nowide && force == 0 && wide >= kWideMinTiles && K >= 128;
   const bool q8 = q8_ok(epi, has_r, has_rs) && !(epi == 2 && colpart) && !trace;
   GemmFamily f;
-  if (act & 0x100) {                                      // fp32 output: the register-staged kernels only
+  if (act & FIBER_ACT_OUT_F32) {   // fp32 output: the register-staged kernels only
     if (mode != 0 || has_r || colpart) return GemmPlan{kRejected, 0, 0};
     f = big >= 192 ? kReg128 : kReg64;
   } else if (wide_ok && q8 && (N % 256 == 0 || (N % 64 == 0 && N > 256))) f = kQ8;
@@ -954,7 +954,7 @@ static GemmPlan gemm_plan(int M, int N, int K, int ldy, int ldr, bool has_r, boo
 // Row-tile height of the fused gelu' * aux column-sum call (act 2 with `colpart`, ldy = N) for an [M,N,K] problem: the rows of
 // `colpart` = ceil(M / tile).  0: the dispatcher rejects that call.
 extern "C" int fiber_gemm_row_tile(int M, int N, int K) {
-  return gemm_plan(M, N, K, N, 0, false, false, true, 2).rows;
+  return gemm_plan(M, N, K, N, 0, false, false, true, FIBER_ACT_GELU_BWD).rows;
 }
 
 // One LDS-DMA launch.  Each (EPI, R, RS) instantiates the persistent kernels only where they are built for it; gemm_plan() pairs a
@@ -974,11 +974,11 @@ static int launch_nt(const GemmPlan& p, const GemmArgs& a, hipStream_t stream) {
   return FIBER_OK;
 }
 
-// Y = rowscale * act(X.W^T + bias) + residual.  bias: fp32[N] or NULL; residual: bf16[M,ldr] or NULL; act: 0 none, 1 exact GELU;
-// act | 0x100 (act 0 only, no residual): Y is fp32 [M, ldy] -- narrow outputs whose consumers need more than bf16 (the
+// Y = rowscale * act(X.W^T + bias) + residual.  bias: fp32[N] or NULL; residual: bf16[M,ldr] or NULL; act: 0 none, FIBER_ACT_GELU exact GELU;
+// act | FIBER_ACT_OUT_F32 (act 0 only, no residual): Y is fp32 [M, ldy] -- narrow outputs whose consumers need more than bf16 (the
 // offset predictor of the deformable convolutions: sampling positions);
 // rowscale: fp32[M / rows_per_sample] or NULL (per-sample DropPath factor on the branch, swin_transformer.py:390-391)
-// act | 0x800 (act 0, residual required): the fp32 RESIDUAL STREAM form -- `residual` is fp32 [M, ldr], the sum goes to `Ypre`
+// act | FIBER_ACT_STREAM_F32 (act 0, residual required): the fp32 RESIDUAL STREAM form -- `residual` is fp32 [M, ldr], the sum goes to `Ypre`
 // viewed as fp32 [M, ldy] and, if Y is non-NULL, once more as bf16 to Y (the shadow GEMM consumers of the stream read);
 // (Ypre, if non-NULL with act=1, receives the pre-activation for the backward pass).  K % 8 == 0, N % 4 == 0,
 // all leading dimensions multiples of 8 elements (16-byte rows).
@@ -989,32 +989,32 @@ extern "C" int fiber_gemm_nt_bf16(const void* X, const void* W, const float* bia
   if (M <= 0 || N <= 0 || K <= 0) return FIBER_OK;
   if ((K & 7) || (N & 3) || (ldx & 7) || (ldw & 7) || (ldy & 3) || (residual && (ldr & 3))) return FIBER_EINVAL;
   if (rowscale && rows_per_sample <= 0) return FIBER_EINVAL;
-  if ((act & 0xff) == 2 && (!aux || (ldaux & 7))) return FIBER_EINVAL;
+  if ((act & 0xff) == FIBER_ACT_GELU_BWD && (!aux || (ldaux & 7))) return FIBER_EINVAL;
   GemmArgs a{(const bf16*)X, (const bf16*)W, bias, (const bf16*)residual, (bf16*)Y, (bf16*)Ypre, rowscale,
              (const bf16*)aux, colpart, M, N, K, ldx, ldw, ldy, ldr, act, rows_per_sample, ldaux};
   static const int stagger_env = getenv("FIBER_GEMM_STAGGER") ? atoi(getenv("FIBER_GEMM_STAGGER")) : 0;   // 1: round-3 barrier form (A/B runs)
-  if (stagger_env) a.act |= 0x4000;
-  if ((size_t)M * N * 2 > ((size_t)256 << 20)) a.act |= 0x2000;   // output larger than the last-level cache: streaming stores (gemm_epilogue.h st_out)
+  if (stagger_env) a.act |= FIBER_ACT_KEEP_STAGGER;
+  if ((size_t)M * N * 2 > ((size_t)256 << 20)) a.act |= FIBER_ACT_NT_STORES;   // output larger than the last-level cache: streaming stores (gemm_epilogue.h st_out)
   const int mode = act & 0xff;
-  if ((mode == 2 || colpart) && !((K % 64 == 0) && (N % 8 == 0) && (ldy % 8 == 0))) return FIBER_EINVAL;   // LDS-DMA kernels only
-  if (mode == 2 && residual) return FIBER_EINVAL;
-  if ((act & 0x800) && (mode != 0 || !residual || !Ypre || colpart || (act & 0x100))) return FIBER_EINVAL;
-  if (colpart && mode != 2 && !(act & 0x1000)) return FIBER_EINVAL;
+  if ((mode == FIBER_ACT_GELU_BWD || colpart) && !((K % 64 == 0) && (N % 8 == 0) && (ldy % 8 == 0))) return FIBER_EINVAL;   // LDS-DMA kernels only
+  if (mode == FIBER_ACT_GELU_BWD && residual) return FIBER_EINVAL;
+  if ((act & FIBER_ACT_STREAM_F32) && (mode != 0 || !residual || !Ypre || colpart || (act & FIBER_ACT_OUT_F32))) return FIBER_EINVAL;
+  if (colpart && mode != FIBER_ACT_GELU_BWD && !(act & FIBER_ACT_TRACE)) return FIBER_EINVAL;
   const GemmPlan plan = gemm_plan(M, N, K, ldy, ldr, residual != nullptr, rowscale != nullptr, colpart != nullptr, act);
   if (plan.family == kRejected) return FIBER_EINVAL;
   const dim3 grid(plan.grid);
   int rc = FIBER_OK;
-  if (plan.family == kQ8 && (act & 0x1000)) {             // tools/gemm_trace.py q8: per-phase timing of the q8 kernel
-    a.act &= 0x40ff;
-    if (mode == 1) hipLaunchKernelGGL((gemm_nt_q8_kernel<1, false, false, true>), grid, dim3(512), 0, stream, a);
+  if (plan.family == kQ8 && (act & FIBER_ACT_TRACE)) {   // tools/gemm_trace.py q8: per-phase timing of the q8 kernel
+    a.act &= FIBER_ACT_KEEP_STAGGER | 0xff;
+    if (mode == FIBER_ACT_GELU) hipLaunchKernelGGL((gemm_nt_q8_kernel<1, false, false, true>), grid, dim3(512), 0, stream, a);
     else hipLaunchKernelGGL((gemm_nt_q8_kernel<0, false, false, true>), grid, dim3(512), 0, stream, a);
   }
   else if (plan.family == kReg128) hipLaunchKernelGGL((gemm_nt_kernel<128, 128>), grid, dim3(256), 0, stream, a);
   else if (plan.family == kReg64) hipLaunchKernelGGL((gemm_nt_kernel<64, 64>), grid, dim3(256), 0, stream, a);
-  else if (act & 0x800) rc = rowscale ? launch_nt<3, true, true>(plan, a, stream) : launch_nt<3, true, false>(plan, a, stream);
-  else if (mode == 2) rc = rowscale ? launch_nt<2, false, true>(plan, a, stream) : launch_nt<2, false, false>(plan, a, stream);
-  else if (mode == 1 && residual) rc = rowscale ? launch_nt<1, true, true>(plan, a, stream) : launch_nt<1, true, false>(plan, a, stream);
-  else if (mode == 1) rc = rowscale ? launch_nt<1, false, true>(plan, a, stream) : launch_nt<1, false, false>(plan, a, stream);
+  else if (act & FIBER_ACT_STREAM_F32) rc = rowscale ? launch_nt<3, true, true>(plan, a, stream) : launch_nt<3, true, false>(plan, a, stream);
+  else if (mode == FIBER_ACT_GELU_BWD) rc = rowscale ? launch_nt<2, false, true>(plan, a, stream) : launch_nt<2, false, false>(plan, a, stream);
+  else if (mode == FIBER_ACT_GELU && residual) rc = rowscale ? launch_nt<1, true, true>(plan, a, stream) : launch_nt<1, true, false>(plan, a, stream);
+  else if (mode == FIBER_ACT_GELU) rc = rowscale ? launch_nt<1, false, true>(plan, a, stream) : launch_nt<1, false, false>(plan, a, stream);
   else if (residual && rowscale) rc = launch_nt<0, true, true>(plan, a, stream);
   else if (residual && plan.family == kQ8) {
     // residual without DropPath (text-layer output projections, blocks with drop_path = 0) on the large-shape path: the q8 instantiation

@@ -158,8 +158,6 @@ inline int ground_blocks(int A) { return cdiv(A, G_ANCH); }
 
 }  // namespace
 
-extern "C" int fiber_fold_rows_f32(const float* part, float* out, int rows, int N, hipStream_t stream);
-
 // fp32 words of the partial-sum workspace both directions need: one per workgroup (loss / dlog_scale) + one per workgroup and token (dtbias)
 extern "C" long fiber_ground_workspace(int B, int A, int T) {
   if (B <= 0 || A <= 0 || T <= 0) return 0;

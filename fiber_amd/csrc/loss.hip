@@ -172,8 +172,6 @@ extern "C" int fiber_ce_bwd_bf16(const void* logits, const long long* labels, co
   return FIBER_OK;
 }
 
-extern "C" int fiber_fold_rows_f32(const float* part, float* out, int rows, int N, hipStream_t stream);
-
 // out[j] = sum over the rows r with labels[r] != ignore_index of x[r, j] (x: bf16 [rows, V], the dlogits fiber_ce_bwd_bf16 wrote: its other
 // rows are zero).  workspace: fp32 [fiber_colsum_labelled_slabs(rows) * V].
 // A slab's row list lives in LDS (one int per row of the slab): fiber_colsum_labelled_max_rows() is the largest row count whose slab plan

@@ -14,8 +14,6 @@
 // copy, ema).  Tables as in adamw_multi_kernel (optim.hip): device pointers per tensor, numel[n], (tensor, chunk) pairs.
 #include "common.h"
 
-extern "C" int fiber_adamw_chunk(void);
-
 namespace {
 
 constexpr int CHUNK = 4096;   // elements per workgroup: fiber_adamw_chunk() (checked by the entry points)

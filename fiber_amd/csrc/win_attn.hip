@@ -1457,8 +1457,6 @@ int fiber_win_fwd_launch(const void* qkv, const float* bias_table, void* o, floa
 int fiber_win_bwd_slices(int n_windows, int heads) { return win_runs(n_windows, heads); }
 int fiber_win_colsum_rows(int n_windows, int heads, int N) { return win_runs(n_windows, heads) * win_strip_groups(N); }
 
-extern "C" int fiber_fold_rows_f32(const float* part, float* out, int rows, int N, hipStream_t stream);
-
 int fiber_win_bwd_launch(const void* qkv, const float* bias_table, const void* o, const void* dout, const float* lse,
                          void* dqkv, float* dbias_table, float* delta_ws, float* dbias_ws, float* dqkv_colsum, float* colsum_ws,
                          int B, int Hres, int Wres, int C, int heads, int ws, int shift, int hmajor, hipStream_t st) {

@@ -5,6 +5,7 @@ CPU or eager fallback -- if the shared library is missing or a tensor is not on 
 """
 import ctypes as C
 import os
+import re
 
 import torch
 
@@ -13,104 +14,81 @@ LIB_PATH = os.environ.get("FIBER_HIP_LIB") or os.path.join(_HERE, "libfiber_hip.
 
 P, I, F, L, U64, DBL = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_uint64, C.c_double
 
-# name -> argtypes (stream appended automatically)
-SIGNATURES = {
-    "fiber_gemm_nt_bf16": [P, P, P, P, P, P, P, I, P, I, P, I, I, I, I, I, I, I, I],
-    "fiber_gemm_tn_bf16": [P, P, P, P, P, I, I, I, I, I, P, I, F],
-    "fiber_gemm_tn_rowmap_bf16": [P, P, P, P, P, I, I, I, I, I, P, I, F, P],
-    "fiber_ln_mlp_fwd_bf16": [P, P, P, P, P, P, P, P, I, I, I, F],
-    "fiber_ln_mlp_bwd_bf16": [P, P, P, P, P, P, P, P, P, P, I, I, I, F],
-    "fiber_layernorm_fwd_bf16": [P, P, P, P, P, P, I, I, F],
-    "fiber_layernorm_bwd_bf16": [P, P, P, P, P, P, P, P, P, P, I, I],
-    "fiber_layernorm_fwd_stream": [P, P, P, P, P, P, P, I, I, F, I],
-    "fiber_layernorm_bwd_stream": [P, P, P, P, P, P, P, P, P, P, I, I, I],
-    "fiber_patch_merge_ln_fwd_stream": [P, P, P, P, P, P, I, I, I, I, F, I],
-    "fiber_patch_merge_ln_bwd_stream": [P, P, P, P, P, P, P, P, P, I, I, I, I, I],
-    "fiber_stream_add": [P, I, P, P, P, P, L, F, U64, F, U64, P, P, P, L],
-    "fiber_stream_add_bwd": [P, P, P, P, L, F, U64, F, U64, P, P, P, P, P, L],
-    "fiber_cast_f32_bf16": [P, P, L],
-    "fiber_patch_merge_ln_fwd_bf16": [P, P, P, P, P, P, I, I, I, I, F],
-    "fiber_patch_merge_ln_bwd_bf16": [P, P, P, P, P, P, P, P, P, I, I, I, I],
-    "fiber_window_attn_fwd_bf16": [P, P, P, P, I, I, I, I, I, I, I, I],
-    "fiber_window_attn_bwd_bf16": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I],
-    "fiber_mha_fwd_bf16": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, F, F, U64, P],
-    "fiber_mha_causal_fwd_bf16": [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, F, F, U64, P],
-    "fiber_mha_bwd_bf16": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, F, F, U64, P],
-    "fiber_mha_causal_bwd_bf16": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, F, F, U64, P],
-    "fiber_mha_decode_self_bf16": [P, P, P, P, I, I, I, I, I, I, I, F],
-    "fiber_mha_decode_cross_bf16": [P, P, P, I, I, I, I, I, I, I, F],
-    "fiber_roberta_embed_fwd": [P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, F, U64, P],
-    "fiber_roberta_embed_bwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, U64, P],
-    "fiber_im2col_patch4": [P, P, I, I, I],
-    "fiber_im2col_patch4_pair": [P, P, P, P, I, I, I],
-    "fiber_gelu_bwd_bf16": [P, P, P, L],
-    "fiber_gelu_bwd_colsum_bf16": [P, P, P, P, P, I, I],
-    "fiber_scale_add_bf16": [P, P, P, F, P, L],
-    "fiber_dot_bf16": [P, P, P, P, L],
-    "fiber_colsum_bf16": [P, P, P, I, I, I],
-    "fiber_fold_rows_f32": [P, P, I, I],
-    "fiber_dropout_bf16": [P, P, L, F, U64, P],
-    "fiber_droppath_scale_f32": [P, I, F, U64, P],
-    "fiber_rowscale_add_bf16": [P, P, P, P, L, L],
-    "fiber_rowscale_colsum_bf16": [P, P, P, P, P, I, I, I],
-    "fiber_ce_fwd_bf16": [P, P, P, P, P, I, I, L],
-    "fiber_colsum_labelled_bf16": [P, P, P, P, I, I, L],
-    "fiber_ce_bwd_bf16": [P, P, P, P, P, I, I, L],
-    "fiber_sample_rows_bf16": [P, P, P, P, P, I, I, I, I, U64, P, L, L],
-    "fiber_seqlogp_fwd_bf16": [P, P, P, P, I, I, L],
-    "fiber_seqlogp_bwd_bf16": [P, P, P, P, P, I, I, L],
-    "fiber_adamw_multi_f32": [P, P, P, I, F, F, F, F, F, I, P],
-    "fiber_grad_sqnorm_multi_f32": [P, P, P, I, P],
-    "fiber_solver_finalize": [P, I, F, P, P, P, I, F, F, P],
-    "fiber_adamw_torch_multi_f32": [P, P, P, I, F, F, F, F, P],
-    "fiber_ema_multi_f32": [P, P, P, I, F],
-    "fiber_resize_bicubic_norm_u8": [P, I, P, P, P, I, I, P, P],
-    "fiber_mlm_mask_i64": [P, P, P, L, U64, C.c_uint, I, I, I, I],
-    "fiber_det_resize_norm_pad_u8": [P, I, P, P, P, I, I, I, I, I, I, I, P, P],
-    "fiber_det_boxes_f32": [P, P, I, I],
-    "fiber_crop_resize_flip_u8": [P, P, I, P, P, P, C.c_longlong, I, I],
-    "fiber_randaug_slot_u8": [P, I, P, P, C.c_longlong, P, P, I, P, P, P, P],
-    "fiber_transpose_multi_bf16": [P, I, I],
-    "fiber_rowperm_cast_multi_bf16": [P, I, I],
-    "fiber_dcn_gather_bf16": [P, P, P, P, I, I, I, I, I, I, I, I, I, I],
-    "fiber_dcn_scatter_bf16": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I],
-    "fiber_dcn_dx_bf16": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I],
-    "fiber_ground_fwd_bf16": [P, P, P, P, P, P, P, P, P, I, I, I, I, F, F],
-    "fiber_ground_bwd_bf16": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, F, F],
-    "fiber_det_scores_f32": [P, P, P, P, P, I, I, I, I, F, I],
-    "fiber_det_scores_rows_f32": [P, P, P, P, P, I, I, I, I, F, I, I],
-    "fiber_det_decode_f32": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F],
-    "fiber_det_nms_mask": [P, P, P, P, I, I, F],
-    "fiber_det_nms_select": [P, P, P, P, P, P, P, P, P, P, I, I, I],
-    "fiber_det_merge": [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I],
-    "fiber_det_aug_collect": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I],
-    "fiber_det_aug_merge": [P, P, P, P, P, P, I, I, I, F, I],
-    "fiber_ground_recall": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, DBL, I],
-    "fiber_retrieval_ranks": [P, P, P, P, P, P, P, I, I, C.c_longlong, I],
-    "fiber_ap_match": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I],
-    "fiber_ap_accumulate": [P, P, P, P, P, P, P, C.c_longlong, I, I, I, I],
-    "fiber_atss_candidates_f32": [P, P, I, P, P, P, P, I, I, I, I],
-    "fiber_atss_resolve_f32": [P, P, P, P, P, P, I, I, I, I],
-    "fiber_atss_finalize_f32": [P, P, P, P, P, P, P, P, P, P, I, I, I, I],
-    "fiber_atss_loss_fwd_f32": [P, P, P, P, P, P, P, I, I, I, I, I],
-    "fiber_atss_loss_bwd_f32": [P, P, P, P, P, P, P, P, I, I, I, I],
-    "fiber_dropblock_mask_u8": [P, I, U64, P, F, I, P, P, I, I, I],
-    "fiber_fpn_merge_fwd_bf16": [P, P, P, P, P, P, I, I, I, I, I, I],
-    "fiber_fpn_merge_bwd_bf16": [P, P, P, P, P, P, I, I, I, I, I, I],
-}
-# host-side helpers without a stream argument
-PLAIN = {"fiber_layernorm_bwd_grid": [I], "fiber_window_attn_bwd_slices": [I, I], "fiber_window_attn_colsum_rows": [I, I, I], "fiber_colsum_slabs": [I, I], "fiber_colsum_labelled_slabs": [I], "fiber_colsum_labelled_max_rows": [], "fiber_gemm_row_tile": [I, I, I], "fiber_gemm_tn_splits": [I, I, I],
-         "fiber_adamw_chunk": [], "fiber_resample_ksize": [I, I], "fiber_resample_ksize_bilinear": [I, I], "fiber_dcn_dx_workspace": [I, I, I, I, I, I, I],
-         "fiber_roberta_embed_bwd_workspace": [I, I, I], "fiber_ground_workspace": [I, I, I], "fiber_det_max_candidates": [], "fiber_det_merge_max_candidates": [], "fiber_det_aug_max_candidates": [],
-         "fiber_ap_max_gt": [], "fiber_ap_chunk": [],
-         "fiber_atss_num_candidates": [P, I, I], "fiber_atss_loss_rows": [I, I]}
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fiber_hip.h")                 # the one statement of the C ABI
 
-PLAIN_LONG = {"fiber_dcn_dx_workspace", "fiber_roberta_embed_bwd_workspace", "fiber_ground_workspace"}          # helpers returning a 64-bit count
-_lib = None
+# C parameter type (without const) -> ctypes; anything with a `*` is a pointer.  Everything else is refused, never guessed.
+_SCALAR = {"int": I, "long": L, "long long": C.c_longlong, "unsigned": C.c_uint, "unsigned int": C.c_uint, "uint64_t": U64,
+           "unsigned long long": U64, "float": F, "double": DBL}
+_RETURN = {"int": I, "long": L}
+_STREAM = "fiber_stream_t"
 
 
 class FiberHipError(RuntimeError):
     pass
+
+
+def _param(p, proto):
+    """ctypes type of one named parameter of `proto`."""
+    if re.search(r"[()\[\]]", p):
+        raise FiberHipError(f"fiber_hip.h: function-pointer or array parameter '{p}' in: {proto}")
+    if "*" in p:
+        return P
+    words = [w for w in p.split() if w != "const"]
+    ctype = _SCALAR.get(" ".join(words[:-1]))
+    if ctype is None or any(words[-1] in t.split() for t in _SCALAR):
+        raise FiberHipError(f"fiber_hip.h: no ctypes mapping for parameter '{p}' (each needs a known type and a name) in: {proto}")
+    return ctype
+
+
+def parse_header(text):
+    """(signatures, plain, restypes, defines) of the declarations in `text`, which is C in the narrow subset fiber_hip.h keeps:
+    comments, preprocessor lines, one `<ret> fiber_<name>(<named params>);` per entry point and `#define FIBER_<NAME> <int>`.
+    A prototype whose last parameter is the stream is a call() entry (argument types listed without the stream), one without a
+    stream a plain() helper.  Raises FiberHipError naming the prototype for anything outside that subset."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    defines = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(FIBER_\w+)[ \t]+(.*\S)[ \t]*$", text, flags=re.M):
+        try:
+            defines[name] = int(value, 0)
+        except ValueError:
+            raise FiberHipError(f"fiber_hip.h: #define {name} {value} is not an integer literal") from None
+    text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{', " ", text, flags=re.M)
+    signatures, plain, restypes = {}, {}, {}
+    for stmt in text.split(";"):
+        if not re.search(r"\bfiber_\w+\s*\(", stmt):
+            continue
+        proto = " ".join(stmt.split())
+        m = re.fullmatch(r"(.*?)\b(fiber_\w+) ?\((.*)\)", proto)
+        if m is None:
+            raise FiberHipError(f"fiber_hip.h: cannot split the declaration: {proto}")
+        ret, name, params = m.group(1).strip(), m.group(2), m.group(3).strip()
+        if ret not in _RETURN:
+            raise FiberHipError(f"fiber_hip.h: no ctypes mapping for return type '{ret}' in: {proto}")
+        params = [] if params in ("", "void") else [p.strip() for p in params.split(",")]
+        has_stream = bool(params) and params[-1].split()[:1] == [_STREAM] and "*" not in params[-1]
+        if has_stream:
+            params.pop()
+        if any(_STREAM in p for p in params):
+            raise FiberHipError(f"fiber_hip.h: the stream must be the last parameter, by value, in: {proto}")
+        (signatures if has_stream else plain)[name] = [_param(p, proto) for p in params]
+        restypes[name] = _RETURN[ret]
+    return signatures, plain, restypes, defines
+
+
+def read_header(path=HEADER_PATH):
+    try:
+        with open(path) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise FiberHipError(f"C ABI header {path} not readable ({e.strerror}); the binding is derived from it") from None
+
+
+# name -> argtypes without the stream (call() appends it); name -> argtypes of the helpers without a stream; name -> restype;
+# the header's FIBER_<NAME> integer constants (return codes, FIBER_DOT_PARTS, the act bits of fiber_gemm_nt_bf16).  Read once, here:
+# tools index these tables before (or without) load().
+SIGNATURES, PLAIN, RESTYPES, DEFINES = read_header()
+_RC_TEXT = {DEFINES["FIBER_EINVAL"]: "invalid argument", DEFINES["FIBER_ELAUNCH"]: "launch failure"}
+_lib = None
 
 
 def load():
@@ -122,14 +100,10 @@ def load():
         raise FiberHipError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                             "or `make -C fiber_amd/csrc` (there is no fallback path)")
     lib = C.CDLL(LIB_PATH)
-    for name, args in SIGNATURES.items():
+    for name, restype in RESTYPES.items():
         fn = getattr(lib, name)
-        fn.argtypes = args + [P]
-        fn.restype = I
-    for name, args in PLAIN.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = L if name in PLAIN_LONG else I
+        fn.argtypes = SIGNATURES[name] + [P] if name in SIGNATURES else PLAIN[name]
+        fn.restype = restype
     _lib = lib
     return lib
 
@@ -160,8 +134,8 @@ def call(name, *args):
         ev.record(cur)
         _TRACE.append((stream, name, [a for a in args if isinstance(a, (int, float))], ev))
         del _TRACE[:-4000]
-    if rc != 0:
-        raise FiberHipError(f"{name} failed with code {rc} ({ {1: 'invalid argument', 2: 'launch failure'}.get(rc, '?')})")
+    if rc != DEFINES["FIBER_OK"]:
+        raise FiberHipError(f"{name} failed with code {rc} ({_RC_TEXT.get(rc, '?')})")
 
 
 def plain(name, *args):

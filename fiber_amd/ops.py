@@ -255,6 +255,11 @@ def start_stream(t16):
     return t16
 
 
+# the `act` argument of fiber_gemm_nt_bf16, as include/fiber_hip.h defines it
+ACT_GELU, ACT_GELU_BWD = lib.DEFINES["FIBER_ACT_GELU"], lib.DEFINES["FIBER_ACT_GELU_BWD"]
+ACT_OUT_F32, ACT_STREAM_F32 = lib.DEFINES["FIBER_ACT_OUT_F32"], lib.DEFINES["FIBER_ACT_STREAM_F32"]
+
+
 def gemm_nt(x2, wb, bias=None, residual=None, act=0, want_pre=False, rowscale=None, rows_per_sample=0, aux=None,
             want_colsum=False, out_fp32=False, res32=None):
     """y = act(x2 @ wb^T + bias) + residual  on the HIP kernel.  x2 [M,K] bf16 (row stride may exceed K).
@@ -269,12 +274,13 @@ def gemm_nt(x2, wb, bias=None, residual=None, act=0, want_pre=False, rowscale=No
         y16 = torch.empty((M, N), dtype=BF16, device=x2.device)
         y32 = torch.empty((M, N), dtype=torch.float32, device=x2.device)
         lib.call("fiber_gemm_nt_bf16", lib.ptr(x2), lib.ptr(wb), lib.ptr(bias), lib.ptr(res32), lib.ptr(y16), lib.ptr(y32),
-                 lib.ptr(rowscale), rows_per_sample, None, 0, None, M, N, K, x2.stride(0), wb.stride(0), N, res32.stride(0), 0x800)
+                 lib.ptr(rowscale), rows_per_sample, None, 0, None, M, N, K, x2.stride(0), wb.stride(0), N, res32.stride(0),
+                 ACT_STREAM_F32)
         return y16, y32
     y = torch.empty((M, N), dtype=torch.float32 if out_fp32 else BF16, device=x2.device)
     if out_fp32:
         assert not act and residual is None and not want_colsum
-        act = 0x100
+        act = ACT_OUT_F32
     pre = torch.empty((M, N), dtype=BF16, device=x2.device) if (want_pre and act) else None
     colpart = None
     if want_colsum:
@@ -738,7 +744,7 @@ def linear(x, weight, bias=None, residual=None, act=None, rowscale=None, rowscal
             y = torch.nn.functional.gelu(y)
         assert rowscale is None
         return y + residual if residual is not None else y
-    y, y32 = _Linear.apply(x, weight, bias, residual, 1 if act else 0, rowscale, rowscale_value, f32_of(residual))
+    y, y32 = _Linear.apply(x, weight, bias, residual, ACT_GELU if act else 0, rowscale, rowscale_value, f32_of(residual))
     return with_f32(y, y32)
 
 
@@ -756,7 +762,7 @@ class _MLP(torch.autograd.Function):
         shp = x.shape
         x2 = _c(x).view(-1, shp[-1])
         need_bwd = any(ctx.needs_input_grad[:5])            # inference (no_grad / frozen): the pre-activation copy is not stored
-        g, h = gemm_nt(x2, bf16_weight(w1), b1, None, 1, need_bwd)
+        g, h = gemm_nt(x2, bf16_weight(w1), b1, None, ACT_GELU, need_bwd)
         rps = (x2.shape[0] // rowscale.numel()) if rowscale is not None else 0
         oshp = (*shp[:-1], w2.shape[0])
         if res32 is not None:                         # fp32 residual stream: (bf16 shadow, fp32 payload)
@@ -798,7 +804,7 @@ class _MLP(torch.autograd.Function):
                          dy2.numel() // rowscale.numel())
                 dy2 = ds
         if fused:
-            dh, _ = gemm_nt(dy2, bf16_weight_t(w2), None, None, 2, False, rs_arg, rps, aux=h)
+            dh, _ = gemm_nt(dy2, bf16_weight_t(w2), None, None, ACT_GELU_BWD, False, rs_arg, rps, aux=h)
             db1 = None
         else:                                         # shapes the DMA kernel does not cover (e.g. Swin-T C=96)
             dh, db1 = gelu_bwd_colsum(_dgrad(dy2, w2), h)
@@ -1528,7 +1534,7 @@ def mha_decode_cross(q, kv, rows_per_image, heads, scale):
     return o
 
 
-_DOT_PARTS = 512      # workspace floats of fiber_dot_bf16 / the d alpha of fiber_stream_add_bwd (FIBER_DOT_PARTS, csrc/common.h)
+_DOT_PARTS = lib.DEFINES["FIBER_DOT_PARTS"]      # workspace floats of fiber_dot_bf16 / the d alpha of fiber_stream_add_bwd
 
 
 class _ScaleAdd(torch.autograd.Function):

@@ -8,8 +8,14 @@
  * Conventions: every pointer is a DEVICE pointer; "bf16" buffers are passed as void* (uint16 storage, row-major);
  * fp32 is used for parameters of normalisation/bias, statistics and gradient accumulators; `stream` is a hipStream_t
  * (the caller's current stream -- kernels are stream-ordered, re-entrant, and never synchronise the host);
- * return value 0 = ok, 1 = invalid argument (shape/alignment contract violated), 2 = launch failure.
+ * the return value is one of the FIBER_ codes below.
  * Inputs are borrowed and never mutated; outputs and workspaces are caller-allocated.
+ *
+ * This file is the one statement of the ABI.  csrc/common.h includes it, so the compiler checks every definition against its
+ * declaration, and fiber_amd/lib.py derives its ctypes prototypes and constants from it (lib.parse_header).  Keep it in the subset that
+ * reader takes: comments, preprocessor lines, `#define FIBER_<NAME> <integer literal>` and one `int|long fiber_<name>(<named parameters>);`
+ * per entry point, with scalar parameters of type int, long, long long, unsigned [int], unsigned long long, uint64_t, float or double,
+ * and `fiber_stream_t stream` last where the entry point launches.
  */
 #ifndef FIBER_HIP_H
 #define FIBER_HIP_H
@@ -19,16 +25,40 @@ extern "C" {
 #endif
 typedef struct ihipStream_t* fiber_stream_t;
 
+/* Return value of every entry point that takes a stream: ok; invalid argument (a shape / alignment / pointer contract stated below is
+ * violated, nothing was launched); launch failure. */
+#define FIBER_OK 0
+#define FIBER_EINVAL 1
+#define FIBER_ELAUNCH 2
+/* Workspace floats of fiber_dot_bf16 and of fiber_stream_add_bwd's d alpha: one partial per workgroup, at most this many workgroups. */
+#define FIBER_DOT_PARTS 512
+
+/* The `act` argument of fiber_gemm_nt_bf16: an epilogue mode in the low byte, or-ed with option bits.
+ * Modes: 0 none; FIBER_ACT_GELU = exact-erf GELU (Ypre, if non-NULL, gets the pre-activation); FIBER_ACT_GELU_BWD = fused GELU backward. */
+#define FIBER_ACT_GELU 1
+#define FIBER_ACT_GELU_BWD 2
+/* Mode 0 without residual: Y is fp32 [M, ldy] -- narrow outputs whose consumers need more than bf16 (the offset predictor of the
+ * deformable convolutions: sampling positions).  Register-staged kernels only. */
+#define FIBER_ACT_OUT_F32 0x100
+/* Mode 0, residual required: the fp32 RESIDUAL STREAM form of the residual epilogue, described under the prototype. */
+#define FIBER_ACT_STREAM_F32 0x800
+/* tools/gemm_trace.py: the per-phase timing build of the q8 kernel; `colpart` receives the clock readings. */
+#define FIBER_ACT_TRACE 0x1000
+/* Set by the entry point itself, callers leave them clear: the output is larger than the last-level cache and is stored non-temporally;
+ * keep the two wave groups' stagger across tiles (FIBER_GEMM_STAGGER=1, A/B runs). */
+#define FIBER_ACT_NT_STORES 0x2000
+#define FIBER_ACT_KEEP_STAGGER 0x4000
+
 /* nn.Linear (+bias, +exact-erf GELU, +per-sample DropPath scale, +residual) : Y = rowscale*act(X.W^T + bias) + R
  * replaces: swin_transformer.py:197,221,233,238,257 (qkv/proj/i2t linears), timm Mlp fc1/fc2 (:325), PatchMerging.reduction
- * (:431), roberta.py:231-241,337,398,415, fiber_module.py:349-350.  act: 0 none, 1 GELU (Ypre, if non-NULL, gets the
- * pre-activation).  Requires K%8==0, N%4==0, ldx/ldw%8==0, ldy/ldr%4==0. */
-/* act 2 = fused GELU backward: Y = rowscale * (X.W^T) * gelu'(aux) with aux = saved pre-activation [M, ldaux];
+ * (:431), roberta.py:231-241,337,398,415, fiber_module.py:349-350.  act: the FIBER_ACT_ values above.
+ * Requires K%8==0, N%4==0, ldx/ldw%8==0, ldy/ldr%4==0. */
+/* FIBER_ACT_GELU_BWD: Y = rowscale * (X.W^T) * gelu'(aux) with aux = saved pre-activation [M, ldaux];
  * colpart (nullable) receives per-row-tile column sums of Y, [ceil(M / fiber_gemm_row_tile(M,N,K)), N] fp32 (bias gradient). */
 int fiber_gemm_nt_bf16(const void* X, const void* W, const float* bias, const void* residual, void* Y, void* Ypre,
                        const float* rowscale, int rows_per_sample, const void* aux, int ldaux, float* colpart, int M, int N,
                        int K, int ldx, int ldw, int ldy, int ldr, int act, fiber_stream_t stream);
-/* act | 0x800 (act 0, residual required) = the fp32 RESIDUAL STREAM form of the residual epilogue (x = x + branch of
+/* FIBER_ACT_STREAM_F32 = the fp32 RESIDUAL STREAM form of the residual epilogue (x = x + branch of
  * swin_transformer.py:388-391, dense + input_tensor of roberta.py:417-423,485 -- the reference keeps these sums in fp32):
  * `residual` is fp32 [M, ldr]; the sum is stored in fp32 at Ypre viewed as float [M, ldy] and, if Y is non-NULL, once more
  * rounded to bf16 at Y (the copy GEMM consumers of the stream read). */

@@ -1,4 +1,4 @@
-"""s_memtime trace of the q8 GEMM's K loop (TRACE build, act bit 0x1000): cycles per K tile spent in each phase's load half /
+"""s_memtime trace of the q8 GEMM's K loop (TRACE build, act bit FIBER_ACT_TRACE): cycles per K tile spent in each phase's load half /
 wait+barrier / MFMA issue / barrier, for the first 8 workgroups x 8 waves.    python tools/gemm_trace.py q8"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -7,7 +7,7 @@ from fiber_amd import lib
 lib.load()
 
 def q8(M, N, K, act=0):
-    """Per-wave, per-phase totals of the q8 kernel (TRACE build, act bit 0x1000): cycles per K tile."""
+    """Per-wave, per-phase totals of the q8 kernel (TRACE build, act bit FIBER_ACT_TRACE): cycles per K tile."""
     x = torch.randn(M, K, device="cuda").to(torch.bfloat16)
     w = (torch.randn(N, K, device="cuda") * K ** -0.5).to(torch.bfloat16)
     b = torch.randn(N, device="cuda")
@@ -16,7 +16,7 @@ def q8(M, N, K, act=0):
     dbg = torch.zeros(8 * 8 * 24, device="cuda")
     for _ in range(int(os.environ.get("FIBER_TRACE_LAUNCHES", "3"))):     # (a clock reading wants >= 2 s of back-to-back launches)
         lib.call("fiber_gemm_nt_bf16", lib.ptr(x), lib.ptr(w), lib.ptr(b), None, lib.ptr(y), lib.ptr(pre), None, 0, None, 0, lib.ptr(dbg),
-                 M, N, K, K, K, N, 0, 0x1000 | act)
+                 M, N, K, K, K, N, 0, lib.DEFINES["FIBER_ACT_TRACE"] | act)
     torch.cuda.synchronize()
     d = dbg.view(8, 8, 24).cpu()
     nk, T = d[0, 0, 18].item(), d[0, 0, 19].item()
