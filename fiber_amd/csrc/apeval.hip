@@ -11,6 +11,8 @@
 // ballots + popcounts carried as integers; the chunks are walked from the last to the first so that the running maximum of the precision
 // from the right is one carried double; the record at which the recall first reaches a threshold writes that threshold's precision.
 // fp64 throughout, contraction off, no fast-math: every division is the correctly rounded one.
+// The COCO protocol (pycocotools' COCOeval for boxes, which the reference calls at evaluation/coco/coco_eval.py:366-386) shares the walk,
+// the key and the accumulation; its matching kernel differs in the crowd rule and in a cap per (image, category): ap_match_coco_kernel.
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -20,6 +22,7 @@ namespace {
 constexpr int AP_MAX_GT = 4096;                            // 64 lanes x the 64 bits of a lane's matched word
 constexpr int AP_CHUNK = 64;
 constexpr int AP_ACC_WAVES = 4;
+constexpr int AP_COCO_MAX_CAT = 4096;                      // one int of dynamic LDS per category: at most 16 KiB for the one wave of a workgroup
 typedef unsigned long long u64;
 
 // (non-ignored, IoU, index) of lane `o` against this lane's: the larger key stays.  ni < 0: no candidate.
@@ -114,6 +117,114 @@ __global__ __launch_bounds__(64) void ap_match_kernel(const float* __restrict__ 
         if (ig) atomicOr(&ignore[slot], bit);
       }
       if (first) valid[slot] = v ? 1 : 0;
+    }
+  }
+}
+
+// COCOeval.evaluateImg for boxes: the LVIS kernel's walk with the COCO API's crowd rule and its cap per (image, category).  A crowd ground
+// truth divides by the detection's area, is never consumed (no bit in `taken`) and counts as ignored; a detection whose rank within its
+// category reaches `cap` is skipped by every wave.  The rank counters live in LDS, one per category: the counter of category c is read and
+// advanced by lane c & 63 alone and broadcast, so no two lanes ever touch one address and the single wave needs no barrier after the
+// zeroing.  Every branch around the shuffles is wave-uniform (d, n and the label are).
+__global__ __launch_bounds__(64) void ap_match_coco_kernel(const float* __restrict__ boxes, const int* __restrict__ labels,
+                                                           const int* __restrict__ count, const double* __restrict__ gt,
+                                                           const double* __restrict__ gt_area, const int* __restrict__ gt_cat,
+                                                           const unsigned char* __restrict__ gt_crowd, const int* __restrict__ gt_count,
+                                                           const double* __restrict__ iou_thrs, const double* __restrict__ area_rng,
+                                                           u64* __restrict__ match, u64* __restrict__ ignore, int* __restrict__ rank,
+                                                           unsigned char* __restrict__ valid, u64* __restrict__ num_gt, int D, int G, int C,
+                                                           int T, int A, int cap, int plus_one) {
+  extern __shared__ int seen[];                            // C ints: the detections of each category met so far in this image
+  const int lane = threadIdx.x;
+  const int p = blockIdx.x;                                // (b * A + a) * T + t
+  const int t = p % T, a = (p / T) % A, b = p / (T * A);
+  const int n = min(max(count[b], 0), D);
+  const int gc = min(max(gt_count[b], 0), G);
+  const int nchunk = (gc + 63) >> 6;
+  const double lo = area_rng[2 * a], hi = area_rng[2 * a + 1];
+  const double thr = fmin(iou_thrs[t], 1.0 - 1e-10);
+  const u64 bit = 1ull << (a * T + t);
+  const bool first = a == 0 && t == 0;
+  const double* g4 = gt + (size_t)b * G * 4;
+  const double* ga = gt_area + (size_t)b * G;
+  const int* gcat = gt_cat + (size_t)b * G;
+  const unsigned char* gcr = gt_crowd + (size_t)b * G;
+  for (int i = lane; i < C; i += 64) seen[i] = 0;          // C <= AP_COCO_MAX_CAT; index i belongs to lane i & 63
+  __syncthreads();
+
+  if (t == 0) {                                            // per (category, area range)
+    for (int g = lane; g < gc; g += 64) {
+      const int c = gcat[g];
+      const bool ig = gcr[g] != 0 || ga[g] < lo || ga[g] > hi;
+      if ((unsigned)c < (unsigned)C && !ig) atomicAdd(&num_gt[(size_t)c * A + a], 1ull);
+    }
+  }
+
+  u64 taken = 0;                                           // bit j: ground truth j * 64 + lane is matched at this (a, t); never a crowd one
+  for (int d = 0; d < D; ++d) {
+    const size_t slot = (size_t)b * D + d;
+    if (d >= n) {                                          // match / ignore were zeroed before the launch
+      if (first && lane == 0) {
+        rank[slot] = -1;
+        valid[slot] = 0;
+      }
+      continue;
+    }
+    const int c = labels[slot] - 1;
+    const bool known = (unsigned)c < (unsigned)C;
+    int r = -1;
+    if (known) {
+      int mine = 0;
+      if (lane == (c & 63)) {
+        mine = seen[c];
+        seen[c] = mine + 1;
+      }
+      r = __shfl(mine, c & 63, 64);
+    }
+    const bool v = known && r < cap;                       // only the first maxDets[-1] of an (image, category) exist
+    if (first && lane == 0) {
+      rank[slot] = r;
+      valid[slot] = v ? 1 : 0;
+    }
+    if (!v) continue;
+    const f32x4 bx = *reinterpret_cast<const f32x4*>(boxes + slot * 4);
+    float wf = bx[2] - bx[0], hf = bx[3] - bx[1];
+    if (plus_one) {                                        // BoxList.convert("xywh"): + TO_REMOVE, a second fp32 rounding
+      wf = wf + 1.0f;
+      hf = hf + 1.0f;
+    }
+    const double dx = (double)bx[0], dy = (double)bx[1], dw = (double)wf, dh = (double)hf;
+    const double da = dw * dh;
+    int ni = -1, bg = -1;
+    double biou = 0.0;
+    for (int j = 0; j < nchunk; ++j) {
+      const int g = (j << 6) + lane;
+      if (g >= gc || gcat[g] != c) continue;
+      const bool crowd = gcr[g] != 0;
+      if (!crowd && ((taken >> j) & 1ull)) continue;       // a crowd region can be matched again
+      const double gx = g4[g * 4], gy = g4[g * 4 + 1], gw = g4[g * 4 + 2], gh = g4[g * 4 + 3];
+      const double iw = fmin(dx + dw, gx + gw) - fmax(dx, gx);
+      const double ih = fmin(dy + dh, gy + gh) - fmax(dy, gy);
+      const double inter = (iw <= 0.0 || ih <= 0.0) ? 0.0 : iw * ih;
+      const double iou = crowd ? inter / da : inter / (da + gw * gh - inter);
+      if (!(iou >= thr)) continue;                         // also a NaN from a detection of no area
+      const bool ig = crowd || ga[g] < lo || ga[g] > hi;
+      key_max(ni, biou, bg, ig ? 0 : 1, iou, g);
+    }
+    if (__ballot(ni >= 0) != 0ull) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const int oni = __shfl_xor(ni, o, 64), og = __shfl_xor(bg, o, 64);
+        const double oiou = __shfl_xor(biou, o, 64);
+        key_max(ni, biou, bg, oni, oiou, og);
+      }
+      if (lane == (bg & 63) && gcr[bg] == 0) taken |= 1ull << (bg >> 6);
+    }
+    if (lane == 0) {
+      const bool m = ni >= 0;
+      const bool ig = m ? ni == 0 : (da < lo || da > hi);
+      if (m) atomicOr(&match[slot], bit);
+      if (ig) atomicOr(&ignore[slot], bit);
     }
   }
 }
@@ -229,6 +340,33 @@ extern "C" int fiber_ap_match(const float* boxes, const int* labels, const int* 
   hipLaunchKernelGGL(ap_match_kernel, dim3((unsigned)(B * T * A)), dim3(64), 0, stream, boxes, labels, count, gt, gt_area, gt_cat, gt_ignore,
                      gt_count, neg_mask, nel_mask, iou_thrs, area_rng, match, ignore, valid, reinterpret_cast<u64*>(num_gt), D, G, C,
                      (C + 63) / 64, T, A, max_dets);
+  FIBER_CHECK_LAUNCH();
+  return FIBER_OK;
+}
+
+extern "C" int fiber_ap_coco_max_categories(void) { return AP_COCO_MAX_CAT; }
+
+extern "C" int fiber_ap_match_coco(const float* boxes, const int* labels, const int* count, const double* gt, const double* gt_area,
+                                   const int* gt_cat, const unsigned char* gt_crowd, const int* gt_count, const double* iou_thrs,
+                                   const double* area_rng, unsigned long long* match, unsigned long long* ignore, int* rank,
+                                   unsigned char* valid, long long* num_gt, int B, int D, int G, int C, int T, int A, int cap, int plus_one,
+                                   hipStream_t stream) {
+  if (B < 0 || D < 0 || G < 0 || C <= 0 || T <= 0 || A <= 0 || cap < 0 || (plus_one != 0 && plus_one != 1)) return FIBER_EINVAL;
+  if ((long long)T * A > 64 || G > AP_MAX_GT || C > AP_COCO_MAX_CAT) return FIBER_EINVAL;
+  if ((long long)B * T * A > 0x7fffffffLL || (long long)B * D > 0x7fffffffLL) return FIBER_EINVAL;
+  if (B == 0) return FIBER_OK;
+  if (!count || !gt_count || !iou_thrs || !area_rng || !num_gt) return FIBER_EINVAL;
+  if (D > 0 && (!boxes || !labels || !match || !ignore || !rank || !valid)) return FIBER_EINVAL;
+  if (G > 0 && (!gt || !gt_area || !gt_cat || !gt_crowd)) return FIBER_EINVAL;
+  if (fiber_misaligned(16, boxes) || fiber_misaligned(8, gt, gt_area, iou_thrs, area_rng, match, ignore, num_gt) ||
+      fiber_misaligned(4, labels, count, gt_cat, gt_count, rank))
+    return FIBER_EINVAL;
+  if (D > 0) {
+    if (hipMemsetAsync(match, 0, (size_t)B * D * 8, stream) != hipSuccess) return FIBER_ELAUNCH;
+    if (hipMemsetAsync(ignore, 0, (size_t)B * D * 8, stream) != hipSuccess) return FIBER_ELAUNCH;
+  }
+  hipLaunchKernelGGL(ap_match_coco_kernel, dim3((unsigned)(B * T * A)), dim3(64), (size_t)C * sizeof(int), stream, boxes, labels, count, gt, gt_area, gt_cat, gt_crowd,
+                     gt_count, iou_thrs, area_rng, match, ignore, rank, valid, reinterpret_cast<u64*>(num_gt), D, G, C, T, A, cap, plus_one);
   FIBER_CHECK_LAUNCH();
   return FIBER_OK;
 }

@@ -2635,6 +2635,48 @@ def ap_accumulate(match, ignore, seg_ptr, num_gt, rec_thrs, T):
     return precision, recall
 
 
+def ap_coco_max_categories():
+    return int(lib.plain("fiber_ap_coco_max_categories"))
+
+
+def ap_match_coco(boxes, labels, count, gt, gt_area, gt_cat, gt_crowd, gt_count, iou_thrs, area_rng, num_gt, cap, plus_one=True):
+    """One launch of fiber_ap_match_coco (the COCO protocol: crowd rule, cap per (image, category)), no host synchronisation.  boxes fp32
+    [B, D, 4] xyxy in the original frame, labels int32 [B, D] (category index + 1), count int32 [B]; gt fp64 [B, G, 4] xywh, gt_area fp64
+    [B, G], gt_cat int32 [B, G], gt_crowd uint8 [B, G], gt_count int32 [B]; iou_thrs fp64 [T], area_rng fp64 [A, 2]; num_gt int64 [C, A]
+    is accumulated IN PLACE; cap = maxDets[-1]; plus_one: the reference's + TO_REMOVE on the detection's extents.
+    -> (match int64 [B, D], ignore int64 [B, D] (bit a * T + t), rank int32 [B, D], valid uint8 [B, D])."""
+    B, D = boxes.shape[:2]
+    G = gt.shape[1]
+    C, A = num_gt.shape
+    T = iou_thrs.numel()
+    if boxes.shape != (B, D, 4) or labels.shape != (B, D) or count.shape != (B,) or gt.shape != (B, G, 4) or gt_area.shape != (B, G) or \
+            gt_cat.shape != (B, G) or gt_crowd.shape != (B, G) or gt_count.shape != (B,) or area_rng.shape != (A, 2):
+        raise ValueError(f"ap_match_coco: boxes {tuple(boxes.shape)}, labels {tuple(labels.shape)}, gt {tuple(gt.shape)}, gt_crowd "
+                         f"{tuple(gt_crowd.shape)}, area_rng {tuple(area_rng.shape)} for A = {A}")
+    if labels.dtype != torch.int32 or count.dtype != torch.int32 or gt.dtype != torch.float64 or gt_area.dtype != torch.float64 or \
+            gt_cat.dtype != torch.int32 or gt_crowd.dtype != torch.uint8 or gt_count.dtype != torch.int32 or \
+            iou_thrs.dtype != torch.float64 or area_rng.dtype != torch.float64 or num_gt.dtype != torch.int64 or not num_gt.is_contiguous():
+        raise ValueError("ap_match_coco: gt / gt_area / iou_thrs / area_rng fp64, labels / count / gt_cat / gt_count int32, gt_crowd uint8, "
+                         "num_gt (contiguous) int64")
+    if T * A > 64:
+        raise ValueError(f"ap_match_coco: {T} thresholds x {A} area ranges exceed the 64 bits of a record's match word")
+    if G > ap_max_gt():
+        raise ValueError(f"ap_match_coco: {G} ground-truth boxes per image exceed the kernel's capacity of {ap_max_gt()}")
+    if C > ap_coco_max_categories():
+        raise ValueError(f"ap_match_coco: {C} categories exceed the kernel's {ap_coco_max_categories()} rank counters")
+    if int(cap) < 0:
+        raise ValueError(f"ap_match_coco: cap {cap}: the largest maxDets, not negative")
+    dev = boxes.device
+    match = torch.empty((B, D), dtype=torch.int64, device=dev)
+    ignore = torch.empty((B, D), dtype=torch.int64, device=dev)
+    rank = torch.empty((B, D), dtype=torch.int32, device=dev)
+    valid = torch.empty((B, D), dtype=torch.uint8, device=dev)
+    lib.call("fiber_ap_match_coco", lib.ptr(_det_f32(boxes)), lib.ptr(_c(labels)), lib.ptr(_c(count)), lib.ptr(_c(gt)), lib.ptr(_c(gt_area)),
+             lib.ptr(_c(gt_cat)), lib.ptr(_c(gt_crowd)), lib.ptr(_c(gt_count)), lib.ptr(_c(iou_thrs)), lib.ptr(_c(area_rng)), lib.ptr(match),
+             lib.ptr(ignore), lib.ptr(rank), lib.ptr(valid), lib.ptr(num_gt), B, D, G, C, T, A, int(cap), 1 if plus_one else 0)
+    return match, ignore, rank, valid
+
+
 # ---- grounding training: ATSS assignment + GIoU / centerness losses (csrc/atss.hip) --------------------------------------------------
 class Assignment:
     """ops.atss_assign's result, fixed shapes: matched int32 [B, A] (-1 unassigned), labels int32 [B, A] (0), reg_targets fp32 [B, A, 4]

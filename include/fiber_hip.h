@@ -561,6 +561,33 @@ int fiber_ap_accumulate(const unsigned long long* match, const unsigned long lon
                         const double* rec_thrs, double* precision, double* recall, long long N, int C, int T, int A, int R,
                         fiber_stream_t stream);
 
+/* Box average precision by the COCO protocol (csrc/apeval.hip): evaluateImg of pycocotools' COCOeval for boxes, which the reference calls
+ * at fine_grained/maskrcnn_benchmark/data/datasets/evaluation/coco/coco_eval.py:366-386.  PARITY UNPINNED against the pycocotools binary:
+ * the rule below is implemented from its statement.  fiber_ap_accumulate then serves both protocols.
+ * fiber_ap_match_coco: one wave per (image, area range, threshold), detections walked in their stored descending-score order.
+ * boxes fp32 [B,D,4] xyxy in the ORIGINAL image frame, labels int32 [B,D] (category index + 1), count int32 [B]; gt fp64 [B,G,4] xywh,
+ * gt_area fp64 [B,G] (the annotation's own area), gt_cat int32 [B,G], gt_crowd uint8 [B,G] (iscrowd), gt_count int32 [B]; iou_thrs fp64
+ * [T], area_rng fp64 [A,2].  There are no federated lists: every category is evaluated in every image.
+ * rank int32 [B,D]: the number of earlier slots d' < d < min(count, D) of the image with the same label, for a label in 1..C; -1 for a
+ * slot past min(count, D) or a label outside 1..C.  valid uint8 [B,D]: 1 iff rank is in 0..cap-1 (cap = maxDets[-1]: only the first cap
+ * detections of an (image, category) exist; a later one is skipped at every (area range, threshold), match = ignore = 0).
+ * The detection box is x, y, fp32(x2 - x), fp32(y2 - y), with plus_one = 1 each extent then + 1 in fp32 (prepare_for_coco_detection,
+ * :125-154: BoxList.convert("xywh") adds TO_REMOVE, structures/bounding_box.py:79-81); plus_one = 0 for true xywh extents.  Everything
+ * after it fp64: da = w * h, iw = min(dx + dw, gx + gw) - max(dx, gx), ih likewise, i = 0 if iw <= 0 or ih <= 0 else iw * ih;
+ * iou = i / da against a crowd ground truth, i / (da + gw * gh - i) otherwise.  A ground truth is ignored when it is crowd or its area
+ * field < lo or > hi.  Per (area range, threshold), detections in score order: among the ground truths of the detection's category with
+ * iou >= min(thr, 1 - 1e-10) that are unmatched or crowd, the largest (non-ignored, iou, index) wins; a crowd one is never consumed.
+ * match / ignore uint64 [B,D]: bit a * T + t; a matched detection is ignored iff its ground truth is, an unmatched one iff its own area
+ * is outside the range.  num_gt int64 [C,A]: the non-ignored ground truths, ACCUMULATED in place with integer atomic adds (two runs give
+ * the same bits).  Every element of match, ignore, rank and valid is written.  The ranks are counted in LDS, one counter per category:
+ * C > fiber_ap_coco_max_categories() -> 1.  T * A > 64, G > fiber_ap_max_gt(), negative sizes or cap, plus_one outside {0,1}, NULL or
+ * misaligned pointers -> 1; B == 0 -> 0 without a launch. */
+int fiber_ap_coco_max_categories(void);
+int fiber_ap_match_coco(const float* boxes, const int* labels, const int* count, const double* gt, const double* gt_area, const int* gt_cat,
+                        const unsigned char* gt_crowd, const int* gt_count, const double* iou_thrs, const double* area_rng,
+                        unsigned long long* match, unsigned long long* ignore, int* rank, unsigned char* valid, long long* num_gt, int B,
+                        int D, int G, int C, int T, int A, int cap, int plus_one, fiber_stream_t stream);
+
 /* Grounding training: ATSS target assignment and the box / centerness losses with fixed shapes and no host synchronisation
  * (csrc/atss.hip); file:line relative to the reference's fine_grained/maskrcnn_benchmark/.  Targets: gt_boxes fp32 [B,Gmax,4] (xyxy),
  * gt_labels int32 [B,Gmax], num_gt int32 [B], positive_map uint8 [B,Gmax,T]; rows g >= num_gt[b] are never read.  anchors fp32 [A,4]: the
